@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- clips/sec of the NISQA predict hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -745,7 +745,14 @@ def main():
     ap.add_argument('--leg', default='all', choices=['all', 'main', 'tts', 'train', 'csv', 'dir'],
                     help='profiling runs: only this part (main = the contract workload without side legs)')
     ap.add_argument('--no-side', action='store_true', help='skip the side legs (configs[2], [3], [4])')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help='write what the timed path returned in its last step to DIR/<name>.npy (float32), for output-for-output '
+                         'comparison of two builds on the same inputs')
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error('--steps must be at least 1')
+    if a.dump_outputs and (a.workload != 'predict_dir' or a.leg not in ('all', 'main')):
+        ap.error('--dump-outputs covers the contract workload (predict_dir, --leg all / main)')
     if a.gpus > 1 and int(os.environ.get('WORLD_SIZE', '1')) == 1:   # plain `python bench.py --gpus N`: launch the ranks ourselves
         sys.exit(self_launch(a.gpus))
     BATCH = a.batch
@@ -834,6 +841,13 @@ def main():
     if rank == 0:
         if os.environ.get('NISQA_BENCH_KO') != '1':           # knock-out builds (tools/ab_build.sh -DNQ_KO=..) compute garbage
             assert torch.isfinite(outs[-1]).all()
+        dumped = None
+        if a.dump_outputs:                                    # the last timed step's [B, heads] rows of every rank, as a caller gets them
+            last = torch.cat([p[-BATCH:] for p in parts], 0) if world > 1 else outs[-1]
+            dumped = {'predictions': last.detach().to('cpu', torch.float32).numpy()}
+            os.makedirs(a.dump_outputs, exist_ok=True)
+            for n_, arr in dumped.items():
+                np.save(os.path.join(a.dump_outputs, n_ + '.npy'), np.ascontiguousarray(arr))
         names = ['mel', 'cnn_front', 'cnn_back', 'selfatt', 'pool']
         for s in range(a.steps):                              # second pass, untimed: all six stage events
             with torch.cuda.stream(streams[s % len(streams)]):
@@ -916,6 +930,9 @@ def main():
                                    'avg_launch_ms': round(stage_ms['mel'], 4)},
             'kernels': kern_tab,
         }
+        if dumped is not None:
+            res['dump_outputs'] = {'dir': a.dump_outputs, 'arrays': {n_: list(v.shape) for n_, v in dumped.items()},
+                                   'what': 'the last timed step: [clips, heads] rows (mos, noi, dis, col, loud) of every rank'}
         if world == 1 and not a.no_extras:
             # the other precision path on the same workload: same --steps / --warmup, same barriers, right after the
             # primary region.  For the default run this is the exact-fp32 path -- the reference's own arithmetic.

@@ -81,3 +81,27 @@ def test_bench_line_carries_the_contract_fields():
     assert 0.5 * d['ms_per_step'] < d['stage_ms']['cnn_front'] < d['ms_per_step']          # the dominant kernel, and it fits the step
     assert set(d['stage_ms']) == {'mel', 'cnn_front', 'cnn_back', 'selfatt', 'pool'}
     assert d['overlap_2_streams']['steps'] >= 200 and d['steady']['steps'] >= 400
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_last_steps_rows_and_repeat_run_to_run(tmp_path):
+    """--dump-outputs DIR: the timed path's last-step rows as DIR/<name>.npy (float32 / float64, <= 64 MB in all), the same
+    from two runs with the same arguments; --steps sets the timed steps the line reports."""
+    import numpy as np
+    dumps = []
+    for i in range(2):
+        d = tmp_path / ('run%d' % i)
+        r = _run(['--steps', '3', '--warmup', '1', '--no-cpu-baseline', '--no-side', '--no-extras', '--dump-outputs', str(d)])
+        assert r.returncode == 0, r.stderr[-3000:]
+        line = json.loads([ln for ln in r.stdout.splitlines() if ln.strip()][-1])
+        assert line['steps'] == 3 and line['ms_per_step'] > 0
+        files = sorted(os.listdir(d))
+        assert files and all(f.endswith('.npy') for f in files)
+        arrs = {f: np.load(d / f) for f in files}
+        assert sum(a.nbytes for a in arrs.values()) <= 64 << 20
+        assert all(a.dtype in (np.float32, np.float64) for a in arrs.values())
+        dumps.append(arrs)
+    rows = dumps[0]['predictions.npy']
+    assert rows.shape == (64, 5) and np.isfinite(rows).all() and rows.std(0).max() > 0
+    for f in dumps[0]:
+        np.testing.assert_array_equal(dumps[0][f], dumps[1][f])

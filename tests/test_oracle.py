@@ -123,16 +123,18 @@ def test_segment_errors():
 
 
 def test_net_oracle_against_live_reference():
-    """Extra pin where the reference tree exists (build container): random clip, live modules."""
+    """Random clip through the live modules where build() staged the reference, else their stored output on the same
+    clip and weights (tests/golden/make_golden_live.py)."""
     from oracle import ref_shim
-    if not ref_shim.reference_available():
-        pytest.skip('reference tree not present')
     args, sd = dict(helpers.DIM_ARGS), helpers.random_state_dict(11, 'NISQA_DIM')
-    model, NL = ref_shim.build_reference_model(args, sd)
     spec = (np.random.default_rng(3).standard_normal((48, 123)) * 20 - 40).astype(np.float32)
-    x, n = NL.segment_specs('t', spec, 15, 4, 1300)
-    with torch.no_grad():
-        ref = model(x.unsqueeze(0), torch.tensor([int(n)])).numpy()[0]
+    if ref_shim.reference_available():
+        model, NL = ref_shim.build_reference_model(args, sd)
+        x, n = NL.segment_specs('t', spec, 15, 4, 1300)
+        with torch.no_grad():
+            ref = model(x.unsqueeze(0), torch.tensor([int(n)])).numpy()[0]
+    else:
+        ref = helpers.golden(helpers.LIVE_FIXTURE)['net_live']
     out = onet.predict_from_melspec(sd, args, spec)
     np.testing.assert_allclose(out, ref, rtol=0, atol=2e-5)
 
@@ -325,21 +327,25 @@ def test_reference_loop_through_the_functional_librosa_stand_in_matches_the_orac
     segment_specs padded to [B, 1300, 1, 48, 15] -> DataLoader -> Framewise pack -> modules; NISQA_lib.py:1420-1467, 2129-2330)
     with librosa's three entry points served by oracle/mel.py -- what the `-m gpu` live-reference test and bench.py's
     cpu_baseline run on the GPU box -- against oracle.net on oracle.mel spectrograms of the same files: mono, stereo (lb.load
-    averages the channels), and one channel picked by ms_channel (mono=False + row select, NISQA_lib.py:2300-2302)."""
+    averages the channels), and one channel picked by ms_channel (mono=False + row select, NISQA_lib.py:2300-2302).
+    Without the staged reference and checkpoint: the loop's stored rows for random weights of the nisqa.tar architecture
+    (tests/golden/make_golden_live.py)."""
     from oracle import ref_shim
     path = helpers.find_weights('nisqa.tar')
-    if path is None or not ref_shim.reference_available():
-        pytest.skip('reference checkpoint / NISQA_lib.py not on this machine (staged under oracle/_ref by build())')
-    from nisqa_amd import synth
-    st = np.stack([synth.synth_pcm16(61, 1.1), synth.synth_pcm16(62, 1.1)], 1)
-    synth.write_wav(str(tmp_path / 'a.wav'), synth.synth_pcm16(60, 1.6), 48000)
-    synth.write_wav(str(tmp_path / 'b_stereo.wav'), st, 48000)
+    live = path is not None and ref_shim.reference_available()
+    if not live:
+        path = helpers.random_checkpoint('nisqa.tar', tmp_path)
+    st = helpers.functional_loop_clips(tmp_path)
     args, sd = helpers.load_checkpoint(path)
-    y = ref_shim.reference_predict(path, str(tmp_path), ['a.wav', 'b_stereo.wav'], bs=2)
+    if live:
+        y = ref_shim.reference_predict(path, str(tmp_path), ['a.wav', 'b_stereo.wav'], bs=2)
+        y1 = ref_shim.reference_predict(path, str(tmp_path), ['b_stereo.wav'], bs=1, ms_channel=1)
+    else:
+        g = helpers.golden(helpers.LIVE_FIXTURE)
+        y, y1 = g['loop_y'], g['loop_y1']
     for row, name in zip(y, ['a.wav', 'b_stereo.wav']):
         want = onet.predict_from_melspec(sd, args, omel.get_melspec(str(tmp_path / name)))
         assert np.abs(row - want).max() < 5e-6
-    y1 = ref_shim.reference_predict(path, str(tmp_path), ['b_stereo.wav'], bs=1, ms_channel=1)
     mono = st[:, 1].astype(np.float32) / np.float32(32768.0)
     want = onet.predict_from_melspec(sd, args, omel.melspec_db_from_audio(mono, 48000))
     assert np.abs(y1[0] - want).max() < 5e-6 and np.abs(y1[0] - y[1]).max() > 1e-4
