@@ -128,15 +128,11 @@ static int predict_batch(const void* pcm, bool pcm16, const int64_t* clip_off, c
     }
     rc = bf ? nisqa_td_selfatt_bf16(feat, tok_off, n_wins, n_clips, total_tok_padded, model->n_layers, model->td_w,
                                     model->td_wb, td, x, stream)
-         : x6 ? nisqa_td_selfatt_bf16x6(feat, tok_off, n_wins, n_clips, total_tok_padded, model->n_layers, model->td_w,
-                                        model->td_wb, td, x, stream)
             : nisqa_td_selfatt(feat, tok_off, n_wins, n_clips, total_tok_padded, model->n_layers, model->td_w, td, x, stream);
     if (rc) return rc;
     NQ_STAGE(4);
     rc = bf ? nisqa_pool_att_bf16(x, tok_off, n_wins, n_clips, total_tok_padded, model->n_heads, model->pool_w,
                                   model->pool_wb, pool, out, stream)
-         : x6 ? nisqa_pool_att_bf16x6(x, tok_off, n_wins, n_clips, total_tok_padded, model->n_heads, model->pool_w,
-                                      model->pool_wb, pool, out, stream)
             : nisqa_pool_att(x, tok_off, n_wins, n_clips, total_tok_padded, model->n_heads, model->pool_w, pool, out, stream);
     if (rc) return rc;
     NQ_STAGE(5);

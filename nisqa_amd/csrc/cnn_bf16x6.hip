@@ -48,19 +48,6 @@ __device__ constexpr int xwin53_hi(int b) { return b == 0 ? 2 : b == 1 ? 4 : 5; 
 // layer-boundary stamps of the phase clock (tools/phase_clock.py with NQ_PRECISION=bf16x6; empty macros unless built with -DNQ_EXPERIMENTAL)
 NQ_CLK_EXPORT(g_phase_clk6, nisqa_debug_phase_clock6)
 
-// 16x16x32 products of T-term operands for conv5 / conv6 (smallest first)
-template <int MT>
-NQ_DEV void mma16_terms(f32x4 (&acc)[MT], const f32x4 (&a)[MT][XT], const f32x4 (&b)[XT]) {
-#pragma unroll
-    for (int order = XT - 1; order >= 0; --order)
-#pragma unroll
-        for (int i = order; i >= 0; --i) {
-            const int j = order - i;
-#pragma unroll
-            for (int t = 0; t < MT; ++t) acc[t] = mfma_bf16x16(a[t][i], b[j], acc[t]);
-        }
-}
-
 // SEGX: the input is the reference's segment tensor x[B][L][1][48][15] (inner-operator mode, NISQA_lib.py:260-268) instead of the
 // spectrogram; no dB floor is applied (x is already clamped)
 template <bool SEGX>
@@ -365,7 +352,7 @@ __global__ __launch_bounds__(256, 1) void cnn_front_bf16x6_kernel(
             }
             if (g + 1 < 18) load_a5(g + 1);
             __builtin_amdgcn_sched_barrier(0);             // requests stay ahead of the step's MFMAs (conv_k_terms: FENCE)
-            mma16_terms<5>(acc5, a5[g & 1], b5[g & 3]);
+            mma16_terms<XT, 5>(acc5, a5[g & 1], b5[g & 3]);
         }
         NQ_STAMP(9);
 #pragma unroll
@@ -424,8 +411,8 @@ __global__ __launch_bounds__(256, 1) void cnn_front_bf16x6_kernel(
             }
             if (g + 1 < 18) load_a6(g + 1);
             __builtin_amdgcn_sched_barrier(0);
-            if (g & 1) mma16_terms<2>(acc6b, a6[1], b6[g & 7]);
-            else mma16_terms<2>(acc6, a6[0], b6[g & 7]);
+            if (g & 1) mma16_terms<XT, 2>(acc6b, a6[1], b6[g & 7]);
+            else mma16_terms<XT, 2>(acc6, a6[0], b6[g & 7]);
         }
         NQ_STAMP(11);
         // this wave's 4 x 96 outputs (slot, channel * 6 + y) go through S4 (dead since the barrier above) so that the

@@ -194,7 +194,7 @@ NQ_DEV void cnn_std_split_body(
             const unsigned a = ob[q % 3] + (q + q / 3) * 100;
             if (F16) {
                 if (q < 11 || lane < 16) lds_store_one_fmt<FMT>(a, SS_PPLANE, v * s0, dummy_mx);
-            } else {
+            } else {                                        // lds_store_terms<3> with the stores behind the split
                 const unsigned hi = cvt_pk_bf16(v, 0.f);
                 const float r1 = v - __uint_as_float(hi << 16);
                 const unsigned mid = cvt_pk_bf16(r1, 0.f);
@@ -262,12 +262,7 @@ NQ_DEV void cnn_std_split_body(
                 acc[0] = mfma32_fmt<FMT>(xa[0][0], w1[1], acc[0]); acc[1] = mfma32_fmt<FMT>(xa[1][0], w1[1], acc[1]);
                 acc[0] = mfma32_fmt<FMT>(xa[0][0], w1[0], acc[0]); acc[1] = mfma32_fmt<FMT>(xa[1][0], w1[0], acc[1]);
             } else {
-            acc[0] = mfma_bf(xa[0][2], w1[0], acc[0]); acc[1] = mfma_bf(xa[1][2], w1[0], acc[1]);   // smallest products first
-            acc[0] = mfma_bf(xa[0][1], w1[1], acc[0]); acc[1] = mfma_bf(xa[1][1], w1[1], acc[1]);
-            acc[0] = mfma_bf(xa[0][0], w1[2], acc[0]); acc[1] = mfma_bf(xa[1][0], w1[2], acc[1]);
-            acc[0] = mfma_bf(xa[0][1], w1[0], acc[0]); acc[1] = mfma_bf(xa[1][1], w1[0], acc[1]);
-            acc[0] = mfma_bf(xa[0][0], w1[1], acc[0]); acc[1] = mfma_bf(xa[1][0], w1[1], acc[1]);
-            acc[0] = mfma_bf(xa[0][0], w1[0], acc[0]); acc[1] = mfma_bf(xa[1][0], w1[0], acc[1]);
+                mma_terms<3, 2>(acc, xa, w1);               // the six products, smallest first
             }
             unsigned r[16];
 #pragma unroll
@@ -517,12 +512,7 @@ NQ_DEV void cnn_std_split_body(
                 if (g + 1 < 18) load_a(g + 1);
                 if constexpr (X6) {
                     __builtin_amdgcn_sched_barrier(0);             // requests stay ahead of the step's MFMAs (one wave per SIMD)
-#pragma unroll
-                    for (int order = 2; order >= 0; --order)      // the six products, smallest first
-#pragma unroll
-                        for (int i_ = order; i_ >= 0; --i_)
-#pragma unroll
-                            for (int t = 0; t < 3; ++t) acc5[t] = mfma_bf16x16(aq[g & 1][t][i_], bq[g & 3][order - i_], acc5[t]);
+                    mma16_terms<3, 3>(acc5, aq[g & 1], bq[g & 3]);
                 } else {
                     mma16_pair_fmt<FMT, 3>(acc5, aq[g & 1], bq[g & 3]);
                 }

@@ -49,6 +49,77 @@ NQ_DEV f32x16 zero16() {
 // D-fragment row of register r for lane half hf
 #define NQ_DROW(r, hf) (((r) & 3) + 8 * ((r) >> 2) + 4 * (hf))
 
+// ---- 32x32 D-layout vectors (lane l: token j = l & 31, half hf = l >> 5; register r of tile mt <-> feature 32 mt + NQ_DROW(r, hf)) ----
+// vec[f] for this lane's features: a bias or LayerNorm weight, or a token's row [tok][32 MT] of a token-major tensor
+template <int MT>
+NQ_DEV void load_dvec(const float* __restrict__ base, f32x16 (&out)[MT], int hf) {
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 v = *(const f32x4*)(base + 32 * mt + 8 * g + 4 * hf);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) out[mt][4 * g + e] = v[e];
+        }
+}
+// the reverse for a token-major row, every value times `scale`
+template <int MT>
+NQ_DEV void store_dtok(float* __restrict__ rowp, const f32x16 (&v)[MT], int hf, float scale) {
+#pragma unroll
+    for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            f32x4 o;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) o[e] = v[mt][4 * g + e] * scale;
+            *(f32x4*)(rowp + 32 * mt + 8 * g + 4 * hf) = o;
+        }
+}
+
+#define LN_EPS 1e-5f
+// LayerNorm over the 64 features of each token (32 in this lane, 32 in lane ^ 32): the mean, and rstd = 1 / sqrt(variance + eps)
+NQ_DEV float ln64_mean_rstd(const f32x16 (&x)[2], float& rstd) {
+    float s = 0.f;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) s += x[mt][r];
+    s += __shfl_xor(s, 32);
+    const float mean = s * (1.0f / 64.0f);
+    float q = 0.f;
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const float d = x[mt][r] - mean;
+            q = fmaf(d, d, q);
+        }
+    q += __shfl_xor(q, 32);
+    rstd = 1.0f / sqrtf(q * (1.0f / 64.0f) + LN_EPS);
+    return mean;
+}
+// x -> gamma * xhat + beta, gamma / beta preloaded in D layout
+NQ_DEV void layernorm64(f32x16 (&x)[2], const f32x16 (&g)[2], const f32x16 (&bt)[2]) {
+    float rstd;
+    const float mean = ln64_mean_rstd(x, rstd);
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) x[mt][r] = (x[mt][r] - mean) * rstd * g[mt][r] + bt[mt][r];
+}
+// the same with gamma / beta read from memory once the moments are known
+NQ_DEV void layernorm64(f32x16 (&x)[2], const float* __restrict__ gamma, const float* __restrict__ beta, int hf) {
+    float rstd;
+    const float mean = ln64_mean_rstd(x, rstd);
+    f32x16 g[2], bt[2];
+    load_dvec<2>(gamma, g, hf);
+    load_dvec<2>(beta, bt, hf);
+#pragma unroll
+    for (int mt = 0; mt < 2; ++mt)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) x[mt][r] = (x[mt][r] - mean) * rstd * g[mt][r] + bt[mt][r];
+}
+
 // Largest b in [0, n) with off[b] <= p   (off is an exclusive prefix sum, off[n] > p).
 NQ_DEV int find_segment(const int32_t* __restrict__ off, int n, int p) {
     int lo = 0, hi = n;            // invariant: off[lo] <= p < off[hi]

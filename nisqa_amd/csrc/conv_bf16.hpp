@@ -1,16 +1,9 @@
-// Split-bf16 ("bf16x3") building blocks shared by the AdaptCNN and StandardCNN kernels: MFMA wrappers, the
-// compiler-visible fp32 -> bf16 split, and the barrier-free 3x3 conv layer over wave-private LDS activations.
+// Split-bf16 ("bf16x3") building blocks shared by the AdaptCNN and StandardCNN kernels: the 16-bit operand formats, the LDS
+// stores of the split activations, and the barrier-free 3x3 conv layers over wave-private LDS activations.  The bf16 split and
+// the MFMA wrappers themselves are bf16_terms.hpp.
 #pragma once
-#include "common.hpp"
+#include "bf16_terms.hpp"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
-NQ_DEV f32x16 mfma_bf(f32x4 a, f32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-NQ_DEV f32x4 mfma_bf16x16(f32x4 a, f32x4 b, f32x4 c) {     // 16x16x32: A[i = l&15][k = 8*(l>>4)+e], D row 4*(l>>4)+r
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 // ---- operand formats of the two-term kernels (cnn_bf16.hip) ---------------------------------------------------------------------
 //   NQ_FMT_BF16X3: x = hi + lo in bf16 (8 + 8 significand bits), products hh + hl + lh: 16 of an fp32 operand's 24 bits
 //   NQ_FMT_F16X3 / NQ_FMT_F16X4: x * 2^e = hi + lo in f16 (11 + 11 significand bits and lo's sign: the residual x - hi is a
@@ -99,14 +92,6 @@ NQ_DEV unsigned bf16_bits(float v) {
 }
 NQ_DEV float bf16_val(unsigned b) { return __uint_as_float(b << 16); }
 
-// fp32 -> bf16 (round to nearest even), two values per instruction: the compiler selects v_cvt_pk_bf16_f32 for
-// this conversion, and -- unlike an inline-asm statement -- tracks its hazards and schedules around it
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-NQ_DEV unsigned cvt_pk_bf16(float a, float b) {
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
 // store v = hi + lo into the two bf16 planes at byte offset `off` of the hi plane
 NQ_DEV void store_split(char* plane_hi, int plane_bytes, int off, float v) {
     const unsigned hi = cvt_pk_bf16(v, 0.f);
@@ -207,7 +192,6 @@ NQ_DEV void conv3x3_bf16(f32x16 (&acc)[MT][NT], const char* act_in, const char* 
 // depend on the data), out-of-image taps redirected to a zero block with ONE select per tap and tile, weight fragments
 // through a buffer resource (address = SGPR descriptor + constant lane offset + immediate).  DESIGN.md 4.5.
 // ======================================================================================================================
-#define NQ_AS3 __attribute__((address_space(3)))
 // Scheduling fences (experiment -DNQ_SB=1|3, DESIGN.md 4.5 "round 3"): hipcc's machine scheduler sinks the ring's
 // prefetches to just before their use (register-pressure heuristics: the ISA shows s_waitcnt vmcnt(1) two MFMAs behind a
 // request).  sched_barrier(0) is a wall no instruction is moved across; with one per K-step (bit 1) and one behind the
@@ -376,21 +360,6 @@ NQ_DEV void lds_store_terms(unsigned a, int plane, float v) {
         lds_st16(a + t * plane, pk);
         if (t + 1 < T) r -= __uint_as_float(pk << 16);
     }
-}
-// acc[m][nt] += sum over the kept term products of a[m][i] x b[nt][j]; smallest products first, consecutive MFMAs on
-// different accumulators
-template <int T, int MT, int NT>
-NQ_DEV void mma_terms(f32x16 (&acc)[MT][NT], const f32x4 (&a)[MT][T], const f32x4 (&b)[NT][T]) {
-#pragma unroll
-    for (int order = T - 1; order >= 0; --order)
-#pragma unroll
-        for (int i = order; i >= 0; --i) {                 // (i, order - i): within an order the term with the smaller A part first
-            const int j = order - i;
-#pragma unroll
-            for (int m = 0; m < MT; ++m)
-#pragma unroll
-                for (int nt = 0; nt < NT; ++nt) acc[m][nt] = mfma_bf(a[m][i], b[nt][j], acc[m][nt]);
-        }
 }
 // conv_k_bf16 for T terms: fragments [step][NT][T][64 lanes][8 bf16], activation planes PLANE bytes apart; A rows always
 // one step ahead (this form runs one wave per SIMD on the 512-register budget).  FENCE: a sched_barrier behind the step's

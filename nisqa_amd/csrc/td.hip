@@ -19,35 +19,6 @@
 #include "layout.hpp"
 #include "../../include/nisqa_hip.h"
 
-#define LN_EPS 1e-5f
-
-// vec[f] for this lane's D-layout features f = 32*mt + (r&3) + 8*(r>>2) + 4*hf
-template <int MT>
-NQ_DEV void load_dvec(const float* __restrict__ base, f32x16 (&out)[MT], int hf) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 v = *(const f32x4*)(base + 32 * mt + 8 * g + 4 * hf);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) out[mt][4 * g + e] = v[e];
-        }
-}
-
-// token-major [tok][64] rows <-> D layout
-NQ_DEV void load_dtok(const float* __restrict__ rowp, f32x16 (&out)[2], int hf) { load_dvec<2>(rowp, out, hf); }
-NQ_DEV void store_dtok(float* __restrict__ rowp, const f32x16 (&v)[2], int hf, float scale) {
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = v[mt][4 * g + e] * scale;
-            *(f32x4*)(rowp + 32 * mt + 8 * g + 4 * hf) = o;
-        }
-}
-
 // out[mt] += W[64*... rows][64] * in   (in = D layout of a 64-feature x 32-token tile)
 template <int MT>
 NQ_DEV void chain_gemm64(const f32x4* __restrict__ af, const f32x16 (&in)[2], f32x16 (&out)[MT], int lane) {
@@ -69,34 +40,6 @@ NQ_DEV void chain_gemm64(const f32x4* __restrict__ af, const f32x16 (&in)[2], f3
                 out[mt] = mfma32(a[s & 1][mt][kk], in[s >> 2][4 * (s & 3) + kk], out[mt]);
         __builtin_amdgcn_sched_barrier(0);
     }
-}
-
-// LayerNorm over the 64 features of each token (32 in this lane, 32 in lane^32)
-NQ_DEV void layernorm64(f32x16 (&x)[2], const float* __restrict__ gamma, const float* __restrict__ beta, int hf) {
-    float s = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s += x[mt][r];
-    s += __shfl_xor(s, 32);
-    const float mean = s * (1.0f / 64.0f);
-    float q = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float d = x[mt][r] - mean;
-            q = fmaf(d, d, q);
-        }
-    q += __shfl_xor(q, 32);
-    const float rstd = 1.0f / sqrtf(q * (1.0f / 64.0f) + LN_EPS);
-    f32x16 g[2], bt[2];
-    load_dvec<2>(gamma, g, hf);
-    load_dvec<2>(beta, bt, hf);
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) x[mt][r] = (x[mt][r] - mean) * rstd * g[mt][r] + bt[mt][r];
 }
 
 // QKV projection of a register-resident x tile; writes q (pre-scaled by 1/sqrt(64)), k, v^T
@@ -245,7 +188,7 @@ __global__ __launch_bounds__(64) void td_layer_kernel(const int32_t* __restrict_
     f32x16 y[2], xr[2];
     load_dvec<2>(lw + TDL_OUT_B, y, h);
     chain_gemm64<2>((const f32x4*)(lw + TDL_OUT_AF), o, y, lane);
-    load_dtok(x_in + (size_t)tok * 64, xr, h);
+    load_dvec<2>(x_in + (size_t)tok * 64, xr, h);
 #pragma unroll
     for (int r = 0; r < 16; ++r) { y[0][r] += xr[0][r]; y[1][r] += xr[1][r]; }
     layernorm64(y, lw + TDL_LN1_G, lw + TDL_LN1_B, h);
@@ -280,7 +223,7 @@ __global__ __launch_bounds__(64) void pool_score_kernel(const float* __restrict_
     if (tile0 - tok_off[b] >= n_wins[b]) return;
     const int tok = tile0 + j;
     f32x16 xr[2];
-    load_dtok(x + (size_t)tok * 64, xr, h);
+    load_dvec<2>(x + (size_t)tok * 64, xr, h);
     for (int hd = 0; hd < n_heads; ++hd) {
         const float* w = pw + (size_t)hd * PL_FLOATS;
         f32x16 hid[4], w2[4], w3[2];

@@ -34,18 +34,11 @@
 // K fragments are the producer's own D registers; a V fragment interleaves the two 16-token tiles of its block (8 bytes per lane
 // each).  The consumer reads a fragment as one 16-byte load per lane (from LDS for Q, from L2 for K / V).
 #include <type_traits>
-#include "common.hpp"
+#include "bf16_terms.hpp"
 #include "layout.hpp"
 #include "../../include/nisqa_hip.h"
 
 #define XT 3
-#define LN_EPS 1e-5f
-#define NQ_AS3 __attribute__((address_space(3)))
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-typedef unsigned short u16;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 #define T16_FRAG 1024                                 /* bytes of one fragment: 64 lanes x 8 bf16 */
 #define T16_GEMM (2 * 4 * XT * T16_FRAG)              /* 64 x 64 GEMM: [s 2][mt 4][term][1 KB] = 24 KB */
@@ -55,9 +48,6 @@ typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 namespace {
 
-NQ_DEV f32x4 mfma16(f32x4 a, f32x4 b, f32x4 c) {
-    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
 // LDS fragment reads are plain loads (the compiler tracks them with lgkmcnt).  What it must NOT see is the LDS-DMA staging of the layer
 // kernel: hipcc orders every LDS read behind ALL outstanding LDS-DMA of the wave (s_waitcnt vmcnt(0): it cannot tell the areas
 // apart), i.e. the next layer's fragments, requested early to travel under this layer's GEMMs, would have to land before those GEMMs
@@ -66,19 +56,6 @@ NQ_DEV f32x4 mfma16(f32x4 a, f32x4 b, f32x4 c) {
 // too few younger requests: they wait for more than they need, never for less.
 template <int OFF>
 NQ_DEV f32x4 lds_rd(unsigned a) { return *(NQ_AS3 const f32x4*)(a + OFF); }
-NQ_DEV unsigned cvt_pk_bf16(float a, float b) {
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-// (v0, v1) -> XT packed bf16 pairs, each term rounded to nearest: v = t[0] + t[1] + t[2] exactly
-NQ_DEV void split2t(float v0, float v1, unsigned (&t)[XT]) {
-    f32x2_t r = {v0, v1};
-#pragma unroll
-    for (int q = 0; q < XT; ++q) {
-        t[q] = cvt_pk_bf16(r[0], r[1]);
-        if (q + 1 < XT) r = r - f32x2_t{__uint_as_float(t[q] << 16), __uint_as_float(t[q] & 0xffff0000u)};
-    }
-}
 // the 8 k-slots of one K-step (two D tiles of 4 registers) -> XT operand fragments
 NQ_DEV void split8(const f32x4& lo, const f32x4& hi, f32x4 (&b)[XT], float scale = 1.0f) {
     unsigned t0[XT], t1[XT], t2[XT], t3[XT];
@@ -132,19 +109,6 @@ NQ_DEV void layernorm64(tile16& x, const tile16& gm, const tile16& bt) {
         for (int r = 0; r < 4; ++r) x.v[mt][r] = (x.v[mt][r] - mean) * rstd * gm.v[mt][r] + bt.v[mt][r];
 }
 
-// the six term products (weight term i, activation term j), i + j <= 2, smallest first; consecutive MFMAs go to the four
-// different output tiles.  SWAP: the activation fragment is the A operand (token-major result: rows = tokens, cols = features).
-template <bool SWAP>
-NQ_DEV void mma_terms(const f32x4 (&w)[4][XT], const f32x4 (&x)[XT], tile16& out) {
-#pragma unroll
-    for (int order = XT - 1; order >= 0; --order)
-#pragma unroll
-        for (int i = order; i >= 0; --i)
-#pragma unroll
-            for (int mt = 0; mt < 4; ++mt)
-                out.v[mt] = SWAP ? mfma16(x[order - i], w[mt][i], out.v[mt]) : mfma16(w[mt][i], x[order - i], out.v[mt]);
-}
-
 // the fragments of one 64 x 64 GEMM ([s 2][mt 4][term][1 KB] in LDS) in registers: requested a phase ahead of their MFMAs
 struct gemm_frags { f32x4 w[2][4 * XT]; };            // [s][mt * XT + term]
 template <int I>
@@ -158,7 +122,9 @@ NQ_DEV void frags_load(gemm_frags& f, unsigned wbase, unsigned lane16) {
     frags_rd12<0>(f.w[0], wbase + lane16);
     frags_rd12<0>(f.w[1], wbase + 12 * T16_FRAG + lane16);
 }
-// six products of one K-step from 12 fragments [mt * XT + term] (see mma_terms)
+// the six term products of one K-step (weight term i, activation term j), i + j <= 2, smallest first, from 12 fragments
+// [mt * XT + term]; consecutive MFMAs go to the four different output tiles.  SWAP: the activation fragment is the A operand
+// (token-major result: rows = tokens, cols = features).
 template <bool SWAP>
 NQ_DEV void mma_terms12(const f32x4 (&w)[12], const f32x4 (&x)[XT], tile16& out) {
 #pragma unroll
@@ -167,7 +133,8 @@ NQ_DEV void mma_terms12(const f32x4 (&w)[12], const f32x4 (&x)[XT], tile16& out)
         for (int i = order; i >= 0; --i)
 #pragma unroll
             for (int mt = 0; mt < 4; ++mt)
-                out.v[mt] = SWAP ? mfma16(x[order - i], w[mt * XT + i], out.v[mt]) : mfma16(w[mt * XT + i], x[order - i], out.v[mt]);
+                out.v[mt] = SWAP ? mfma_bf16x16(x[order - i], w[mt * XT + i], out.v[mt])
+                                 : mfma_bf16x16(w[mt * XT + i], x[order - i], out.v[mt]);
 }
 // out += W in
 template <bool SWAP = false>
@@ -450,7 +417,8 @@ __global__ __launch_bounds__(256, 1) void td16_layer_kernel(const int32_t* __res
 #pragma unroll
                         for (int i = order; i >= 0; --i)
 #pragma unroll
-                            for (int jt = 0; jt < 2; ++jt) sa[jt][order] = mfma16(kf[(jt * 2 + s) * XT + i], q[s][order - i], sa[jt][order]);
+                            for (int jt = 0; jt < 2; ++jt)
+                                sa[jt][order] = mfma_bf16x16(kf[(jt * 2 + s) * XT + i], q[s][order - i], sa[jt][order]);
 #pragma unroll
                 for (int jt = 0; jt < 2; ++jt)
 #pragma unroll

@@ -10,31 +10,10 @@
 //     the weight fragments are packed in the matching order on the host;
 //   * q, k are stored as bf16 hi/lo planes [tok][64], v as hi/lo planes [64][tok] (same bytes as fp32);
 //   * softmax, LayerNorm, residuals, biases stay fp32 in registers.
-#include "common.hpp"
+#include "bf16_terms.hpp"
 #include "layout.hpp"
 #include "../../include/nisqa_hip.h"
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-#define LN_EPS 1e-5f
-
-NQ_DEV f32x16 mfma_bf(f32x4 a, f32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// fp32 -> bf16 (round to nearest even), two values per instruction: the compiler selects v_cvt_pk_bf16_f32 for
-// this conversion, and -- unlike an inline-asm statement -- tracks its hazards and schedules around it
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-NQ_DEV unsigned cvt_pk_bf16(float a, float b) {
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-// (v0, v1) -> packed bf16 hi pair and packed bf16 lo pair
-NQ_DEV void split2(float v0, float v1, unsigned& hi, unsigned& lo) {
-    hi = cvt_pk_bf16(v0, v1);
-    lo = cvt_pk_bf16(v0 - __uint_as_float(hi << 16), v1 - __uint_as_float(hi & 0xffff0000u));
-}
 // 8 consecutive registers of a D fragment -> B-operand (hi, lo) of one K=16 step
 NQ_DEV void split8(const f32x16& a, int base, f32x4& hi, f32x4& lo) {
 #pragma unroll
@@ -46,28 +25,6 @@ NQ_DEV void split8(const f32x16& a, int base, f32x4& hi, f32x4& lo) {
     }
 }
 
-template <int MT>
-NQ_DEV void load_dvec(const float* __restrict__ base, f32x16 (&out)[MT], int hf) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 v = *(const f32x4*)(base + 32 * mt + 8 * g + 4 * hf);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) out[mt][4 * g + e] = v[e];
-        }
-}
-NQ_DEV void store_dtok(float* __restrict__ rowp, const f32x16 (&v)[2], int hf) {
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = v[mt][4 * g + e];
-            *(f32x4*)(rowp + 32 * mt + 8 * g + 4 * hf) = o;
-        }
-}
 // a 64-feature D tile as bf16 hi / lo rows [64] (token-major planes)
 NQ_DEV void store_dtok_split(u16* __restrict__ hi_row, u16* __restrict__ lo_row, const f32x16 (&v)[2], int hf, float scale) {
 #pragma unroll
@@ -123,30 +80,6 @@ NQ_DEV void chain_gemm_bf(const u16* __restrict__ wb, const f32x16 (&in)[2], f32
     chain_mma<MT>(f, in, out);
 }
 
-// LayerNorm over the 64 features of each token (gamma / beta preloaded in D layout)
-NQ_DEV void layernorm64(f32x16 (&x)[2], const f32x16 (&g)[2], const f32x16 (&bt)[2]) {
-    float s = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) s += x[mt][r];
-    s += __shfl_xor(s, 32);
-    const float mean = s * (1.0f / 64.0f);
-    float q = 0.f;
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const float d = x[mt][r] - mean;
-            q = fmaf(d, d, q);
-        }
-    q += __shfl_xor(q, 32);
-    const float rstd = 1.0f / sqrtf(q * (1.0f / 64.0f) + LN_EPS);
-#pragma unroll
-    for (int mt = 0; mt < 2; ++mt)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) x[mt][r] = (x[mt][r] - mean) * rstd * g[mt][r] + bt[mt][r];
-}
 struct qkv_planes { u16 *qh, *ql, *kh, *kl, *vh, *vl; };   // q,k: [NP][64]; v: [64][NP]
 NQ_DEV qkv_planes planes_of(float* base, size_t np64) {
     u16* p = (u16*)base;                                    // 6 planes of np*64 bf16 = 3 * np64 floats
@@ -241,7 +174,7 @@ __global__ __launch_bounds__(64) void td_proj_bf16_kernel(const float* __restric
     qkv_pre qp;
     qkv_prefetch(tw + TD_LAYER0, twb + TDB_LAYER0, qp, lane);
     layernorm64(acc, g0, b0);
-    store_dtok(x + (size_t)tok * 64, acc, h);
+    store_dtok(x + (size_t)tok * 64, acc, h, 1.0f);
     qkv_store_bf(tw + TD_LAYER0, twb + TDB_LAYER0, acc, planes_of(qkv, (size_t)np * 64), tok, np, lane, qp);
 }
 
@@ -371,7 +304,7 @@ __global__ __launch_bounds__(64) void td_layer_bf16_kernel(const int32_t* __rest
 #pragma unroll
     for (int r = 0; r < 16; ++r) { y[0][r] += h2[0][r]; y[1][r] += h2[1][r]; }
     layernorm64(y, g, bt);
-    store_dtok(x_out + (size_t)tok * 64, y, h);
+    store_dtok(x_out + (size_t)tok * 64, y, h, 1.0f);
     if (lw_next) qkv_store_bf(lw_next, lwb_next, y, planes_of(qkv_next, (size_t)np * 64), tok, np, lane, qp);
 }
 

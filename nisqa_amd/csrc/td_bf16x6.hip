@@ -2,34 +2,12 @@
 // ("bf16x6"): every GEMM operand as THREE bf16 terms (hi + mid + lo: an exact split of the fp32 value) and six
 // v_mfma_f32_32x32x16_bf16 products per term pair (hh, hm, mh, hl, lh, mm; fp32 accumulate) -- cnn_bf16x6.hip, DESIGN.md 4.5.
 // One wave per (32-token tile, head); the self-attention kernels of the same precision are td16_bf16x6.hip.
-#include "common.hpp"
+#include "bf16_terms.hpp"
 #include "layout.hpp"
 #include "../../include/nisqa_hip.h"
 
 #define XT 3
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned short u16;
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-#define LN_EPS 1e-5f
 
-NQ_DEV f32x16 mfma_bf(f32x4 a, f32x4 b, f32x16 c) {
-    return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-typedef __bf16 bf16x2_t __attribute__((ext_vector_type(2)));
-typedef float f32x2_t __attribute__((ext_vector_type(2)));
-NQ_DEV unsigned cvt_pk_bf16(float a, float b) {
-    const f32x2_t v = {a, b};
-    return __builtin_bit_cast(unsigned, __builtin_convertvector(v, bf16x2_t));
-}
-// (v0, v1) -> XT packed bf16 pairs, each term rounded to nearest: v = t[0] + t[1] + t[2] exactly
-NQ_DEV void split2t(float v0, float v1, unsigned (&t)[XT]) {
-    f32x2_t r = {v0, v1};
-#pragma unroll
-    for (int q = 0; q < XT; ++q) {
-        t[q] = cvt_pk_bf16(r[0], r[1]);
-        if (q + 1 < XT) r = r - f32x2_t{__uint_as_float(t[q] << 16), __uint_as_float(t[q] & 0xffff0000u)};
-    }
-}
 // 8 consecutive registers of a D fragment -> the XT B-operand terms of one K=16 step
 NQ_DEV void split8t(const f32x16& a, int base, f32x4 (&b)[XT]) {
 #pragma unroll
@@ -41,17 +19,6 @@ NQ_DEV void split8t(const f32x16& a, int base, f32x4 (&b)[XT]) {
     }
 }
 
-template <int MT>
-NQ_DEV void load_dvec(const float* __restrict__ base, f32x16 (&out)[MT], int hf) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 v = *(const f32x4*)(base + 32 * mt + 8 * g + 4 * hf);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) out[mt][4 * g + e] = v[e];
-        }
-}
 // out[mt] += W * in  (W: chain-order fragments [4 steps][MTT][XT][64][8], in: D layout of a 64 x 32 tile); the fragments of a
 // whole GEMM are requested by chain_load a phase ahead of chain_mma (one wave per SIMD: every load is an exposed round trip)
 template <int MT>
@@ -68,24 +35,13 @@ NQ_DEV void chain_load(const u16* __restrict__ wb, int mt0, chain_frags<MT>& f, 
             for (int k = 0; k < XT; ++k) f.t[s][mt][k] = af[((s * MTT + mt0 + mt) * XT + k) * 64];
 }
 
-// the six term products (weight term i, activation term j), i + j <= 2, smallest first; consecutive MFMAs on different tiles
-template <int MT>
-NQ_DEV void mma_terms(const f32x4 (&a)[MT][XT], const f32x4 (&b)[XT], f32x16 (&out)[MT]) {
-#pragma unroll
-    for (int order = XT - 1; order >= 0; --order)
-#pragma unroll
-        for (int i = order; i >= 0; --i)
-#pragma unroll
-            for (int mt = 0; mt < MT; ++mt) out[mt] = mfma_bf(a[mt][i], b[order - i], out[mt]);
-}
-
 template <int MT>
 NQ_DEV void chain_mma(const chain_frags<MT>& f, const f32x16 (&in)[2], f32x16 (&out)[MT]) {
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
         f32x4 b[XT];
         split8t(in[s >> 1], 8 * (s & 1), b);
-        mma_terms<MT>(f.t[s], b, out);
+        mma_terms<XT, MT>(out, f.t[s], b);            // the six products: weight term i, activation term j, i + j <= 2
     }
 }
 

@@ -445,7 +445,6 @@ __global__ __launch_bounds__((BM / (32 * MT)) * (BN / (32 * NT)) * 64) void conv
 //     lane i receives column i of that block (tools/micro/trread.hip prints the mapping from the hardware).
 // ---------------------------------------------------------------------------------------------------------
 typedef short nq_s16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned nq_u32x2 __attribute__((ext_vector_type(2)));
 
 template <int R, bool KC>
 struct bf_tile {
@@ -461,11 +460,11 @@ struct bf_tile {
             unsigned a;
             if (KC) a = base + (i / (GB_K / 4)) * RS + 8 * (i % (GB_K / 4));
             else a = base + (i / (R / 4)) * RS + 8 * (i % (R / 4));
-            const unsigned h0 = cvt_pk_bf16(v[j][0], v[j][1]), h1 = cvt_pk_bf16(v[j][2], v[j][3]);
-            const unsigned l0 = cvt_pk_bf16(v[j][0] - __uint_as_float(h0 << 16), v[j][1] - __uint_as_float(h0 & 0xffff0000u));
-            const unsigned l1 = cvt_pk_bf16(v[j][2] - __uint_as_float(h1 << 16), v[j][3] - __uint_as_float(h1 & 0xffff0000u));
-            *(NQ_AS3 nq_u32x2*)(a) = nq_u32x2{h0, h1};
-            *(NQ_AS3 nq_u32x2*)(a + PLANE) = nq_u32x2{l0, l1};
+            unsigned h0, l0, h1, l1;
+            split2(v[j][0], v[j][1], h0, l0);
+            split2(v[j][2], v[j][3], h1, l1);
+            *(NQ_AS3 u32x2*)(a) = u32x2{h0, h1};
+            *(NQ_AS3 u32x2*)(a + PLANE) = u32x2{l0, l1};
         }
     }
     // lane-dependent part of a fragment address for the 32 rows starting at row0

@@ -275,7 +275,8 @@ extern "C" int nisqa_segconv_pack_f32_many(int32_t n_jobs, const int32_t* modes,
     return NQ_LAUNCH_STATUS();
 }
 
-// four consecutive channels of one pixel -> T bf16 terms each (round to nearest), 8 bytes per plane
+// four consecutive channels of one pixel -> T bf16 terms each (round to nearest), 8 bytes per plane: split2t (bf16_terms.hpp) with the
+// two pairs' terms interleaved -- the same arithmetic, but two split2t calls compile to a different schedule of these kernels
 template <int T>
 NQ_DEV void sc_store_terms4(unsigned a, int plane, f32x4 v) {
     f32x2_t r0 = {v[0], v[1]}, r1 = {v[2], v[3]};
@@ -431,6 +432,7 @@ __global__ __launch_bounds__(256, SC_WGS) void segconv_bf16_kernel(
                         lds_st32(a + C::PLANE + 4, cvt_pk_f16(sv[2] - f1[0], sv[3] - f1[1]));
                         continue;
                     }
+                    // split2 (bf16_terms.hpp) with both hi pairs first: the order this loop's schedule comes out of
                     const unsigned h0 = cvt_pk_bf16(v[j][0], v[j][1]), h1 = cvt_pk_bf16(v[j][2], v[j][3]);
                     const unsigned l0 = cvt_pk_bf16(v[j][0] - __uint_as_float(h0 << 16), v[j][1] - __uint_as_float(h0 & 0xffff0000u));
                     const unsigned l1 = cvt_pk_bf16(v[j][2] - __uint_as_float(h1 << 16), v[j][3] - __uint_as_float(h1 & 0xffff0000u));

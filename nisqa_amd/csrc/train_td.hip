@@ -27,38 +27,14 @@
 #include "../../include/nisqa_hip.h"
 #include "../../include/nisqa_train.h"
 
-#define LN_EPS 1e-5f
 #define TDT_MAX_LAYERS 4
 #define TDT_MAX_HEADS 8
 
-// ---- D-layout helpers (lane l: token j = l & 31, half hf = l >> 5; register r of tile mt <-> feature 32 mt + DROW(r, hf)) ----
-template <int MT>
-NQ_DEV void ld_vec(const float* __restrict__ base, f32x16 (&out)[MT], int hf) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            const f32x4 v = *(const f32x4*)(base + 32 * mt + 8 * g + 4 * hf);
-#pragma unroll
-            for (int e = 0; e < 4; ++e) out[mt][4 * g + e] = v[e];
-        }
-}
+// ---- D-layout helpers beside common.hpp's load_dvec / store_dtok (register r of tile mt <-> feature 32 mt + NQ_DROW(r, hf)) ----
 NQ_DEV f32x16 ld_row16(const float* __restrict__ base, int hf) {      // 32 consecutive row values -> the D rows of this lane half
     f32x16 o[1];
-    ld_vec<1>(base, o, hf);
+    load_dvec<1>(base, o, hf);
     return o[0];
-}
-template <int MT>
-NQ_DEV void st_vec(float* __restrict__ rowp, const f32x16 (&v)[MT], int hf, float scale) {
-#pragma unroll
-    for (int mt = 0; mt < MT; ++mt)
-#pragma unroll
-        for (int g = 0; g < 4; ++g) {
-            f32x4 o;
-#pragma unroll
-            for (int e = 0; e < 4; ++e) o[e] = v[mt][4 * g + e] * scale;
-            *(f32x4*)(rowp + 32 * mt + 8 * g + 4 * hf) = o;
-        }
 }
 // feature-major copy: base[feature][np tokens]
 NQ_DEV void st_fm(float* __restrict__ base, int np, int tok, const f32x16 (&v)[2], int hf, float scale) {
@@ -130,7 +106,8 @@ NQ_DEV f32x16 ld_mask_row(const float* __restrict__ row, int col0, int n, int hf
     return m;
 }
 
-// LayerNorm over the 64 features of a token (32 in this lane, 32 in lane ^ 32); x -> gamma * xhat + beta, xhat and rstd kept
+// LayerNorm over the 64 features of a token (32 in this lane, 32 in lane ^ 32); x -> gamma * xhat + beta, xhat and rstd kept (the moments
+// of common.hpp's ln64_mean_rstd written out: through that helper these kernels compile to a different schedule)
 NQ_DEV void ln_fwd(f32x16 (&x)[2], const float* __restrict__ gamma, const float* __restrict__ beta, int hf, f32x16 (&xh)[2],
                    float& rstd) {
     float s = 0.f;
@@ -151,8 +128,8 @@ NQ_DEV void ln_fwd(f32x16 (&x)[2], const float* __restrict__ gamma, const float*
     q += __shfl_xor(q, 32);
     rstd = 1.0f / sqrtf(q * (1.0f / 64.0f) + LN_EPS);
     f32x16 g[2], bt[2];
-    ld_vec<2>(gamma, g, hf);
-    ld_vec<2>(beta, bt, hf);
+    load_dvec<2>(gamma, g, hf);
+    load_dvec<2>(beta, bt, hf);
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -164,7 +141,7 @@ NQ_DEV void ln_fwd(f32x16 (&x)[2], const float* __restrict__ gamma, const float*
 // d: d loss / d (LayerNorm output) in, d loss / d (LayerNorm input) out: rstd * (g - mean(g) - xhat * mean(g * xhat)), g = d * gamma
 NQ_DEV void ln_bwd(f32x16 (&d)[2], const f32x16 (&xh)[2], float rstd, const float* __restrict__ gamma, int hf) {
     f32x16 g[2];
-    ld_vec<2>(gamma, g, hf);
+    load_dvec<2>(gamma, g, hf);
     float s1 = 0.f, s2 = 0.f;
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
@@ -209,17 +186,17 @@ struct tdt_heads { tdt_head_p h[TDT_MAX_HEADS]; int n; };
 NQ_DEV void qkv_store(const tdt_layer_p& L, const f32x16 (&x)[2], int ptok, int np, int lane, float vm) {
     const int hf = lane >> 5;
     f32x16 acc[6];
-    ld_vec<6>(L.b_qkv, acc, hf);
+    load_dvec<6>(L.b_qkv, acc, hf);
     chain_gemm<2, 6>((const f32x4*)L.f_qkv, x, acc, lane);
     f32x16 t2[2];
     t2[0] = acc[0]; t2[1] = acc[1];
-    st_vec<2>(L.qs + (size_t)ptok * 64, t2, hf, 0.125f * vm);
+    store_dtok<2>(L.qs + (size_t)ptok * 64, t2, hf, 0.125f * vm);
     st_fm(L.qsT, np, ptok, t2, hf, 0.125f * vm);
     t2[0] = acc[2]; t2[1] = acc[3];
-    st_vec<2>(L.k + (size_t)ptok * 64, t2, hf, vm);
+    store_dtok<2>(L.k + (size_t)ptok * 64, t2, hf, vm);
     st_fm(L.kT, np, ptok, t2, hf, vm);
     t2[0] = acc[4]; t2[1] = acc[5];
-    st_vec<2>(L.v + (size_t)ptok * 64, t2, hf, vm);
+    store_dtok<2>(L.v + (size_t)ptok * 64, t2, hf, vm);
     st_fm(L.vT, np, ptok, t2, hf, vm);
 }
 
@@ -240,7 +217,7 @@ __global__ __launch_bounds__(64) void tdt_proj_fwd_kernel(tdt_common c, const fl
     const f32x4* frow = (const f32x4*)(feat + (size_t)utok * 384);
     const f32x4* af = (const f32x4*)f_w0;
     f32x16 acc[2];
-    ld_vec<2>(b0, acc, hf);
+    load_dvec<2>(b0, acc, hf);
     // this lane's half of its token's 384 features: 48 independent 16-byte reads requested together (a lane walks its own
     // row, 1.5 KB from its neighbour's: nothing coalesces, so the reads are latency, not bandwidth)
     f32x4 bv[48];
@@ -269,8 +246,8 @@ __global__ __launch_bounds__(64) void tdt_proj_fwd_kernel(tdt_common c, const fl
     f32x16 xh[2];
     float rstd;
     ln_fwd(acc, g0, be0, hf, xh, rstd);
-    st_vec<2>(xh0 + (size_t)ptok * 64, xh, hf, vm);
-    st_vec<2>(x0 + (size_t)ptok * 64, acc, hf, vm);
+    store_dtok<2>(xh0 + (size_t)ptok * 64, xh, hf, vm);
+    store_dtok<2>(x0 + (size_t)ptok * 64, acc, hf, vm);
     if (hf == 0) rs0[ptok] = rstd * vm;
     qkv_store(L0, acc, ptok, c.np, lane, vm);
 }
@@ -369,46 +346,46 @@ __global__ __launch_bounds__(64) void tdt_layer_fwd_kernel(tdt_common c, tdt_lay
 #pragma unroll
     for (int r = 0; r < 16; ++r) { o[0][r] *= inv_l; o[1][r] *= inv_l; }
     if (hf == 0) L.lse[ptok] = valid ? m + logf(l) : 0.f;
-    st_vec<2>(L.ctx + (size_t)ptok * 64, o, hf, vm);
+    store_dtok<2>(L.ctx + (size_t)ptok * 64, o, hf, vm);
 
     // out_proj, dropout1, residual, LayerNorm1
     f32x16 y[2], t[2], xh[2];
     float rstd;
-    ld_vec<2>(L.b_out, y, hf);
+    load_dvec<2>(L.b_out, y, hf);
     chain_gemm<2, 2>((const f32x4*)L.f_out, o, y, lane);
     if (L.m1 && valid) {
-        ld_vec<2>(L.m1 + (size_t)utok * 64, t, hf);
+        load_dvec<2>(L.m1 + (size_t)utok * 64, t, hf);
         mul_t<2>(y, t);
     }
-    ld_vec<2>(x_in + (size_t)ptok * 64, t, hf);
+    load_dvec<2>(x_in + (size_t)ptok * 64, t, hf);
 #pragma unroll
     for (int r = 0; r < 16; ++r) { y[0][r] += t[0][r]; y[1][r] += t[1][r]; }
     ln_fwd(y, L.g1, L.be1, hf, xh, rstd);
-    st_vec<2>(L.xh1 + (size_t)ptok * 64, xh, hf, vm);
-    st_vec<2>(L.x1 + (size_t)ptok * 64, y, hf, vm);
+    store_dtok<2>(L.xh1 + (size_t)ptok * 64, xh, hf, vm);
+    store_dtok<2>(L.x1 + (size_t)ptok * 64, y, hf, vm);
     if (hf == 0) L.rs1[ptok] = rstd * vm;
     // FFN: relu(linear1), dropout, linear2, dropout2, residual, LayerNorm2
     f32x16 h1[2], h2[2];
-    ld_vec<2>(L.b_ff1, h1, hf);
+    load_dvec<2>(L.b_ff1, h1, hf);
     chain_gemm<2, 2>((const f32x4*)L.f_ff1, y, h1, lane);
 #pragma unroll
     for (int r = 0; r < 16; ++r) { h1[0][r] = fmaxf(h1[0][r], 0.f); h1[1][r] = fmaxf(h1[1][r], 0.f); }
     if (L.mf && valid) {
-        ld_vec<2>(L.mf + (size_t)utok * 64, t, hf);
+        load_dvec<2>(L.mf + (size_t)utok * 64, t, hf);
         mul_t<2>(h1, t);
     }
-    st_vec<2>(L.hd + (size_t)ptok * 64, h1, hf, vm);
-    ld_vec<2>(L.b_ff2, h2, hf);
+    store_dtok<2>(L.hd + (size_t)ptok * 64, h1, hf, vm);
+    load_dvec<2>(L.b_ff2, h2, hf);
     chain_gemm<2, 2>((const f32x4*)L.f_ff2, h1, h2, lane);
     if (L.m2 && valid) {
-        ld_vec<2>(L.m2 + (size_t)utok * 64, t, hf);
+        load_dvec<2>(L.m2 + (size_t)utok * 64, t, hf);
         mul_t<2>(h2, t);
     }
 #pragma unroll
     for (int r = 0; r < 16; ++r) { y[0][r] += h2[0][r]; y[1][r] += h2[1][r]; }
     ln_fwd(y, L.g2, L.be2, hf, xh, rstd);
-    st_vec<2>(L.xh2 + (size_t)ptok * 64, xh, hf, vm);
-    st_vec<2>(x_out + (size_t)ptok * 64, y, hf, vm);
+    store_dtok<2>(L.xh2 + (size_t)ptok * 64, xh, hf, vm);
+    store_dtok<2>(x_out + (size_t)ptok * 64, y, hf, vm);
     if (hf == 0) L.rs2[ptok] = rstd * vm;
     if (has_next) {
         qkv_store(Ln, y, ptok, np, lane, vm);
@@ -418,9 +395,9 @@ __global__ __launch_bounds__(64) void tdt_layer_fwd_kernel(tdt_common c, tdt_lay
     for (int hd = 0; hd < hs.n; ++hd) {
         const tdt_head_p& H = hs.h[hd];
         f32x16 u[4], w2[4];
-        ld_vec<4>(H.b1, u, hf);
+        load_dvec<4>(H.b1, u, hf);
         chain_gemm<2, 4>((const f32x4*)H.f_p1, y, u, lane);
-        ld_vec<4>(H.w2, w2, hf);
+        load_dvec<4>(H.w2, w2, hf);
         float s = 0.f;
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
@@ -430,7 +407,7 @@ __global__ __launch_bounds__(64) void tdt_layer_fwd_kernel(tdt_common c, tdt_lay
                 s = fmaf(w2[mt][r], u[mt][r], s);
             }
         s += __shfl_xor(s, 32);
-        st_vec<4>(H.u + (size_t)ptok * 128, u, hf, vm);
+        store_dtok<4>(H.u + (size_t)ptok * 128, u, hf, vm);
         if (hf == 0) H.sc[ptok] = (s + H.b2[0]) * vm;
     }
 }
@@ -540,45 +517,45 @@ __global__ __launch_bounds__(256) void tdt_pool_clip_kernel(tdt_common c, tdt_he
 NQ_DEV void bwd_part_a(const tdt_layer_p& L, f32x16 (&dx)[2], int ptok, int utok, bool valid, float vm, int np, int lane) {
     const int hf = lane >> 5;
     f32x16 t[2], xh[2];
-    st_vec<2>(L.dx + (size_t)ptok * 64, dx, hf, vm);               // LayerNorm2 parameter gradients: column sums of dx (* xhat2)
-    ld_vec<2>(L.xh2 + (size_t)ptok * 64, xh, hf);
+    store_dtok<2>(L.dx + (size_t)ptok * 64, dx, hf, vm);               // LayerNorm2 parameter gradients: column sums of dx (* xhat2)
+    load_dvec<2>(L.xh2 + (size_t)ptok * 64, xh, hf);
     ln_bwd(dx, xh, L.rs2[ptok], L.g2, hf);                         // dx := d r2
     f32x16 df[2];
     df[0] = dx[0]; df[1] = dx[1];
     if (L.m2 && valid) {
-        ld_vec<2>(L.m2 + (size_t)utok * 64, t, hf);
+        load_dvec<2>(L.m2 + (size_t)utok * 64, t, hf);
         mul_t<2>(df, t);
     }
-    st_vec<2>(L.df + (size_t)ptok * 64, df, hf, vm);
+    store_dtok<2>(L.df + (size_t)ptok * 64, df, hf, vm);
     f32x16 dh[2];
     zero_t<2>(dh);
     chain_gemm<2, 2>((const f32x4*)L.t_ff2, df, dh, lane);
-    ld_vec<2>(L.hd + (size_t)ptok * 64, t, hf);                    // hd = relu(.) * mask: gate and mask in one comparison
+    load_dvec<2>(L.hd + (size_t)ptok * 64, t, hf);                    // hd = relu(.) * mask: gate and mask in one comparison
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
         for (int r = 0; r < 16; ++r) dh[mt][r] = t[mt][r] > 0.f ? dh[mt][r] : 0.f;
     if (L.mf && valid) {
-        ld_vec<2>(L.mf + (size_t)utok * 64, t, hf);
+        load_dvec<2>(L.mf + (size_t)utok * 64, t, hf);
         mul_t<2>(dh, t);
     }
-    st_vec<2>(L.dh + (size_t)ptok * 64, dh, hf, vm);
+    store_dtok<2>(L.dh + (size_t)ptok * 64, dh, hf, vm);
     chain_gemm<2, 2>((const f32x4*)L.t_ff1, dh, dx, lane);         // dx := d x1 = W1^T dh + d r2
-    st_vec<2>(L.dx1 + (size_t)ptok * 64, dx, hf, vm);
-    ld_vec<2>(L.xh1 + (size_t)ptok * 64, xh, hf);
+    store_dtok<2>(L.dx1 + (size_t)ptok * 64, dx, hf, vm);
+    load_dvec<2>(L.xh1 + (size_t)ptok * 64, xh, hf);
     ln_bwd(dx, xh, L.rs1[ptok], L.g1, hf);                         // dx := d r1
-    st_vec<2>(L.dr1 + (size_t)ptok * 64, dx, hf, vm);
+    store_dtok<2>(L.dr1 + (size_t)ptok * 64, dx, hf, vm);
     if (L.m1 && valid) {
-        ld_vec<2>(L.m1 + (size_t)utok * 64, t, hf);
+        load_dvec<2>(L.m1 + (size_t)utok * 64, t, hf);
         mul_t<2>(dx, t);
     }
-    st_vec<2>(L.datt + (size_t)ptok * 64, dx, hf, vm);
+    store_dtok<2>(L.datt + (size_t)ptok * 64, dx, hf, vm);
     f32x16 dc[2];
     zero_t<2>(dc);
     chain_gemm<2, 2>((const f32x4*)L.t_out, dx, dc, lane);
-    st_vec<2>(L.dctx + (size_t)ptok * 64, dc, hf, vm);
+    store_dtok<2>(L.dctx + (size_t)ptok * 64, dc, hf, vm);
     st_fm(L.dctxT, np, ptok, dc, hf, vm);
-    ld_vec<2>(L.ctx + (size_t)ptok * 64, t, hf);
+    load_dvec<2>(L.ctx + (size_t)ptok * 64, t, hf);
     float dd = 0.f;
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
@@ -601,16 +578,16 @@ __global__ __launch_bounds__(64) void tdt_bwd_tail_kernel(tdt_common c, tdt_laye
     for (int hd = 0; hd < hs.n; ++hd) {
         const tdt_head_p& H = hs.h[hd];
         f32x16 u[4], w2[4], dp[2];
-        ld_vec<4>(H.u + (size_t)ptok * 128, u, hf);
-        ld_vec<4>(H.w2, w2, hf);
+        load_dvec<4>(H.u + (size_t)ptok * 128, u, hf);
+        load_dvec<4>(H.w2, w2, hf);
         const float dsc = H.dsc[ptok], att = H.att[ptok];
 #pragma unroll
         for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
             for (int r = 0; r < 16; ++r) u[mt][r] = u[mt][r] > 0.f ? dsc * w2[mt][r] : 0.f;    // d u through the ReLU
-        st_vec<4>(H.du + (size_t)ptok * 128, u, hf, vm);
+        store_dtok<4>(H.du + (size_t)ptok * 128, u, hf, vm);
         chain_gemm<4, 2>((const f32x4*)H.t_p1, u, dx, lane);       // += linear1^T d u
-        ld_vec<2>(H.dpooled + (size_t)b * 64, dp, hf);
+        load_dvec<2>(H.dpooled + (size_t)b * 64, dp, hf);
 #pragma unroll
         for (int r = 0; r < 16; ++r) { dx[0][r] = fmaf(att, dp[0][r], dx[0][r]); dx[1][r] = fmaf(att, dp[1][r], dx[1][r]); }
     }
@@ -655,7 +632,7 @@ __global__ __launch_bounds__(64) void tdt_attn_bwd_kernel(tdt_common c, tdt_laye
         // its start, used behind its 64 MFMAs
         f32x4 kA[8], vA[8], kB[8], vB[8];
         if (share >= ntile) {                                    // fewer key tiles than shares: this share's plane holds zeros
-            st_vec<2>(part + (size_t)ptok * 192, dq, hf, 0.f);
+            store_dtok<2>(part + (size_t)ptok * 192, dq, hf, 0.f);
             return;
         }
         {
@@ -709,7 +686,7 @@ __global__ __launch_bounds__(64) void tdt_attn_bwd_kernel(tdt_common c, tdt_laye
             tile(kt, kA, vA, kB, vB);
             if (kt + nshare < ntile) tile(kt + nshare, kB, vB, kA, vA);
         }
-        st_vec<2>(part + (size_t)ptok * 192, dq, hf, valid ? 0.125f : 0.f);      // q entered the scores as q / 8
+        store_dtok<2>(part + (size_t)ptok * 192, dq, hf, valid ? 0.125f : 0.f);      // q entered the scores as q / 8
     } else {
         f32x4 kf[8], vf[8];
 #pragma unroll
@@ -723,8 +700,8 @@ __global__ __launch_bounds__(64) void tdt_attn_bwd_kernel(tdt_common c, tdt_laye
         zero_t<2>(dv);
         f32x4 qA[8], cA[8], qB[8], cB[8];
         if (share >= ntile) {
-            st_vec<2>(part + (size_t)ptok * 192 + 64, dk, hf, 0.f);
-            st_vec<2>(part + (size_t)ptok * 192 + 128, dv, hf, 0.f);
+            store_dtok<2>(part + (size_t)ptok * 192 + 64, dk, hf, 0.f);
+            store_dtok<2>(part + (size_t)ptok * 192 + 128, dv, hf, 0.f);
             return;
         }
         {
@@ -789,8 +766,8 @@ __global__ __launch_bounds__(64) void tdt_attn_bwd_kernel(tdt_common c, tdt_laye
             tile(qt, qA, cA, qB, cB);
             if (qt + nshare < ntile) tile(qt + nshare, qB, cB, qA, cA);
         }
-        st_vec<2>(part + (size_t)ptok * 192 + 64, dk, hf, 1.f);
-        st_vec<2>(part + (size_t)ptok * 192 + 128, dv, hf, 1.f);
+        store_dtok<2>(part + (size_t)ptok * 192 + 64, dk, hf, 1.f);
+        store_dtok<2>(part + (size_t)ptok * 192 + 128, dv, hf, 1.f);
     }
 }
 
@@ -811,37 +788,37 @@ __global__ __launch_bounds__(64) void tdt_bwd_mid_kernel(tdt_common c, tdt_layer
     const float vm = valid ? 1.f : 0.f;
     const int utok = c.seg_off[b] + (valid ? kq : 0);
     f32x16 dqkv[6], dx[2];
-    ld_vec<6>(Lup.dqkv + (size_t)ptok * 192, dqkv, hf);
+    load_dvec<6>(Lup.dqkv + (size_t)ptok * 192, dqkv, hf);
     {                                                            // + the other shares of the attention backward; the total goes back
         f32x16 pp[6];                                            // to d qkv for the weight-gradient GEMM and the bias column sums
 #pragma unroll 1
         for (int sh = 1; sh < TDT_ASPLIT; ++sh) {
-            ld_vec<6>(Lup.dqkvp + ((size_t)(sh - 1) * c.np + ptok) * 192, pp, hf);
+            load_dvec<6>(Lup.dqkvp + ((size_t)(sh - 1) * c.np + ptok) * 192, pp, hf);
 #pragma unroll
             for (int mt = 0; mt < 6; ++mt)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) dqkv[mt][r] += pp[mt][r];
         }
-        st_vec<6>(Lup.dqkv + (size_t)ptok * 192, dqkv, hf, 1.f);
+        store_dtok<6>(Lup.dqkv + (size_t)ptok * 192, dqkv, hf, 1.f);
     }
-    ld_vec<2>(Lup.dr1 + (size_t)ptok * 64, dx, hf);
+    load_dvec<2>(Lup.dr1 + (size_t)ptok * 64, dx, hf);
     chain_gemm<6, 2>((const f32x4*)Lup.t_qkv, dqkv, dx, lane);
     if (has_lower) {
         bwd_part_a(Llow, dx, ptok, utok, valid, vm, c.np, lane);
         return;
     }
-    st_vec<2>(dxl0 + (size_t)ptok * 64, dx, hf, vm);
+    store_dtok<2>(dxl0 + (size_t)ptok * 64, dx, hf, vm);
     f32x16 xh[2];
-    ld_vec<2>(xh0 + (size_t)ptok * 64, xh, hf);
+    load_dvec<2>(xh0 + (size_t)ptok * 64, xh, hf);
     ln_bwd(dx, xh, rs0[ptok], g0, hf);
-    st_vec<2>(dx0 + (size_t)ptok * 64, dx, hf, vm);
-    if (valid) st_vec<2>(dx0u + (size_t)utok * 64, dx, hf, 1.f);
+    store_dtok<2>(dx0 + (size_t)ptok * 64, dx, hf, vm);
+    if (valid) store_dtok<2>(dx0u + (size_t)utok * 64, dx, hf, 1.f);
 #pragma unroll 1
     for (int half = 0; half < 2; ++half) {
         f32x16 acc[6];
         zero_t<6>(acc);
         chain_gemm<2, 6>((const f32x4*)(t_w0 + (size_t)half * (8 * 6 * 256)), dx, acc, lane);
-        if (valid) st_vec<6>(dfeat + (size_t)utok * 384 + 192 * half, acc, hf, 1.f);
+        if (valid) store_dtok<6>(dfeat + (size_t)utok * 384 + 192 * half, acc, hf, 1.f);
     }
 }
 

@@ -49,7 +49,7 @@ NQ_DEV void conv_k_local(f32x16 (&acc)[MT][NT], __amdgpu_buffer_rsrc_t rsrc, int
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
-            for (int t = 0; t < T; ++t) a[slot][m][t] = lds_ld128_a(a_ad[m][t] + tapoff + 32 * s);
+            for (int t = 0; t < T; ++t) a[slot][m][t] = lds_ld128(a_ad[m][t] + tapoff + 32 * s);
     };
 #pragma unroll
     for (int g = 0; g < RING - 1; ++g) load_b(g, g);
