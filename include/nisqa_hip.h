@@ -321,6 +321,21 @@ int nisqa_resample(const void* pcm, int32_t is_pcm16, const int64_t* in_off, con
                    int32_t n_clips, int64_t max_out, double ratio, const float* table, int32_t nwin, int32_t num_table,
                    void* ws, size_t ws_bytes, float* out, void* stream);
 
+/* Alignment + fusion of the double-ended model NISQA_DE (NISQA_lib.py:406-424): Alignment.forward (:1264-1270) with AttDot /
+ * AttCosine (:1272-1294) and ApplyHardAttention / ApplySoftAttention (:1359-1378), then Fusion.forward (:1405-1417) without
+ * lin_fusion (de_fuse_dim null).  x [dev] fp32 [NP][64]: the first self-attention's output for the degraded AND the reference clips;
+ * pair b's degraded tokens are rows deg_tok_off[b] .. + deg_n_wins[b], its reference tokens rows ref_tok_off[b] .. + ref_n_wins[b]
+ * (both offset vectors in the tok_off convention: b + 1 entries, multiples of 64; the reference clips may follow the degraded ones in
+ * the same x, ref_tok_off = tok_off + n_pairs).  align: 0 dot, 1 cosine (each row / max(||row||, 1e-8), then the dot product);
+ * apply: 0 hard (the lowest-index maximum of the RAW scores -- the reference takes it over their softmax), 1 soft;
+ * fuse: 0 'x/y/-' -> [x, y, x - y] (F = 192), 1 '+/-' -> [x + y, x - y] (128), 2 'x/y' -> [x, y] (128).  out [dev] fp32 rows of
+ * ld_out >= F floats (multiple of 4), row = the degraded token's row in the deg_tok_off layout, total_deg_tok_padded =
+ * deg_tok_off[n_pairs] rows; columns F .. ld_out - 1 are not written; rows of padding tokens get zeros.  idx_out [dev] (optional,
+ * NULL): int32 per row, the chosen reference token (hard) or -1 (soft, padding).  Exact fp32 in every precision form. */
+int nisqa_de_align_fuse(const float* x, const int32_t* deg_tok_off, const int32_t* deg_n_wins, const int32_t* ref_tok_off,
+                        const int32_t* ref_n_wins, int32_t n_pairs, int32_t total_deg_tok_padded, int32_t align, int32_t apply,
+                        int32_t fuse, int32_t ld_out, float* out, int32_t* idx_out, void* stream);
+
 /* Self-test of the MFMA fragment maps the kernels rely on: D = A(32xK) * B(Kx32) with
  * v_mfma_f32_32x32x2_f32, a/b/d [dev] row-major.  Used by tests only. */
 int nisqa_selftest_mfma(const float* a, const float* b, float* d, int32_t k, void* stream);

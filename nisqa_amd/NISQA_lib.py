@@ -6,9 +6,10 @@ argument meaning and error behaviour, with the arithmetic moved to the HIP engin
   predict_mos / predict_dim (NL:1420-1467)        batching loop: WAV ingest -> device -> HIP forward
   NISQA / NISQA_DIM     (NL:29-268)                parameter containers with the reference's
                                                    state_dict keys; forward() runs the HIP path
+  NISQA_DE              (NL:272-424)               the same for the double-ended model (inference only)
 
 Evaluation statistics (eval_results and helpers, NL:1469-1852) are re-exported from nisqa_amd/evaluation.py.
-Out of scope here (raise NotImplementedError): training, NISQA_DE,
+Out of scope here (raise NotImplementedError): training (NISQA_DE training included),
 alternative blocks no shipped checkpoint uses.
 """
 import os
@@ -231,6 +232,46 @@ class NISQA_DIM(_NisqaBase):
         self.name = 'NISQA_DIM'
 
 
+class NISQA_DE(nn.Module):
+    """Parameter container of the double-ended model (NL:272-424) with the reference's state_dict keys: cnn.*, time_dependency.*,
+    time_dependency_2.* (input width = the fuse width), pool.*.  Alignment / Fusion hold no parameters for de_align dot / cosine and
+    de_fuse_dim null -- the configurations the HIP engine runs (engine.check_de_args); anything else raises here, before any GPU work."""
+
+    def __init__(self, **kw):
+        super().__init__()
+        from .engine import DE_FUSE_WIDTH, check_de_args
+        g = lambda k, d=None: kw.get(k, d)
+        check_de_args(dict(kw, de_align=g('de_align', 'dot'), de_align_apply=g('de_align_apply', 'hard'), de_fuse=g('de_fuse', 'x/y/-')))
+        self.name = 'NISQA_DE'
+        self._hp = dict(kw)
+        self._engine = None
+        self._engine_args = None
+        self.cnn = _Wrap(_AdaptCNNParams(g('cnn_c_out_1', 16), g('cnn_c_out_2', 32), g('cnn_c_out_3', 64),
+                                         g('cnn_kernel_size', 3), g('cnn_pool_3', [6, 3])))
+        d = g('td_sa_d_model', 64)
+        self.time_dependency = _Wrap(_SelfAttentionParams(self.cnn.model.fan_out, d, g('td_sa_num_layers', 2), g('td_sa_h', 64)))
+        self.time_dependency_2 = _Wrap(_SelfAttentionParams(DE_FUSE_WIDTH[g('de_fuse', 'x/y/-')], g('td_2_sa_d_model', 64),
+                                                            g('td_2_sa_num_layers', 2), g('td_2_sa_h', 64)))
+        self.pool = _Wrap(_PoolAttFFParams(g('td_2_sa_d_model', 64), g('pool_att_h', 128)))
+
+    def bind_args(self, args):
+        self._engine_args = args
+        self._engine = None
+        return self
+
+    def engine(self, device=None):
+        if self._engine is None:
+            from .engine import HipNisqaDE
+            if self._engine_args is None:
+                raise RuntimeError('bind_args(checkpoint_args) must be called before the HIP engine is built')
+            self._engine = HipNisqaDE(self._engine_args, self.state_dict(), device)
+        return self._engine
+
+    def forward(self, x, n_wins):
+        raise NotImplementedError('NISQA_DE: the segment-tensor forward is not implemented on the HIP engine; use predict() '
+                                  '(predict_csv with csv_ref)')
+
+
 # ---------------------------------------------------------------------------------------------
 # Dataset mirror
 # ---------------------------------------------------------------------------------------------
@@ -242,8 +283,8 @@ class SpeechQualityDataset(object):
                  seg_length=15, max_length=None, to_memory=False, to_memory_workers=0, transform=None,
                  seg_hop_length=1, ms_n_fft=1024, ms_hop_length=80, ms_win_length=170, ms_n_mels=32, ms_sr=48e3,
                  ms_fmax=16e3, ms_channel=None, double_ended=False, filename_column_ref=None, dim=False):
-        if double_ended:
-            raise NotImplementedError('double-ended (NISQA_DE) datasets are out of scope')
+        if double_ended and not filename_column_ref:
+            raise ValueError('a double-ended dataset needs filename_column_ref (the csv column of the reference files, csv_ref)')
         if transform is not None:
             raise NotImplementedError('spectrogram transforms are not supported on the HIP path')
         self.df, self.df_con, self.data_dir = df, df_con, data_dir
@@ -252,6 +293,15 @@ class SpeechQualityDataset(object):
         self.ms_n_fft, self.ms_hop_length, self.ms_win_length = ms_n_fft, ms_hop_length, ms_win_length
         self.ms_n_mels, self.ms_sr, self.ms_fmax, self.ms_channel = ms_n_mels, ms_sr, ms_fmax, ms_channel
         self.dim = dim
+        self.double_ended, self.filename_column_ref = bool(double_ended), filename_column_ref
+
+    def ref_view(self):
+        """The same table with the reference files as its file column (double-ended datasets): the readers and the header probe
+        take a dataset's file column, so the reference file of item i is item i of this view."""
+        v = object.__new__(type(self))
+        v.__dict__.update(self.__dict__)
+        v.filename_column, v.double_ended = self.filename_column_ref, False
+        return v
 
     def __len__(self):
         return len(self.df)
@@ -280,6 +330,9 @@ class SpeechQualityDataset(object):
         computed by the HIP front end; the overlapping-window gather (NL:2266-2280) is a host-side view for callers
         that want the reference's item format -- the predict loop never materialises it."""
         assert isinstance(index, int), 'index must be integer (no slice)'
+        if self.double_ended:
+            raise NotImplementedError('item access of a double-ended dataset is not implemented on the HIP path; predict_mos reads the '
+                                      '(degraded, reference) pairs itself')
         if getattr(self, '_engine_factory', None) is None:
             raise RuntimeError('SpeechQualityDataset item access needs bind_engine(...) (spectrograms are computed on the GPU)')
         eng = self._engine_factory()
@@ -373,11 +426,80 @@ def batch_policy(eng, ds, indices, bs):
                                byte_cap=int(os.environ.get('NISQA_BATCH_BYTES', BATCH_BYTE_CAP)))
 
 
+def pair_tokens(ds, indices, num_workers=0):
+    """Work of each item of a double-ended dataset: the degraded file's segments plus the reference file's, from the RIFF headers
+    alone (an unreadable header counts as one segment; the error itself is raised when the file is loaded)."""
+    idx = list(indices)
+    tok = np.zeros(len(idx), dtype=np.int64)
+    for view in (ds, ds.ref_view()):
+        info = _ingest.probe_headers(view, idx, num_workers)
+        ok = info['status'] == _lib_mod.WAV_OK
+        tok += np.where(ok, tokens_of(view, np.where(ok, info['n_frames'], 0), np.where(ok, info['sample_rate'], 48000)), 1)
+    return tok
+
+
+def _predict_de(model, ds, bs, dev, num_workers, on_rows=None):
+    """_predict for a double-ended dataset (NISQA_DE): y_hat [N, 1].  Items are (degraded, reference) file pairs, read with the
+    readers of the single-ended loop (WAV / FLAC, ms_channel) and batched in table order: at least ``bs`` pairs and, unless
+    NISQA_EXACT_BS=1, at least MIN_TOKENS_SA segments of work; rows do not depend on the batch composition.  Over several ranks the
+    shards are work-balanced on pair_tokens."""
+    dev = torch.device(dev)
+    if model._engine is None and dev.type != 'cuda':
+        raise RuntimeError('nisqa_amd has no CPU path: device {} requested but the hot path runs only as HIP kernels '
+                           'on an MI355X'.format(dev))
+    eng = model.engine(dev if dev.index is not None else None)
+    n = len(ds)
+    lo, hi = _dist.shard_range(n)
+    bounds = None
+    rank, world = _dist.world()
+    if world > 1 and os.environ.get('NISQA_SHARD_BY_COUNT') != '1':
+        tok = np.zeros(n, dtype=np.int64)
+        probe_err = None
+        try:
+            if hi > lo:
+                tok[lo:hi] = pair_tokens(ds, range(lo, hi), num_workers)
+        except Exception as e:                                      # noqa: BLE001 (re-raised on every rank below)
+            probe_err = e
+            tok[lo:hi] = 0
+        tok = _dist.all_reduce_sum_i64(tok)
+        _dist.raise_together(probe_err)
+        bounds = _dist.balanced_bounds(tok, world)
+        lo, hi = bounds[rank]
+    y_local = np.zeros((hi - lo, 1), dtype=np.float32)
+    loop_err = None
+    try:
+        bs = max(1, int(bs))
+        min_tok = 0 if os.environ.get('NISQA_EXACT_BS') == '1' else int(os.environ.get('NISQA_MIN_TOKENS', MIN_TOKENS_SA))
+        refs = ds.ref_view()
+        i = lo
+        while i < hi:
+            ids, deg, ref, names, work = [], [], [], [], 0
+            while i < hi and (len(ids) < bs or work < min_tok):
+                d, r = ds.load_audio(i), refs.load_audio(i)
+                ids.append(i)
+                deg.append(d)
+                ref.append(r)
+                names.append((ds.file_path(i), refs.file_path(i)))
+                work += int(tokens_of(ds, [len(d[0]), len(r[0])], [d[1], r[1]]).sum())
+                i += 1
+            out = eng.forward_items(deg + ref, [p[0] for p in names] + [p[1] for p in names])
+            rows = out.cpu().numpy()
+            y_local[np.asarray(ids) - lo] = rows
+            if on_rows is not None:
+                on_rows(ids, rows)
+    except Exception as e:                                          # noqa: BLE001 (raised on every rank below)
+        loop_err = e
+    _dist.raise_together(loop_err)
+    return _dist.gather_rows(y_local, n, lo, hi, dev, bounds)
+
+
 def _predict(model, ds, bs, dev, num_workers, on_rows=None):
     """Shared body of predict_mos / predict_dim: returns y_hat [N, heads] float32 for ALL items of ds
     (clip-sharded over ranks when torch.distributed is initialised, then gathered).
     on_rows(ids, rows): optional callback with every batch's item indices and [B, heads] float32 rows as they come back from
     the device (nisqaModel.predict formats the table cells there, under the next batches' transfers)."""
+    if getattr(ds, 'double_ended', False):
+        return _predict_de(model, ds, bs, dev, num_workers, on_rows)
     dev = torch.device(dev)
     if model._engine is None and dev.type != 'cuda':
         raise RuntimeError('nisqa_amd has no CPU path: device {} requested but the hot path runs only as HIP kernels '

@@ -384,6 +384,9 @@ class nisqaModel(object):
 
     # ---- datasets (reference NISQA_model.py:732-847) ---------------------------------------------
     def _loadDatasets(self):
+        if self.args['double_ended'] and self.args['mode'] in ('predict_file', 'predict_dir'):
+            raise NotImplementedError('NISQA_DE scores a degraded file against its reference file: mode {} has no reference '
+                                      'column; use predict_csv with csv_ref'.format(self.args['mode']))
         if self.args['mode'] == 'predict_file':
             self._loadDatasetsFile()
         elif self.args['mode'] == 'predict_dir':
@@ -450,6 +453,8 @@ class nisqaModel(object):
             dcon = pd.read_csv(os.path.join(self.args['data_dir'], self.args['csv_con']))
         else:
             dcon = None
+        if self.args['double_ended'] and not self.args.get('csv_ref'):
+            raise ValueError('NISQA_DE needs csv_ref: the csv column with the reference file of each row (--csv_ref)')
         self.ds_val = self._dataset(dfile, dcon, self.args['data_dir'], self.args['csv_deg'], False)
 
     # ---- model (reference NISQA_model.py:928-1030) -------------------------------------------------
@@ -473,6 +478,9 @@ class nisqaModel(object):
             self.args['dim'] = False
         if self.args['model'] == 'NISQA_DE':
             self.args['double_ended'] = True
+            if self.args['mode'] == 'main':
+                raise NotImplementedError('NISQA_DE (double-ended) training is out of scope of nisqa_amd (inference only: '
+                                          'predict_csv with csv_ref)')
         else:
             self.args['double_ended'] = False
             self.args['csv_ref'] = None
@@ -485,6 +493,8 @@ class nisqaModel(object):
                 'td_2_sa_dropout', 'td_2_lstm_h', 'td_2_lstm_num_layers', 'td_2_lstm_dropout',
                 'td_2_lstm_bidirectional', 'pool', 'pool_att_h', 'pool_att_dropout']
         self.model_args = {k: self.args[k] for k in keys}
+        if self.args['double_ended']:                                  # reference NISQA_model.py:1009-1015
+            self.model_args.update({k: self.args[k] for k in ('de_align', 'de_align_apply', 'de_fuse_dim', 'de_fuse')})
 
         print('Model architecture: ' + self.args['model'])
         if self.args['model'] == 'NISQA':
@@ -492,7 +502,7 @@ class nisqaModel(object):
         elif self.args['model'] == 'NISQA_DIM':
             self.model = NL.NISQA_DIM(**self.model_args)
         elif self.args['model'] == 'NISQA_DE':
-            raise NotImplementedError('NISQA_DE (double-ended) is out of scope of nisqa_amd')
+            self.model = NL.NISQA_DE(**self.model_args)
         else:
             raise NotImplementedError('Model not available')
 

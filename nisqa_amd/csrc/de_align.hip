@@ -1,0 +1,240 @@
+// Alignment + fusion of the double-ended model (NISQA_DE, reference nisqa/NISQA_lib.py:406-424): for every degraded token i the
+// reference's token it aligns to, then the fused feature row -- Alignment.forward (NISQA_lib.py:1264-1270) with AttDot / AttCosine
+// (:1272-1294) and ApplyHardAttention / ApplySoftAttention (:1359-1378), then Fusion.forward (:1405-1417) without lin_fusion.
+//
+// One workgroup (4 waves) per 64-token tile of one degraded clip.  Each lane keeps ONE degraded token's 64 features in registers
+// (lane i of every wave: token i of the tile); the clip's reference tokens stream through LDS in 64-token blocks (16 KB), wave w
+// scoring rows 16 w .. 16 w + 15 of each block.  Every lane of a wave reads the same LDS row at the same time (a broadcast), so the
+// score loop is conflict-free; a score is a k-ordered fp32 fma chain over the 64 features -- exact fp32 in every precision form.
+//   hard: a running (max, index) per lane over its rows, ascending, strict '>' (the lowest index wins a tie, as torch's argmax);
+//         the four waves' winners are merged the same way.  The reference takes the argmax of the SOFTMAX of the scores; the two
+//         can only differ where rounding of the softmax merges scores a few ulps apart -- this kernel takes it over the raw scores
+//         (DESIGN.md 4.8).
+//   soft: an online softmax per lane (block max, one rescale of the 64 accumulators per block), the four waves' (max, sum, rows)
+//         merged through LDS in a fixed order (deterministic).
+//   cosine: every row divided by max(||row||, 1e-8) once, then the dot product -- torch's CosineSimilarity, which normalises each
+//         operand before the product (not q.y / (|q| |y|)).
+// Reference tokens j >= n_wins_y are never read (the reference masks their scores to -inf).  Rows of degraded tokens >= n_wins_x
+// are written as zeros: the second self-attention multiplies them by zero probabilities, where a NaN would survive.
+#include "common.hpp"
+#include "../../include/nisqa_hip.h"
+
+namespace {
+
+constexpr int DA_D = 64;                               // feature width of the first self-attention (d_model)
+constexpr int DA_TILE = 64;                            // degraded tokens per workgroup
+constexpr int DA_BLK = 64;                             // reference tokens per LDS block
+constexpr int DA_WAVES = 4;
+constexpr int DA_ROWS = DA_BLK / DA_WAVES;             // rows of a block one wave scores
+
+__global__ __launch_bounds__(256) void de_align_fuse_kernel(const float* __restrict__ x, const int32_t* __restrict__ deg_off,
+                                                            const int32_t* __restrict__ deg_n, const int32_t* __restrict__ ref_off,
+                                                            const int32_t* __restrict__ ref_n, int n_pairs, int cosine, int soft,
+                                                            int fuse, int ld_out, float* __restrict__ out,
+                                                            int32_t* __restrict__ idx_out) {
+    __shared__ float yb[DA_BLK][DA_D];                                 // one block of reference rows (normalised for cosine)
+    __shared__ float mm[DA_WAVES][DA_TILE], ml[DA_WAVES][DA_TILE];     // (max, sum) or (best score, index) per wave and token
+    const int t = threadIdx.x, i = t & 63, w = t >> 6;
+    const int tile0 = blockIdx.x * DA_TILE;
+    const int b = find_segment(deg_off, n_pairs, tile0);
+    const int nx = deg_n[b], ny = ref_n[b];
+    const int ti = tile0 - deg_off[b] + i;                             // this lane's token within its clip
+    const bool valid = ti < nx;
+    const int F = fuse == 0 ? 3 * DA_D : 2 * DA_D;
+    const int q0 = 16 * w;                                             // output: features q0 .. q0 + 15 of every part
+    if (tile0 - deg_off[b] >= nx) {                                    // a tile of padding rows only
+        float* o = out + (size_t)(tile0 + i) * ld_out;
+        for (int p = 0; p < F / DA_D; ++p)
+#pragma unroll
+            for (int e = 0; e < 16; e += 4) *(f32x4*)(o + p * DA_D + q0 + e) = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (idx_out && w == 0) idx_out[tile0 + i] = -1;
+        return;
+    }
+    const float* xr = x + (size_t)(tile0 + i) * DA_D;
+    const float* yr0 = x + (size_t)ref_off[b] * DA_D;
+
+    float q[DA_D];
+    if (valid) {
+#pragma unroll
+        for (int d = 0; d < DA_D; d += 4) {
+            const f32x4 v = *(const f32x4*)(xr + d);
+            q[d] = v[0]; q[d + 1] = v[1]; q[d + 2] = v[2]; q[d + 3] = v[3];
+        }
+    } else {
+#pragma unroll
+        for (int d = 0; d < DA_D; ++d) q[d] = 0.f;
+    }
+    if (cosine) {
+        float ss = 0.f;
+#pragma unroll
+        for (int d = 0; d < DA_D; ++d) ss = fmaf(q[d], q[d], ss);
+        const float nrm = fmaxf(sqrtf(ss), 1e-8f);
+#pragma unroll
+        for (int d = 0; d < DA_D; ++d) q[d] = q[d] / nrm;
+    }
+
+    float best = -INFINITY, m = -INFINITY, l = 0.f;                    // hard: (best, bi); soft: (m, l, o)
+    int bi = 0;
+    float o[DA_D];
+#pragma unroll
+    for (int d = 0; d < DA_D; ++d) o[d] = 0.f;
+
+    const int nblk = (ny + DA_BLK - 1) / DA_BLK;
+    for (int jb = 0; jb < nblk; ++jb) {
+        __syncthreads();                                               // the previous block is consumed
+        {   // stage: thread t -> row t >> 2, features 16 (t & 3) .. + 15
+            const int jr = t >> 2, f0 = 16 * (t & 3), j = jb * DA_BLK + jr;
+            f32x4 v[4];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = j < ny ? *(const f32x4*)(yr0 + (size_t)j * DA_D + f0 + 4 * e) : f32x4{0.f, 0.f, 0.f, 0.f};
+            if (cosine) {
+                float ss = 0.f;
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) ss = fmaf(v[e][k], v[e][k], ss);
+                ss += __shfl_xor(ss, 1);
+                ss += __shfl_xor(ss, 2);
+                const float nrm = fmaxf(sqrtf(ss), 1e-8f);
+#pragma unroll
+                for (int e = 0; e < 4; ++e)
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) v[e][k] = v[e][k] / nrm;
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) *(f32x4*)(&yb[jr][f0 + 4 * e]) = v[e];
+        }
+        __syncthreads();
+        const int j0 = jb * DA_BLK + q0;                               // this wave's first row of the block
+        const int nr = min(DA_ROWS, ny - j0);                          // valid rows of it (may be <= 0)
+        if (!valid || nr <= 0) continue;
+        float s[DA_ROWS];
+#pragma unroll
+        for (int r = 0; r < DA_ROWS; ++r) {
+            float acc = 0.f;
+#pragma unroll
+            for (int d = 0; d < DA_D; d += 4) {
+                const f32x4 y4 = *(const f32x4*)(&yb[q0 + r][d]);
+                acc = fmaf(q[d], y4[0], acc);
+                acc = fmaf(q[d + 1], y4[1], acc);
+                acc = fmaf(q[d + 2], y4[2], acc);
+                acc = fmaf(q[d + 3], y4[3], acc);
+            }
+            s[r] = r < nr ? acc : -INFINITY;                           // key mask (NISQA_lib.py:1258-1262)
+        }
+        if (!soft) {
+#pragma unroll
+            for (int r = 0; r < DA_ROWS; ++r)
+                if (s[r] > best) { best = s[r]; bi = j0 + r; }
+        } else {
+            float mb = -INFINITY;
+#pragma unroll
+            for (int r = 0; r < DA_ROWS; ++r) mb = fmaxf(mb, s[r]);
+            const float mn = fmaxf(m, mb);                             // finite: row j0 is valid
+            const float alpha = expf(m - mn);                          // 0 while m is still -inf
+            l *= alpha;
+#pragma unroll
+            for (int d = 0; d < DA_D; ++d) o[d] *= alpha;
+#pragma unroll
+            for (int r = 0; r < DA_ROWS; ++r) {
+                if (r >= nr) break;
+                const float p = expf(s[r] - mn);
+                l += p;
+#pragma unroll
+                for (int d = 0; d < DA_D; d += 4) {                    // the RAW reference row (ApplySoftAttention: bmm(att, y))
+                    const f32x4 y4 = *(const f32x4*)(yr0 + (size_t)(j0 + r) * DA_D + d);
+                    o[d] = fmaf(p, y4[0], o[d]);
+                    o[d + 1] = fmaf(p, y4[1], o[d + 1]);
+                    o[d + 2] = fmaf(p, y4[2], o[d + 2]);
+                    o[d + 3] = fmaf(p, y4[3], o[d + 3]);
+                }
+            }
+            m = mn;
+        }
+    }
+
+    // merge the four waves' partial results (through LDS, wave 1, 2, 3 in turn: a fixed order); wave 0 ends with the aligned row
+    // (soft, left in yb as [feature][token]) or index (hard) of every token
+    float (*buf)[DA_TILE] = yb;                                        // yb is free once the last block is scored
+    mm[w][i] = soft ? m : best;
+    ml[w][i] = soft ? l : __int_as_float(bi);
+    __syncthreads();
+    if (!soft) {
+        if (w == 0 && valid) {
+            for (int v = 1; v < DA_WAVES; ++v) {                       // a wave's rows ascend within a block but not across
+                const float sv = mm[v][i];                             // blocks: compare (score, index) explicitly
+                const int iv = __float_as_int(ml[v][i]);
+                if (sv > best || (sv == best && iv < bi)) { best = sv; bi = iv; }
+            }
+            ml[0][i] = __int_as_float(bi);
+        }
+    } else {
+        float M = -INFINITY, L = 0.f;
+        for (int v = 0; v < DA_WAVES; ++v) M = fmaxf(M, mm[v][i]);
+        for (int v = 0; v < DA_WAVES; ++v) L = fmaf(ml[v][i], valid ? expf(mm[v][i] - M) : 0.f, L);
+        const float a = valid ? expf(m - M) : 0.f;                     // 0 for a wave that saw no valid row
+#pragma unroll
+        for (int d = 0; d < DA_D; ++d) o[d] *= a;
+        for (int v = 1; v < DA_WAVES; ++v) {
+            if (w == v)
+#pragma unroll
+                for (int d = 0; d < DA_D; ++d) buf[d][i] = o[d];
+            __syncthreads();
+            if (w == 0)
+#pragma unroll
+                for (int d = 0; d < DA_D; ++d) o[d] += buf[d][i];
+            __syncthreads();
+        }
+        if (w == 0) {
+            const float inv = valid ? 1.0f / L : 0.f;
+#pragma unroll
+            for (int d = 0; d < DA_D; ++d) buf[d][i] = o[d] * inv;
+        }
+    }
+    __syncthreads();
+
+    // fusion: every wave writes features q0 .. q0 + 15 of each part of row i
+    float* orow = out + (size_t)(tile0 + i) * ld_out;
+    if (!valid) {
+        for (int p = 0; p < F / DA_D; ++p)
+#pragma unroll
+            for (int e = 0; e < 16; e += 4) *(f32x4*)(orow + p * DA_D + q0 + e) = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (idx_out && w == 0) idx_out[tile0 + i] = -1;
+        return;
+    }
+    const int jsel = soft ? 0 : __float_as_int(ml[0][i]);
+    if (idx_out && w == 0) idx_out[tile0 + i] = soft ? -1 : jsel;
+#pragma unroll
+    for (int e = 0; e < 16; e += 4) {
+        const f32x4 xv = *(const f32x4*)(xr + q0 + e);
+        f32x4 yv;
+        if (soft) yv = f32x4{buf[q0 + e][i], buf[q0 + e + 1][i], buf[q0 + e + 2][i], buf[q0 + e + 3][i]};
+        else yv = *(const f32x4*)(yr0 + (size_t)jsel * DA_D + q0 + e);
+        if (fuse == 0) {                                               // 'x/y/-': [x, y, x - y]
+            *(f32x4*)(orow + q0 + e) = xv;
+            *(f32x4*)(orow + DA_D + q0 + e) = yv;
+            *(f32x4*)(orow + 2 * DA_D + q0 + e) = xv - yv;
+        } else if (fuse == 1) {                                        // '+/-': [x + y, x - y]
+            *(f32x4*)(orow + q0 + e) = xv + yv;
+            *(f32x4*)(orow + DA_D + q0 + e) = xv - yv;
+        } else {                                                       // 'x/y': [x, y]
+            *(f32x4*)(orow + q0 + e) = xv;
+            *(f32x4*)(orow + DA_D + q0 + e) = yv;
+        }
+    }
+}
+
+}  // namespace
+
+extern "C" int nisqa_de_align_fuse(const float* x, const int32_t* deg_tok_off, const int32_t* deg_n_wins, const int32_t* ref_tok_off,
+                                   const int32_t* ref_n_wins, int32_t n_pairs, int32_t total_deg_tok_padded, int32_t align,
+                                   int32_t apply, int32_t fuse, int32_t ld_out, float* out, int32_t* idx_out, void* stream) {
+    const int F = fuse == 0 ? 3 * DA_D : 2 * DA_D;
+    if (n_pairs <= 0 || total_deg_tok_padded <= 0 || (total_deg_tok_padded % DA_TILE) || align < 0 || align > 1 || apply < 0 ||
+        apply > 1 || fuse < 0 || fuse > 2 || ld_out < F || (ld_out & 3))
+        return NISQA_ERR_ARG;
+    NQ_LAUNCH_BEGIN();
+    hipLaunchKernelGGL(de_align_fuse_kernel, dim3(total_deg_tok_padded / DA_TILE), dim3(256), 0, (hipStream_t)stream, x, deg_tok_off,
+                       deg_n_wins, ref_tok_off, ref_n_wins, n_pairs, align, apply, fuse, ld_out, out, idx_out);
+    return NQ_LAUNCH_STATUS();
+}

@@ -451,3 +451,163 @@ class HipNisqa(object):
                                                self.n_heads, _ptr(self.pool_w), _ptr(ws), _ptr(out), self._stream()),
                        'nisqa_pool_att')
         return out
+
+
+# -- NISQA_DE (double-ended): reference NISQA_lib.py:272-424 ------------------------------------------------------------------
+DE_ALIGN = {'dot': 0, 'cosine': 1}                 # AttDot / AttCosine (NISQA_lib.py:1272-1294)
+DE_APPLY = {'hard': 0, 'soft': 1}                  # ApplyHardAttention / ApplySoftAttention (:1359-1378)
+DE_FUSE = {'x/y/-': 0, '+/-': 1, 'x/y': 2}         # Fusion without lin_fusion (:1380-1417)
+DE_FUSE_WIDTH = {'x/y/-': 192, '+/-': 128, 'x/y': 128}
+DE_FEAT_LD = 384                                   # row stride of the fused features: the self-attention kernels' projection width
+
+
+def check_de_args(args, precision=None):
+    """The NISQA_DE configurations the HIP engine runs; anything else raises NotImplementedError naming the option -- before any GPU
+    work (no device is touched here)."""
+    a = args
+    g = lambda k, d=None: a.get(k, d)
+    if g('cnn_model') != 'adapt':
+        raise NotImplementedError('NISQA_DE on the HIP engine needs cnn_model=adapt, got cnn_model={}'.format(g('cnn_model')))
+    if list(g('cnn_pool_1') or []) != [24, 7] or list(g('cnn_pool_2') or []) != [12, 5] or list(g('cnn_pool_3') or []) != [6, 3] \
+            or g('cnn_fc_out_h') is not None or (g('cnn_c_out_1'), g('cnn_c_out_2'), g('cnn_c_out_3')) != (16, 32, 64):
+        raise NotImplementedError('NISQA_DE on the HIP engine needs the nisqa.tar CNN geometry (cnn_c_out 16/32/64, pools 24x7/12x5/6x3, '
+                                  'cnn_fc_out_h null)')
+    for td in ('td', 'td_2'):
+        if g(td) != 'self_att':
+            raise NotImplementedError('NISQA_DE on the HIP engine needs {}=self_att, got {}={}'.format(td, td, g(td)))
+        if g(td + '_sa_d_model') != 64 or g(td + '_sa_nhead') != 1 or g(td + '_sa_h') != 64 or not g(td + '_sa_num_layers'):
+            raise NotImplementedError('NISQA_DE on the HIP engine needs {0}_sa_d_model=64, {0}_sa_nhead=1, {0}_sa_h=64'.format(td))
+        if g(td + '_sa_pos_enc'):
+            raise NotImplementedError('NISQA_DE on the HIP engine has no positional encoding ({}_sa_pos_enc)'.format(td))
+    if g('pool') != 'att' or not g('pool_att_h'):
+        raise NotImplementedError('NISQA_DE on the HIP engine needs pool=att, got pool={}'.format(g('pool')))
+    if g('de_align', 'dot') not in DE_ALIGN:
+        raise NotImplementedError('NISQA_DE on the HIP engine: de_align={} is not supported (dot, cosine)'.format(g('de_align', 'dot')))
+    if g('de_align_apply', 'hard') not in DE_APPLY:
+        raise NotImplementedError('NISQA_DE on the HIP engine: de_align_apply={} is not supported (hard, soft)'.format(
+            g('de_align_apply', 'hard')))
+    if g('de_fuse', 'x/y/-') not in DE_FUSE:
+        raise NotImplementedError('NISQA_DE on the HIP engine: de_fuse={} is not supported (x/y/-, +/-, x/y)'.format(g('de_fuse', 'x/y/-')))
+    if g('de_fuse_dim') is not None:
+        raise NotImplementedError('NISQA_DE on the HIP engine: de_fuse_dim={} (lin_fusion) is not supported'.format(g('de_fuse_dim')))
+    if precision == 'bf16x3':
+        raise NotImplementedError('NISQA_DE on the HIP engine: precision bf16x3 is not supported (f32, bf16x6, f16x4, f16x3)')
+
+
+class HipNisqaDE(object):
+    """NISQA_DE (double-ended: a degraded clip scored against its reference clip, NISQA_lib.py:406-424) on one MI355X.
+    A batch of B pairs is ONE plan of 2B clips: the B degraded clips, then their B reference clips.  mel + AdaptCNN and the first
+    self-attention run on all 2B clips with the shared weights; nisqa_de_align_fuse aligns and fuses; the second self-attention
+    (time_dependency_2) and the attention pooling run on the B degraded clips."""
+
+    def __init__(self, args, state_dict, device=None, precision=None):
+        prec = precision or os.environ.get('NISQA_HIP_PRECISION') or DEFAULT_PRECISION
+        check_de_args(args, prec)
+        self.args = args
+        single = dict(args, model='NISQA', td_2='skip')               # mel, CNN, time_dependency, pool.model: the single-ended engine
+        self.base = HipNisqa(single, state_dict, device, prec)
+        self.lib, self.device, self.precision = self.base.lib, self.base.device, self.base.precision
+        self.n_heads = 1
+        self.align = DE_ALIGN[args.get('de_align', 'dot')]
+        self.apply = DE_APPLY[args.get('de_align_apply', 'hard')]
+        self.fuse = DE_FUSE[args.get('de_fuse', 'x/y/-')]
+        self.fuse_width = DE_FUSE_WIDTH[args.get('de_fuse', 'x/y/-')]
+        self.n_layers2 = int(args['td_2_sa_num_layers'])
+        up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
+        pfx = 'time_dependency_2.model.'
+        self.td2_w = up(_w.pack_self_att(state_dict, self.n_layers2, pfx, in_features=self.fuse_width))
+        self.td2_wb = up(_w.pack_self_att_bf16(state_dict, self.n_layers2, pfx, terms=3, in_features=self.fuse_width).view(np.int16)) \
+            if self.base.td_precision == 'bf16x6' else None
+
+    def _stream(self):
+        return self.base._stream()
+
+    # -- plans ------------------------------------------------------------------------------------------
+    def plan(self, lengths_deg, lengths_ref, sr, names=None):
+        """One plan of 2B clips (degraded, then reference) at one rate."""
+        return self.base.plan(list(lengths_deg) + list(lengths_ref), sr, names)
+
+    # -- stages -----------------------------------------------------------------------------------------
+    def align_fuse(self, x, plan, want_idx=False):
+        """x: [NP, 64] first self-attention output of the plan's 2B clips -> (fused [NP_deg, 384] with the fused features in columns
+        0 .. F-1 and zeros behind them, hard-mode indices [NP_deg] int32 or None)."""
+        B = plan.n_clips // 2
+        assert plan.n_clips == 2 * B and x.shape == (plan.total_tok, 64) and x.dtype == torch.float32
+        d = plan.to(self.device)
+        np_deg = int(plan.tok_off[B])
+        out = torch.zeros((np_deg, DE_FEAT_LD), dtype=torch.float32, device=self.device)
+        idx = torch.empty(np_deg, dtype=torch.int32, device=self.device) if want_idx else None
+        t, n = d['tok_off'], d['n_wins']
+        _lib.check(self.lib.nisqa_de_align_fuse(_ptr(x), _ptr(t), _ptr(n), _ptr(t[B:]), _ptr(n[B:]), B, np_deg, self.align, self.apply,
+                                                self.fuse, DE_FEAT_LD, _ptr(out), _ptr(idx) if want_idx else None, self._stream()),
+                   'nisqa_de_align_fuse')
+        return out, idx
+
+    def td2_pool(self, fused, dplan):
+        """time_dependency_2 + pool on the fused features of the degraded clips (dplan: their plan) -> [B, 1]"""
+        d = dplan.to(self.device)
+        np_ = dplan.total_tok
+        ws = torch.empty(np_ * 64 * 9, dtype=torch.float32, device=self.device)
+        x = torch.zeros((np_, 64), dtype=torch.float32, device=self.device)
+        out = torch.empty((dplan.n_clips, 1), dtype=torch.float32, device=self.device)
+        b = self.base
+        if b.td_precision == 'bf16x6':
+            wsp = torch.empty(np_ * 16 + dplan.n_clips, dtype=torch.float32, device=self.device)
+            _lib.check(self.lib.nisqa_td_pool_bf16x6(_ptr(fused), _ptr(d['tok_off']), _ptr(d['n_wins']), dplan.n_clips, np_, self.n_layers2,
+                                                     _ptr(self.td2_w), _ptr(self.td2_wb), 1, _ptr(b.pool_wb), _ptr(ws), _ptr(x), _ptr(wsp),
+                                                     _ptr(out), self._stream()), 'nisqa_td_pool_bf16x6')
+            return out
+        _lib.check(self.lib.nisqa_td_selfatt(_ptr(fused), _ptr(d['tok_off']), _ptr(d['n_wins']), dplan.n_clips, np_, self.n_layers2,
+                                             _ptr(self.td2_w), _ptr(ws), _ptr(x), self._stream()), 'nisqa_td_selfatt')
+        wsp = torch.empty(np_ * 16, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.nisqa_pool_att(_ptr(x), _ptr(d['tok_off']), _ptr(d['n_wins']), dplan.n_clips, np_, 1, _ptr(b.pool_w),
+                                           _ptr(wsp), _ptr(out), self._stream()), 'nisqa_pool_att')
+        return out
+
+    def forward_features(self, feat, plan, want_idx=False):
+        """feat [NP, 384]: AdaptCNN output of the plan's 2B clips -> ([B, 1], hard-mode indices or None)"""
+        x = self.base.td(feat, plan)                   # materialised: the alignment reads every token of both clips
+        fused, idx = self.align_fuse(x, plan, want_idx)
+        B = plan.n_clips // 2
+        out = self.td2_pool(fused, BatchPlan.from_n_wins(plan.n_wins[:B]))
+        return (out, idx) if want_idx else out
+
+    def features(self, pcm, plan, sr):
+        mel, floor = self.base.mel(pcm, plan, sr, clamp=False)
+        return self.base.cnn(mel, floor, plan)[0]
+
+    def forward_pcm(self, pcm, plan, sr, want_idx=False):
+        """pcm: device tensor of the plan's 2B clips back to back (degraded, then reference; float32 or int16 PCM) -> [B, 1]"""
+        assert pcm.is_cuda and pcm.numel() == plan.total_samples
+        return self.forward_features(self.features(pcm, plan, sr), plan, want_idx)
+
+    def forward_items(self, items, names=None):
+        """items: 2B host clips (samples int16 / float32, sr) -- the degraded clips, then the reference clips -> [B, 1] on the device.
+        Clips of one (rate, sample type) share one mel + CNN launch; with several such groups the CNN rows are gathered into the
+        2B-clip layout (a copy) before the self-attention."""
+        names = names if names is not None else [None] * len(items)
+        groups = {}
+        for c, (y, sr) in enumerate(items):
+            groups.setdefault((int(sr), y.dtype == np.int16), []).append(c)
+        b = self.base
+        n_wins = np.zeros(len(items), np.int64)
+        parts = []
+        for (sr, _), cs in groups.items():
+            lengths = [len(items[c][0]) for c in cs]
+            gplan = b.audio_plan(lengths, sr, [names[c] for c in cs])
+            pcm = torch.from_numpy(np.concatenate([items[c][0] for c in cs])).to(self.device)
+            pcm = b.resample(pcm, lengths, sr)
+            parts.append((cs, gplan, self.features(pcm, gplan, b.rate(sr))))
+            n_wins[cs] = gplan.n_wins
+        plan = BatchPlan.from_n_wins(n_wins)
+        if len(parts) == 1 and parts[0][0] == list(range(len(items))):
+            feat = parts[0][2]
+        else:
+            src, base_row = np.zeros(plan.total_tok, np.int64), 0
+            for cs, gplan, f in parts:
+                for k, c in enumerate(cs):
+                    rows = int(plan.tok_off[c + 1] - plan.tok_off[c])
+                    src[plan.tok_off[c]:plan.tok_off[c] + rows] = base_row + gplan.tok_off[k] + np.arange(rows)
+                base_row += gplan.total_tok
+            feat = torch.cat([f for _, _, f in parts])[torch.from_numpy(src).to(self.device)]
+        return self.forward_features(feat, plan)

@@ -170,17 +170,33 @@ def pack_adapt_cnn(sd, pfx='cnn.model.'):
     return blob
 
 
-def pack_self_att(sd, n_layers, pfx='time_dependency.model.'):
-    """SelfAttention (d_model 64, 1 head, sa_h 64, input 384) -> float32 blob."""
-    if tuple(sd[pfx + 'linear.weight'].shape) != (64, 384):
-        raise NotImplementedError('HIP self-attention kernel needs Linear 384->64')
+SA_IN_FEATURES = (384, 192, 128)      # AdaptCNN fan-out; NISQA_DE's fused features 'x/y/-' (3 x 64) and '+/-' / 'x/y' (2 x 64)
+
+
+def _proj_weight(sd, pfx, in_features):
+    """SelfAttention.linear.weight [64][in_features] as the kernels' [64][384]: the columns past in_features are zero.  The kernels
+    contract K = 384 in K-steps from column 0 up, so the zero columns only add exact zero products after the real ones -- the result
+    is bit for bit that of an in_features-wide projection with the same contraction order."""
+    if in_features not in SA_IN_FEATURES:
+        raise NotImplementedError('HIP self-attention kernel takes an input width of {}, got {}'.format(SA_IN_FEATURES, in_features))
+    if tuple(sd[pfx + 'linear.weight'].shape) != (64, in_features):
+        raise NotImplementedError('HIP self-attention kernel needs Linear {}->64, got {}'.format(
+            in_features, tuple(sd[pfx + 'linear.weight'].shape)))
+    w = np.zeros((64, 384), np.float64)
+    w[:, :in_features] = _np(sd, pfx + 'linear.weight')
+    return w
+
+
+def pack_self_att(sd, n_layers, pfx='time_dependency.model.', in_features=384):
+    """SelfAttention (d_model 64, 1 head, sa_h 64, input in_features: 384, or 192 / 128 zero-extended to 384) -> float32 blob."""
+    wproj = _proj_weight(sd, pfx, in_features)
     blob = np.zeros(TD_LAYER0 + n_layers * TDL_FLOATS, np.float32)
 
     def put(off, arr):
         arr = np.asarray(arr, np.float32).reshape(-1)
         blob[off:off + arr.size] = arr
 
-    put(TD_PROJ_AF, linear_a_fragments(_np(sd, pfx + 'linear.weight')))
+    put(TD_PROJ_AF, linear_a_fragments(wproj))
     put(TD_PROJ_B, _np(sd, pfx + 'linear.bias'))
     put(TD_LN0_G, _np(sd, pfx + 'norm1.weight'))
     put(TD_LN0_B, _np(sd, pfx + 'norm1.bias'))
@@ -433,9 +449,11 @@ def linear_a_fragments_bf16_t16(w, chain, terms=3):
     return np.stack(bf16_split(vals, terms), 3).reshape(-1)
 
 
-def pack_self_att_bf16(sd, n_layers, pfx='time_dependency.model.', terms=2):
+def pack_self_att_bf16(sd, n_layers, pfx='time_dependency.model.', terms=2, in_features=384):
     """terms = 2: hi / lo fragments of td_bf16.hip (32 x 16 fragments, TDB_* offsets); terms = 3: hi / mid / lo fragments of
-    td16_bf16x6.hip (16 x 32 fragments for its 16-token tiles; the TDX_* offsets: the blocks hold the same number of elements)"""
+    td16_bf16x6.hip (16 x 32 fragments for its 16-token tiles; the TDX_* offsets: the blocks hold the same number of elements).
+    in_features: as pack_self_att (the projection zero-extended to 384 columns)."""
+    wproj = _proj_weight(sd, pfx, in_features)
     if terms == 2:
         PROJ, LAYER0, QKV, OUT, FF1, FF2, LSZ = TDB_PROJ, TDB_LAYER0, TDBL_QKV, TDBL_OUT, TDBL_FF1, TDBL_FF2, TDBL_U16S
         frag = lambda w, chain: linear_a_fragments_bf16(w, chain=chain, terms=2)
@@ -447,7 +465,7 @@ def pack_self_att_bf16(sd, n_layers, pfx='time_dependency.model.', terms=2):
     def put(off, fr):
         blob[off:off + fr.size] = fr
 
-    put(PROJ, frag(_np(sd, pfx + 'linear.weight'), False))
+    put(PROJ, frag(wproj, False))
     for l in range(n_layers):
         p = pfx + 'layers.%d.' % l
         base = LAYER0 + l * LSZ

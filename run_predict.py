@@ -19,6 +19,10 @@ parser.add_argument('--csv_deg', type=str, help='column in csv with files name/p
 parser.add_argument('--num_workers', type=int, default=0, help='number of workers for pytorchs dataloader')
 parser.add_argument('--bs', type=int, default=1, help='batch size for predicting')
 parser.add_argument('--ms_channel', type=int, help='audio channel in case of stereo file')
+# the one flag the reference lacks: a double-ended (NISQA_DE) checkpoint in predict_csv mode reads each row's reference file from this
+# column (absent: the checkpoint's own csv_ref)
+parser.add_argument('--csv_ref', type=str, default=argparse.SUPPRESS,
+                    help='column in csv with the reference file name/path (NISQA_DE checkpoints)')
 
 
 def build_args(argv=None):
