@@ -141,7 +141,7 @@ def bilstm(sd, x, pfx='time_dependency.model.lstm.'):
         w_ih, w_hh = sd[pfx + 'weight_ih_l0' + sfx], sd[pfx + 'weight_hh_l0' + sfx]
         b = sd[pfx + 'bias_ih_l0' + sfx] + sd[pfx + 'bias_hh_l0' + sfx]
         H = w_hh.shape[1]
-        h = torch.zeros(H); c = torch.zeros(H); out = []
+        h = torch.zeros(H, dtype=seq.dtype); c = torch.zeros(H, dtype=seq.dtype); out = []
         for t in range(seq.shape[0]):
             g = w_ih @ seq[t] + w_hh @ h + b
             i, f, gg, o = torch.sigmoid(g[:H]), torch.sigmoid(g[H:2 * H]), torch.tanh(g[2 * H:3 * H]), torch.sigmoid(g[3 * H:])

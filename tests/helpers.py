@@ -78,6 +78,27 @@ def functional_loop_clips(d):
     return st
 
 
+def tok_offsets(n_wins, gran=64, slack=0):
+    """tok_off of ``n_wins`` with every clip padded to a multiple of ``gran`` tokens, plus ``slack`` extra rows for every
+    other clip (clips 1, 3, 5, ...)."""
+    n = np.asarray(n_wins, np.int64).reshape(-1)
+    pad = -(-n // gran) * gran + slack * (np.arange(len(n)) % 2)
+    return np.concatenate([[0], np.cumsum(pad)]).astype(np.int32)
+
+
+def plan_with_layout(n_wins, tok_off, frame_off=None):
+    """A BatchPlan over ``n_wins`` with a caller-chosen token layout (and frame layout, for the CNN entries that read mel_tm)."""
+    from nisqa_amd.engine import BatchPlan
+    plan = BatchPlan.from_n_wins(n_wins)
+    plan.tok_off = np.asarray(tok_off, np.int32)
+    plan.total_tok = int(plan.tok_off[-1])
+    assert len(plan.tok_off) == plan.n_clips + 1 and (np.diff(plan.tok_off) >= plan.n_wins).all()
+    if frame_off is not None:
+        plan.frame_off = np.asarray(frame_off, np.int32)
+        plan.total_frames = int(plan.frame_off[-1])
+    return plan
+
+
 def eval_frame_to_arrays(prefix, df):
     """A results frame of eval_results as plain arrays (no pickles) under ``prefix``."""
     out = {prefix + 'columns': np.array(list(df.columns)), prefix + 'index': df.index.to_numpy()}
