@@ -229,7 +229,15 @@ int nisqa_pool_final(const int32_t* tok_off, const int32_t* n_wins, int32_t n_cl
  * nisqa_lstm_laststep replaces LSTM.forward (bidirectional, hidden 128; NISQA_lib.py:925-943) and
  * PoolLastStepBi.forward (NISQA_lib.py:1107-1115): out[B][1]; hfin_ws scratch [B][256] floats; seq_opt (may be
  * NULL) receives the full [NP][256] LSTM output; lstm_w from nisqa_amd.weights.pack_lstm_laststep.
+ * nisqa_lstm_pool is the same BiLSTM followed by the pooling pool_mode selects (NISQA_lib.py:1085-1224):
+ * NISQA_LSTM_POOL_LAST_STEP_BI (PoolLastStepBi: bit-identical to nisqa_lstm_laststep), NISQA_LSTM_POOL_AVG (PoolAvg:
+ * the masked mean over the clip's n_wins steps, summed in float64) or NISQA_LSTM_POOL_MAX (PoolMax: the masked maximum),
+ * then the [256] -> 1 linear layer; hfin_ws [B][256] receives the pooled vector (forward direction in 0..127, backward in
+ * 128..255).  Any other pool_mode, or n_clips <= 0, returns NISQA_ERR_ARG before any launch.
  * ------------------------------------------------------------------------------------------ */
+#define NISQA_LSTM_POOL_LAST_STEP_BI 0
+#define NISQA_LSTM_POOL_AVG 1
+#define NISQA_LSTM_POOL_MAX 2
 int nisqa_cnn_standard(const float* mel_tm, const int32_t* frame_off, const int32_t* tok_off,
                        const int32_t* n_wins, const float* clip_floor, int32_t n_clips,
                        int32_t total_tok_padded, int32_t seg_hop, const float* cnn_std_w,
@@ -253,6 +261,9 @@ int nisqa_cnn_standard_f16(const float* mel_tm, const int32_t* frame_off, const 
 int nisqa_lstm_laststep(const float* feat20, const int32_t* tok_off, const int32_t* n_wins,
                         int32_t n_clips, const float* lstm_w, float* hfin_ws, float* seq_opt,
                         float* out, void* stream);
+int nisqa_lstm_pool(const float* feat20, const int32_t* tok_off, const int32_t* n_wins,
+                    int32_t n_clips, const float* lstm_w, int32_t pool_mode, float* hfin_ws,
+                    float* seq_opt, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Whole forward for one batch: replaces the body of the per-batch step of predict_dim /
@@ -281,7 +292,9 @@ typedef struct {
     const uint16_t* td_wb;   /* split-bf16 self-attention fragments, or NULL */
     const uint16_t* pool_wb; /* split-bf16 pooling fragments, or NULL */
     int32_t arch;            /* 0 = CNN-SA-AP (nisqa.tar, nisqa_mos_only.tar); 1 = StandardCNN + BiLSTM + last-step
-                              * pooling (nisqa_tts.tar): cnn_w = cnn_std_w blob, td_w = lstm_w blob, pool_w unused */
+                              * pooling (nisqa_tts.tar): cnn_w = cnn_std_w blob, td_w = lstm_w blob, pool_w unused;
+                              * 2 / 3 = StandardCNN + BiLSTM + average / max pooling (the CNN-LSTM-AVG recipe and its
+                              * pool: max variant), blobs as for arch 1; any other value: NISQA_ERR_ARG */
     /* Batches may be in flight on SEVERAL streams at once (the predict loop keeps two): every kernel pair of this library
      * is bit-exact under overlap.  (Round 1 kept the mel + CNN sections of different streams apart with two event
      * fields here; the cause -- a gfx950 packed-f32 op_sel form that misreads next to another kernel's bf16 MFMA waves,

@@ -120,7 +120,7 @@ class _LSTMParams(nn.Module):
             p_.requires_grad_(False)
 
 
-class _PoolLastStepBiParams(nn.Module):
+class _PoolLastStepBiParams(nn.Module):            # the [256] -> 1 linear layer of PoolLastStepBi, PoolAvg and PoolMax alike
     def __init__(self, d):
         super().__init__()
         self.linear = _lin(1, d)
@@ -141,9 +141,11 @@ class _NisqaBase(nn.Module):
         self._hp = dict(kw)
         self._engine = None
         self._engine_args = None
-        if g('cnn_model') == 'standard' and g('td') == 'lstm' and g('pool') == 'last_step_bi' \
-                and g('td_2', 'skip') in (None, 'skip') and n_heads == 1:
-            # nisqa_tts.tar architecture (NL:712-836, NL:897-943, NL:1099-1115)
+        if g('cnn_model') == 'standard' and g('td') == 'lstm' and n_heads == 1:
+            # nisqa_tts.tar (pool=last_step_bi) and the CNN-LSTM-AVG recipe (pool=avg / max): one parameter tree, the pooling's
+            # linear layer is pool.model.linear in all three (NL:712-836, NL:897-943, NL:1099-1115, NL:1185-1224)
+            from .engine import check_lstm_args
+            check_lstm_args(kw, n_heads)
             self.cnn = _Wrap(_StandardCNNParams(g('cnn_c_out_1', 16), g('cnn_c_out_2', 32), g('cnn_c_out_3', 64),
                                                 g('cnn_fc_out_h', 20)))
             self.time_dependency = _Wrap(_LSTMParams(self.cnn.model.fan_out, g('td_lstm_h', 128)))
@@ -153,7 +155,8 @@ class _NisqaBase(nn.Module):
                 or g('td_2', 'skip') not in (None, 'skip') or not g('pool_att_h', 128):
             raise NotImplementedError(
                 'nisqa_amd accelerates the CNN-SA-AP path (cnn_model=adapt, td=self_att, td_2=skip, pool=att with '
-                'pool_att_h) and the nisqa_tts path (cnn_model=standard, td=lstm, pool=last_step_bi); got '
+                'pool_att_h) and the StandardCNN + BiLSTM path of nisqa_tts and the CNN-LSTM-AVG recipe (cnn_model=standard, '
+                'td=lstm, pool=last_step_bi, avg or max); got '
                 'cnn_model={} td={} td_2={} pool={}'.format(g('cnn_model'), g('td'), g('td_2'), g('pool')))
         self.cnn = _Wrap(_AdaptCNNParams(g('cnn_c_out_1', 16), g('cnn_c_out_2', 32), g('cnn_c_out_3', 64),
                                          g('cnn_kernel_size', 3), g('cnn_pool_3', [6, 3])))
@@ -412,7 +415,7 @@ def tokens_of(ds, n_frames, sample_rate):
 def batch_policy(eng, ds, indices, bs):
     """Length-aware batches for the predict loop (ingest.LengthAware): --bs is a lower bound, batches are cut by
     segments / clips / staged bytes after sorting a window of items by length."""
-    lstm = getattr(eng, 'arch', 0) == 1
+    lstm = getattr(eng, 'arch', 0) in (1, 2, 3)           # StandardCNN + BiLSTM with last-step / average / max pooling
     # Large jobs get larger batches: an H2D copy carries ~80 us that does not scale with its size (64 MB copies run at 53 GB/s inside
     # the loop where 245 MB copies run at 56), but a job needs a few hundred batches to keep the pipeline's fill and drain small --
     # so the floor grows with the job, 1 x (<= 25 k items) ... 4 x (>= 100 k items) of MIN_TOKENS_SA.  Measured on a directory of

@@ -37,6 +37,7 @@ static int predict_batch(const void* pcm, bool pcm16, const int64_t* clip_off, c
                          int32_t total_frames, int32_t total_tok_padded, const nisqa_mel_cfg* cfg,
                          const nisqa_model_dev* model, void* ws, size_t ws_bytes, float* out, void* stream) {
     if (!cfg || !model || !ws || n_clips <= 0 || total_frames <= 0 || total_tok_padded <= 0) return NISQA_ERR_ARG;
+    if (model->arch < 0 || model->arch > 3) return NISQA_ERR_ARG;
     const ws_plan p = plan_ws(n_clips, total_frames, total_tok_padded);
     if (ws_bytes < p.total) return NISQA_ERR_WORKSPACE;
     char* w = (char*)ws;
@@ -67,9 +68,9 @@ static int predict_batch(const void* pcm, bool pcm16, const int64_t* clip_off, c
         if (rc) return rc;
     }
     NQ_STAGE(1);
-    if (model->arch == 1) {
-        // StandardCNN + BiLSTM + last-step pooling; scratch: p3 region holds [NP][12][64], feat region [NP][20],
-        // td region the [B][256] final LSTM states
+    if (model->arch >= 1) {
+        // StandardCNN + BiLSTM + last-step (arch 1), average (2) or max (3) pooling; scratch: p3 region holds [NP][12][64],
+        // feat region [NP][20], td region the [B][256] pooled LSTM states
         rc = model->cnn_mode == 1
                  ? nisqa_cnn_standard_bf16(mel, frame_off, tok_off, n_wins, cfloor, n_clips, total_tok_padded,
                                            model->seg_hop, model->cnn_w, model->cnn_wb, feat, stream)
@@ -84,7 +85,10 @@ static int predict_batch(const void* pcm, bool pcm16, const int64_t* clip_off, c
         if (rc) return rc;
         NQ_STAGE(2);
         NQ_STAGE(3);
-        rc = nisqa_lstm_laststep(feat, tok_off, n_wins, n_clips, model->td_w, td, nullptr, out, stream);
+        rc = model->arch == 1 ? nisqa_lstm_laststep(feat, tok_off, n_wins, n_clips, model->td_w, td, nullptr, out, stream)
+                              : nisqa_lstm_pool(feat, tok_off, n_wins, n_clips, model->td_w,
+                                                model->arch == 2 ? NISQA_LSTM_POOL_AVG : NISQA_LSTM_POOL_MAX, td, nullptr,
+                                                out, stream);
         if (rc) return rc;
         NQ_STAGE(4);
         NQ_STAGE(5);

@@ -110,6 +110,36 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+# pool option of a StandardCNN + BiLSTM model -> nisqa_model_dev.arch / nisqa_lstm_pool's pool_mode
+LSTM_ARCH = {'last_step_bi': 1, 'avg': 2, 'max': 3}
+LSTM_POOL_MODE = {1: _lib.LSTM_POOL_LAST_STEP_BI, 2: _lib.LSTM_POOL_AVG, 3: _lib.LSTM_POOL_MAX}
+
+
+def check_lstm_args(args, n_heads=1):
+    """The StandardCNN + BiLSTM configurations the HIP engine runs: nisqa_tts.tar (pool=last_step_bi) and the CNN-LSTM-AVG recipe
+    (config/train_nisqa_cnn_lstm_avg.yaml, pool=avg, or pool=max) -- fc 20, one bidirectional layer of 128, td_2=skip, one head.
+    Returns the nisqa_model_dev.arch (1, 2, 3); anything else raises NotImplementedError naming the option, before any GPU work.
+    Missing keys take the reference NISQA's defaults (NISQA_lib.py:36-73)."""
+    g = lambda k, d=None: args.get(k, d)
+    if g('td_2', 'skip') not in (None, 'skip'):
+        raise NotImplementedError('HIP engine: td=lstm needs td_2=skip, got td_2={}'.format(g('td_2')))
+    if n_heads != 1 or g('model', 'NISQA') != 'NISQA':
+        raise NotImplementedError('HIP engine: td=lstm is built for model=NISQA (one MOS head), got model={}'.format(
+            g('model', 'NISQA_DIM' if n_heads == 5 else 'NISQA')))
+    if not g('td_lstm_bidirectional', True):
+        raise NotImplementedError('HIP engine: a unidirectional LSTM (td_lstm_bidirectional=False) is not supported; the BiLSTM is')
+    pool = g('pool')
+    if pool not in LSTM_ARCH:
+        raise NotImplementedError('HIP engine: pool={} on the LSTM is not supported (last_step_bi, avg, max)'.format(pool))
+    if g('td_lstm_num_layers', 1) != 1:
+        raise NotImplementedError('HIP engine: td_lstm_num_layers={} is not supported (1)'.format(g('td_lstm_num_layers')))
+    if g('td_lstm_h', 128) != 128:
+        raise NotImplementedError('HIP engine: td_lstm_h={} is not supported (128)'.format(g('td_lstm_h')))
+    if g('cnn_fc_out_h', 20) != 20:
+        raise NotImplementedError('HIP engine: cnn_fc_out_h={} is not supported with td=lstm (20)'.format(g('cnn_fc_out_h')))
+    return LSTM_ARCH[pool]
+
+
 class HipNisqa(object):
     """nisqa.tar / nisqa_mos_only.tar (CNN-SA-AP) on one MI355X."""
 
@@ -122,30 +152,30 @@ class HipNisqa(object):
                  off for ~25 % of the operands; as close to float64 as 'f32' by measurement); self-attention and pooling as in 'bf16x6';
         'bf16x3' (opt-in): two bf16 terms, three products: 16 of the 24 operand mantissa bits, |dMOS| <= 5e-5, the fast mode.
         The environment variable NISQA_HIP_PRECISION overrides the default."""
+        a = args
+        lstm = a.get('cnn_model') == 'standard' and a.get('td') == 'lstm'
+        lstm_arch = check_lstm_args(a) if lstm else 0           # unsupported LSTM options raise before any GPU work
+        if a.get('td') == 'self_att' and a.get('pool') in ('avg', 'max'):
+            raise NotImplementedError('HIP engine: pool={} behind self-attention is not supported (pool=att)'.format(a.get('pool')))
         if not torch.cuda.is_available():
             raise RuntimeError('nisqa_amd: no GPU visible (torch.cuda.is_available() is False); '
                                'the HIP engine has no CPU fallback')
         self.lib = _lib.load()
         self.device = torch.device(device if device is not None else 'cuda:%d' % torch.cuda.current_device())
         self.args = args
-        a = args
         sa = a.get('cnn_model') == 'adapt' and a.get('td') == 'self_att' and a.get('pool') == 'att'
-        tts = a.get('cnn_model') == 'standard' and a.get('td') == 'lstm' and a.get('pool') == 'last_step_bi'
-        if not (sa or tts) or a.get('td_2') not in (None, 'skip') or a.get('td_sa_pos_enc'):
+        if not (sa or lstm) or a.get('td_2') not in (None, 'skip') or a.get('td_sa_pos_enc'):
             raise NotImplementedError(
                 'HIP engine covers cnn_model=adapt / td=self_att / pool=att (nisqa.tar, nisqa_mos_only.tar) and '
-                'cnn_model=standard / td=lstm / pool=last_step_bi (nisqa_tts.tar); got cnn_model={} td={} td_2={} pool={}'
-                .format(a.get('cnn_model'), a.get('td'), a.get('td_2'), a.get('pool')))
+                'cnn_model=standard / td=lstm / pool=last_step_bi, avg or max (nisqa_tts.tar, the CNN-LSTM-AVG recipe); '
+                'got cnn_model={} td={} td_2={} pool={}'.format(a.get('cnn_model'), a.get('td'), a.get('td_2'), a.get('pool')))
         if a['ms_seg_length'] != SEG_LEN or a['ms_n_mels'] != 48:
             raise NotImplementedError('HIP engine is built for 15-frame segments of 48 mel bands')
         if sa and (list(a['cnn_pool_1']) != [24, 7] or list(a['cnn_pool_2']) != [12, 5] or list(a['cnn_pool_3']) != [6, 3]
                    or a['td_sa_nhead'] != 1 or a['td_sa_d_model'] != 64 or not a.get('pool_att_h')):
             raise NotImplementedError('HIP engine is built for the nisqa.tar geometry (pools 24x7/12x5/6x3, 1 head, '
                                       'd_model 64, pool_att_h)')
-        if tts and (a.get('cnn_fc_out_h') != 20 or a.get('td_lstm_h') != 128 or a.get('td_lstm_num_layers') != 1
-                    or not a.get('td_lstm_bidirectional') or a['model'] != 'NISQA'):
-            raise NotImplementedError('HIP engine is built for the nisqa_tts.tar geometry (fc 20, BiLSTM 128 x 1 layer)')
-        self.arch = 1 if tts else 0
+        self.arch = lstm_arch           # 0 CNN-SA-AP; 1 / 2 / 3 StandardCNN + BiLSTM + last-step / average / max pooling
         # ms_sr: lb.load(path, sr=ms_sr) resamples every file to that rate first (NISQA_lib.py:2300, 2304); None in every shipped checkpoint
         self.ms_sr = int(a['ms_sr']) if a.get('ms_sr') is not None else None
         self._resample_tables = {}
@@ -158,8 +188,8 @@ class HipNisqa(object):
             raise ValueError('precision must be one of {}, got {}'.format(', '.join(PRECISIONS), self.precision))
         # the operand format of self-attention / pooling: the f16 CNN modes pair with the three-term kernels
         self.td_precision = 'bf16x6' if self.precision in ('f16x3', 'f16x4') else self.precision
-        if self.arch == 1:
-            # StandardCNN (split-bf16 or exact-fp32 MFMA) + BiLSTM + last-step pooling (fp32 VALU)
+        if self.arch >= 1:
+            # StandardCNN (split-bf16 or exact-fp32 MFMA) + BiLSTM + last-step / average / max pooling (fp32 VALU)
             self.n_layers, self.n_heads = 0, 1
             self.cnn_w = up(_w.pack_standard_cnn(state_dict))
             self.td_w = up(_w.pack_lstm_laststep(state_dict))
@@ -398,16 +428,25 @@ class HipNisqa(object):
                                                _ptr(self.cnn_w), _ptr(p3), _ptr(feat), self._stream()), 'nisqa_cnn_standard')
         return feat
 
-    def lstm(self, feat20, plan, want_seq=False):
-        """BiLSTM + PoolLastStepBi -> (out [B,1], seq [NP,256] or None)"""
+    def lstm(self, feat20, plan, want_seq=False, arch=None, want_pooled=False):
+        """BiLSTM + the pooling of ``arch`` (default: the engine's own; 1 PoolLastStepBi, 2 PoolAvg, 3 PoolMax)
+        -> (out [B,1], seq [NP,256] or None), and the pooled vector [B,256] as a third item when want_pooled"""
+        arch = self.arch if arch is None else arch
+        if arch not in LSTM_POOL_MODE:
+            raise ValueError('lstm(): arch must be 1, 2 or 3, got {}'.format(arch))
         d = plan.to(self.device)
         hfin = torch.empty((plan.n_clips, 256), dtype=torch.float32, device=self.device)
         seq = torch.zeros((plan.total_tok, 256), dtype=torch.float32, device=self.device) if want_seq else None
         out = torch.empty((plan.n_clips, 1), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.nisqa_lstm_laststep(_ptr(feat20), _ptr(d['tok_off']), _ptr(d['n_wins']), plan.n_clips,
-                                                _ptr(self.td_w), _ptr(hfin), _ptr(seq) if want_seq else None, _ptr(out),
-                                                self._stream()), 'nisqa_lstm_laststep')
-        return out, seq
+        if arch == 1:
+            _lib.check(self.lib.nisqa_lstm_laststep(_ptr(feat20), _ptr(d['tok_off']), _ptr(d['n_wins']), plan.n_clips,
+                                                    _ptr(self.td_w), _ptr(hfin), _ptr(seq) if want_seq else None, _ptr(out),
+                                                    self._stream()), 'nisqa_lstm_laststep')
+        else:
+            _lib.check(self.lib.nisqa_lstm_pool(_ptr(feat20), _ptr(d['tok_off']), _ptr(d['n_wins']), plan.n_clips, _ptr(self.td_w),
+                                                LSTM_POOL_MODE[arch], _ptr(hfin), _ptr(seq) if want_seq else None, _ptr(out),
+                                                self._stream()), 'nisqa_lstm_pool')
+        return (out, seq, hfin) if want_pooled else (out, seq)
 
     def td(self, feat, plan):
         d = plan.to(self.device)

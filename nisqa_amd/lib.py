@@ -12,6 +12,7 @@ LIB_PATH = os.environ.get('NISQA_HIP_LIB') or os.path.join(_HERE, 'libnisqa_hip.
 
 NISQA_OK, NISQA_ERR_ARG, NISQA_ERR_LAUNCH, NISQA_ERR_WORKSPACE = 0, 1, 2, 3
 ABI_VERSION = 2
+LSTM_POOL_LAST_STEP_BI, LSTM_POOL_AVG, LSTM_POOL_MAX = 0, 1, 2       # nisqa_lstm_pool's pool_mode (NISQA_LSTM_POOL_*)
 
 c_p = ctypes.c_void_p
 c_i32 = ctypes.c_int32
@@ -55,6 +56,7 @@ SYMBOLS = {
     'nisqa_cnn_standard_bf16x6': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p]),
     'nisqa_cnn_standard_f16': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_i32, c_p, c_p]),
     'nisqa_lstm_laststep': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p]),
+    'nisqa_lstm_pool': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_p, c_i32, c_p, c_p, c_p, c_p]),
     'nisqa_td_selfatt': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p]),
     'nisqa_td_selfatt_bf16': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p]),
     'nisqa_pool_att_bf16': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p]),
