@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """bench.py -- clips/sec of the NISQA predict hot path on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -19,11 +19,16 @@ drives the drop-in surface itself: nisqaModel(predict_csv).predict() over a CSV 
 `--distinct` different ones reused cyclically) -> native ingest -> H2D -> kernels -> all_gather; N is fixed, ranks
 shard it (`"scaling": "strong"`), a "step" is one bs-clip batch of a rank.  PCIe-inclusive: not the contract line.
 
-Extra objects on the JSON line (DESIGN.md "Measurement"):
+A plain run does what the headline figure needs and no more: set-up, the sustained-MFMA probe that brings the clocks to
+their loaded state (not under --no-extras), W warm-up steps, the K timed steps, --dump-outputs, one JSON line.  Beside the contract keys that line carries only what the timed
+region itself yields:
   roofline            dominant kernel (cnn_front_bf16_kernel, the whole AdaptCNN: 160.6 GFLOP per launch at bs 64):
                       algorithmic FLOPs / mean launch duration from HIP events recorded inside the timed region on the
                       launch stream, against the dense bf16 MFMA peak; `traffic` = HBM bytes per launch and `mfma_util`
-                      from the rocprofv3 PMC passes of the same build (profiles/rNN_pmc_kernels.json; null when absent).
+                      from the rocprofv3 PMC passes of the same build (profiles/rNN_pmc_kernels.json; null when absent);
+                      `peak_sustained` from the probe that ran ahead of the warm-up steps.
+
+`--full` adds everything else (DESIGN.md "Measurement"); each of these takes GPU or host time of its own:
   roofline_secondary  mel_frame_kernel against the fp32 VALU peak (FLOPs of the pruned FFT actually executed).
   kernels             per stage: mean ms, mfma_util / HBM bytes from the same PMC file.
   f32                 the same workload, same --steps / --warmup, on the exact-fp32 path (the reference's own arithmetic):
@@ -38,6 +43,7 @@ Extra objects on the JSON line (DESIGN.md "Measurement"):
                       tts_mixed (configs[3]: nisqa_tts.tar, mixed 3-30 s clips), train_step (configs[4]:
                       forward + backward + Adam at bs 32).  `--leg main|tts|train|csv|dir` runs one of them alone (profiling).
   cpu_baseline        the CPU oracle (port of the reference path) at bs = 64 on this box's host cores, rank 0, N = 1.
+A side leg named by `--leg tts|train|csv|dir` and `--workload predict_csv` are runs of their own and need no `--full`.
 """
 import argparse
 import glob
@@ -748,6 +754,9 @@ def main():
     ap.add_argument('--dump-outputs', default=None, metavar='DIR',
                     help='write what the timed path returned in its last step to DIR/<name>.npy (float32), for output-for-output '
                          'comparison of two builds on the same inputs')
+    ap.add_argument('--full', action='store_true',
+                    help='also measure everything beside the headline figure: the untimed per-stage pass (stage_ms, roofline_secondary, '
+                         'kernels), the other precisions, steady, overlap_2/3_streams, cpu_baseline and the side legs')
     a = ap.parse_args()
     if a.steps < 1:
         ap.error('--steps must be at least 1')
@@ -791,7 +800,8 @@ def main():
     # rank: the power management raises the clocks over the first ~20 ms of load after any quiet period, and a 20-step timed
     # region (16 ms) behind 5 warm-up steps would be measured on that ramp -- 4 % below the rate of every later step
     # (tools/probe_clock_ramp2.py: 0.746 against 0.718 ms per step; `steady` below is the cross-check).
-    # NISQA_BENCH_PROBE_LAST=1 restores the old order (probe after the timed region).
+    # NISQA_BENCH_PROBE_LAST=1 restores the old order (probe after the timed region).  A plain run keeps the probe: it sets the
+    # clock state the headline figure is measured at.
     sus, probe_first = None, (not a.no_extras and os.environ.get('NISQA_BENCH_PROBE_LAST') != '1')
 
     streams = [torch.cuda.Stream(device=dev) for _ in range(max(1, a.streams))]
@@ -800,13 +810,14 @@ def main():
     # Events of the TIMED region: only the two around the dominant kernel (the roofline's live duration).  An event record costs
     # stream time -- six per step read 60.5 k clips/s where the same steps without events read 62.2 k (profiles/
     # r06_stage_event_cost.txt) --, so the other stage times come from a second pass of the same K steps right behind the timed
-    # region (evs_all, untimed).
+    # region (evs_all, untimed; --full only).
     evs, evs_all = [], []                                # (created before the warm-up: no host work between it and the timed region)
     for _ in range(a.steps):
-        e = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
-        for x in e:
-            x.record(streams[len(evs) % len(streams)])   # forces handle creation; re-recorded inside the library
-        evs_all.append(e)
+        if a.full:
+            e = [torch.cuda.Event(enable_timing=True) for _ in range(6)]
+            for x in e:
+                x.record(streams[len(evs) % len(streams)])   # forces handle creation; re-recorded inside the library
+            evs_all.append(e)
         e = [None] + [torch.cuda.Event(enable_timing=True) for _ in range(2)] + [None] * 3
         for x in e[1:3]:
             x.record(streams[len(evs) % len(streams)])
@@ -849,12 +860,14 @@ def main():
             for n_, arr in dumped.items():
                 np.save(os.path.join(a.dump_outputs, n_ + '.npy'), np.ascontiguousarray(arr))
         names = ['mel', 'cnn_front', 'cnn_back', 'selfatt', 'pool']
-        for s in range(a.steps):                              # second pass, untimed: all six stage events
-            with torch.cuda.stream(streams[s % len(streams)]):
-                eng.forward_pcm(pcm, plan, SR, stage_events=evs_all[s])
-        torch.cuda.synchronize()
-        stage_ms = {n: float(np.mean([evs_all[s][i].elapsed_time(evs_all[s][i + 1]) for s in range(a.steps)]))
-                    for i, n in enumerate(names)}
+        stage_ms = {}
+        if a.full:
+            for s in range(a.steps):                          # second pass, untimed: all six stage events
+                with torch.cuda.stream(streams[s % len(streams)]):
+                    eng.forward_pcm(pcm, plan, SR, stage_events=evs_all[s])
+            torch.cuda.synchronize()
+            stage_ms = {n: float(np.mean([evs_all[s][i].elapsed_time(evs_all[s][i + 1]) for s in range(a.steps)]))
+                        for i, n in enumerate(names)}
         # the dominant kernel's launch duration: live, over the timed region itself
         stage_ms['cnn_front'] = float(np.mean([evs[s][1].elapsed_time(evs[s][2]) for s in range(a.steps)]))
         pmc, pmc_file = pmc_kernels()
@@ -887,23 +900,11 @@ def main():
         k = pmc.get(CNN_KERNEL[eng.precision]) or {}
         if k.get('GRBM_GUI_ACTIVE') and k.get('_ms', 0) >= 0.05:           # (not a clock for launches under ~50 us: tools/pmc_to_json.py)
             roof['shader_clock_mhz_profiled'] = round(k['GRBM_GUI_ACTIVE'] / 8.0 / (k['_ms'] * 1e-3) / 1e6, 0)
-        if world == 1 and not a.no_extras and eng.precision != 'f32':
+        if world == 1 and not a.no_extras and eng.precision != 'f32' and (sus or a.full):    # (a plain run reports a probe it ran anyway)
             sus = sus or mfma_sustained(dev)
             roof['peak_sustained'] = {'what': 'dense v_mfma_f32_32x32x16_bf16 on register operands, measured on this GPU just now: '
                                               'zero operands reach the data-sheet peak, random operands are power-limited',
                                       **sus, 'frac_of_sustained_random': round(roof['achieved'] / sus['random']['tflops'], 4)}
-        mel_flop = FLOP_MEL_FRAME * plan.total_frames
-        mel_ach = mel_flop / (stage_ms['mel'] * 1e-3) / 1e12
-        mtr, _ = pmc_derived(pmc.get('mel_frame_kernel'))
-        kern_tab = {}
-        tdp = eng.td_precision
-        for stage, ks in (('mel', ['mel_frame_kernel']), ('cnn', ['cnn_front_kernel', 'cnn_back_kernel'] if eng.precision == 'f32' else [CNN_KERNEL[eng.precision]]),
-                          ('selfatt', ['td_fused_bf16_kernel', 'td_proj_bf16_kernel', 'td_layer_bf16_kernel'] if tdp == 'bf16x3' else ['td16_proj_kernel', 'td16_layer_kernel<false>', 'td16_layer_kernel<true>'] if tdp == 'bf16x6' else ['td_proj_kernel', 'td_layer_kernel']),
-                          ('pool', ['pool_score_bf16_kernel', 'pool_final_kernel'] if tdp == 'bf16x3' else [] if tdp == 'bf16x6' else ['pool_score_kernel', 'pool_final_kernel'])):
-            for kn in ks:
-                if kn in pmc:
-                    tr, mu = pmc_derived(pmc[kn])
-                    kern_tab[kn] = {'stage': stage, 'hbm_bytes_per_launch': tr, 'mfma_util': mu}
         res = {
             'metric': 'clips/sec (10 s, 48 kHz)', 'value': round(clips / dt, 2), 'unit': 'clips/s',
             'n_gpus': world, 'steps': a.steps, 'warmup': a.warmup, 'ms_per_step': round(1e3 * dt / a.steps, 4),
@@ -916,24 +917,38 @@ def main():
                        'segments_per_batch': int(plan.n_wins.sum()), 'frames_per_batch': plan.total_frames,
                        'parallelism': 'clip-sharded x%d, final all_gather of MOS rows' % world,
                        'collective_backend': backend, 'world_size_seen': world},
-            'stage_ms': {k: round(v, 4) for k, v in stage_ms.items()},
-            'stage_ms_note': 'cnn_front: HIP events around the dominant kernel inside the timed region (its live launch duration); the other '
-                             'stages: a second, untimed pass of the same steps with all six stage events (an event record costs ~5 us of '
-                             'stream time; selfatt carries the attention pooling since round 6: nisqa_td_pool_bf16x6)',
-            'clock_state': ('the sustained-MFMA probe of roofline.peak_sustained (~100 ms of dense MFMA) ran before the warm-up steps: '
-                            'the timed steps start at the loaded clock state (a short region behind an idle GPU measures 4 % low; '
-                            'NISQA_BENCH_PROBE_LAST=1 restores the old order)') if probe_first else 'no load before the warm-up steps',
-            'roofline': roof,
-            'roofline_secondary': {'kernel': 'mel_frame_kernel (pruned 4 x FFT-512 + sparse mel bank + dB)', 'bound': 'valu',
-                                   'achieved': round(mel_ach, 2), 'peak': PEAK_F32, 'unit': 'TFLOP/s',
-                                   'frac': round(mel_ach / PEAK_F32, 4), 'flop_per_launch': mel_flop, 'traffic': mtr,
-                                   'avg_launch_ms': round(stage_ms['mel'], 4)},
-            'kernels': kern_tab,
         }
+        if a.full:
+            res['stage_ms'] = {k: round(v, 4) for k, v in stage_ms.items()}
+            res['stage_ms_note'] = ('cnn_front: HIP events around the dominant kernel inside the timed region (its live launch duration); the other '
+                                    'stages: a second, untimed pass of the same steps with all six stage events (an event record costs ~5 us of '
+                                    'stream time; selfatt carries the attention pooling since round 6: nisqa_td_pool_bf16x6)')
+        res['clock_state'] = ('the sustained-MFMA probe of roofline.peak_sustained (~100 ms of dense MFMA) ran before the warm-up steps: '
+                              'the timed steps start at the loaded clock state (a short region behind an idle GPU measures 4 % low; '
+                              'NISQA_BENCH_PROBE_LAST=1 restores the old order)') if probe_first else 'no load before the warm-up steps'
+        res['roofline'] = roof
+        if a.full:
+            mel_flop = FLOP_MEL_FRAME * plan.total_frames
+            mel_ach = mel_flop / (stage_ms['mel'] * 1e-3) / 1e12
+            mtr, _ = pmc_derived(pmc.get('mel_frame_kernel'))
+            kern_tab = {}
+            tdp = eng.td_precision
+            for stage, ks in (('mel', ['mel_frame_kernel']), ('cnn', ['cnn_front_kernel', 'cnn_back_kernel'] if eng.precision == 'f32' else [CNN_KERNEL[eng.precision]]),
+                              ('selfatt', ['td_fused_bf16_kernel', 'td_proj_bf16_kernel', 'td_layer_bf16_kernel'] if tdp == 'bf16x3' else ['td16_proj_kernel', 'td16_layer_kernel<false>', 'td16_layer_kernel<true>'] if tdp == 'bf16x6' else ['td_proj_kernel', 'td_layer_kernel']),
+                              ('pool', ['pool_score_bf16_kernel', 'pool_final_kernel'] if tdp == 'bf16x3' else [] if tdp == 'bf16x6' else ['pool_score_kernel', 'pool_final_kernel'])):
+                for kn in ks:
+                    if kn in pmc:
+                        tr, mu = pmc_derived(pmc[kn])
+                        kern_tab[kn] = {'stage': stage, 'hbm_bytes_per_launch': tr, 'mfma_util': mu}
+            res['roofline_secondary'] = {'kernel': 'mel_frame_kernel (pruned 4 x FFT-512 + sparse mel bank + dB)', 'bound': 'valu',
+                                         'achieved': round(mel_ach, 2), 'peak': PEAK_F32, 'unit': 'TFLOP/s',
+                                         'frac': round(mel_ach / PEAK_F32, 4), 'flop_per_launch': mel_flop, 'traffic': mtr,
+                                         'avg_launch_ms': round(stage_ms['mel'], 4)}
+            res['kernels'] = kern_tab
         if dumped is not None:
             res['dump_outputs'] = {'dir': a.dump_outputs, 'arrays': {n_: list(v.shape) for n_, v in dumped.items()},
                                    'what': 'the last timed step: [clips, heads] rows (mos, noi, dis, col, loud) of every rank'}
-        if world == 1 and not a.no_extras:
+        if a.full and world == 1 and not a.no_extras:
             # the other precision path on the same workload: same --steps / --warmup, same barriers, right after the
             # primary region.  For the default run this is the exact-fp32 path -- the reference's own arithmetic.
             # (and 'bf16x6': every GEMM at fp32 operand precision on the bf16 matrix pipe -- three exact bf16 terms per operand, six
@@ -989,7 +1004,7 @@ def main():
             res['steady'] = {'value': round(BATCH * n3 / dt3, 2), 'unit': 'clips/s', 'steps': n3, 'warmup': 50,
                              'ms_per_step': round(1e3 * dt3 / n3, 4), 'stage_ms': {k: round(v, 4) for k, v in st3.items()},
                              'roofline_frac': roofline_of(eng.precision, st3['cnn_front'])['frac']}
-        if world == 1 and len(streams) == 1 and not a.no_extras:
+        if a.full and world == 1 and len(streams) == 1 and not a.no_extras:
             # the same steps alternated over 2 streams (what the predict loop does) and over 3: launches overlap, one batch's
             # VALU-bound mel kernel runs next to another's MFMA-bound CNN kernel.  No events inside; >= 200 steps behind 4 per stream
             # (a 20-step region on freshly created streams measures their start-up)
@@ -1006,9 +1021,9 @@ def main():
                         eng.forward_pcm(pcm, plan, SR)
                 torch.cuda.synchronize()
                 res['overlap_%d_streams' % ns] = {'value': round(BATCH * n_ov / (time.perf_counter() - t1), 2), 'unit': 'clips/s', 'steps': n_ov}
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             res['cpu_baseline'] = cpu_baseline(margs, sd)
-        if world == 1 and a.leg == 'all' and not a.no_side and not a.no_extras:
+        if a.full and world == 1 and a.leg == 'all' and not a.no_side and not a.no_extras:
             # BASELINE.json configs[2], [3], [4]: bounded side legs (a failure in one must not cost the contract line)
             res['side'] = {}
             for name, fn in (('tts_mixed', lambda: side_tts(dev, 3, not a.no_cpu_baseline, pmc)),

@@ -65,8 +65,8 @@ def test_bench_predict_csv_gpus2_plain_python_one_json_line():
 def test_bench_line_carries_the_contract_fields():
     """One JSON line with the driver's contract keys, the roofline of the dominant kernel measured inside the timed region (only the
     two events around the CNN kernel are recorded there: an event record costs stream time, profiles/r06_stage_event_cost.txt) and
-    the other stage times from the untimed second pass."""
-    r = _run(['--steps', '4', '--warmup', '2', '--no-cpu-baseline', '--no-side'])
+    the other stage times from the untimed second pass (--full)."""
+    r = _run(['--steps', '4', '--warmup', '2', '--no-cpu-baseline', '--no-side', '--full'])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
     assert len(lines) == 1, r.stdout[-2000:]
@@ -81,6 +81,29 @@ def test_bench_line_carries_the_contract_fields():
     assert 0.5 * d['ms_per_step'] < d['stage_ms']['cnn_front'] < d['ms_per_step']          # the dominant kernel, and it fits the step
     assert set(d['stage_ms']) == {'mel', 'cnn_front', 'cnn_back', 'selfatt', 'pool'}
     assert d['overlap_2_streams']['steps'] >= 200 and d['steady']['steps'] >= 400
+
+
+@pytest.mark.gpu
+def test_plain_bench_line_is_the_headline_alone():
+    """A plain run (no --full) times the steps and prints the contract line with the roofline its timed region yields; nothing that
+    takes a run of its own (the untimed stage pass, the other precisions, steady, overlap, cpu_baseline, side legs) is on it."""
+    r = _run(['--steps', '4', '--warmup', '2'])
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+    assert len(lines) == 1, r.stdout[-2000:]
+    d = json.loads(lines[0])
+    for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'scaling', 'vs_baseline', 'dtype',
+              'data', 'config', 'roofline'):
+        assert k in d, k
+    assert d['metric'] == 'clips/sec (10 s, 48 kHz)' and d['unit'] == 'clips/s' and d['higher_is_better'] is True
+    assert d['n_gpus'] == 1 and d['steps'] == 4 and d['warmup'] == 2 and d['dtype'].startswith('bf16x6')
+    assert abs(d['value'] * d['ms_per_step'] / (64 * 1e3) - 1) < 1e-3          # value and ms_per_step describe the same K steps
+    roof = d['roofline']
+    assert roof['bound'] == 'mfma' and 0.02 < roof['frac'] < 0.2 and 0.5 * d['ms_per_step'] < roof['avg_launch_ms'] < d['ms_per_step']
+    assert 'peak_sustained' in roof                                             # the clock-conditioning probe ran ahead of the warm-up
+    for k in ('stage_ms', 'roofline_secondary', 'kernels', 'f32', 'value_f32', 'steady', 'overlap_2_streams', 'overlap_3_streams',
+              'cpu_baseline', 'side'):
+        assert k not in d, k
 
 
 @pytest.mark.gpu

@@ -16,22 +16,22 @@ for WL in "--leg main" "--leg main --precision f16x4" "--leg main --precision bf
   w=$((w+1)); i=0
   for set in "${SETS[@]}"; do
     i=$((i+1)); d=/tmp/pmcp_${w}_$i; rm -rf $d
-    (cd /tmp && timeout 300 rocprofv3 --pmc $set --output-format csv -d $d -o pmc -- python $OLDPWD/bench.py --no-cpu-baseline --no-extras --steps 5 --warmup 3 $WL > $d.log 2>&1)
+    (cd /tmp && timeout 300 rocprofv3 --pmc $set --output-format csv -d $d -o pmc -- python $OLDPWD/bench.py --full --no-cpu-baseline --no-extras --steps 5 --warmup 3 $WL > $d.log 2>&1)
     case $w in 5|6) dirs="$dirs tts:=$d";; 7) dirs="$dirs train:=$d";; *) dirs="$dirs $d";; esac
   done
 done
 python tools/pmc_to_json.py $O/${R}_pmc_kernels.json $dirs > $O/${R}_pmc_kernels.txt 2>&1
 cp $O/${R}_pmc_kernels.json profiles/${R}_pmc_kernels.json      # so that the bench lines below carry traffic / mfma_util
 # the contract line (default precision bf16x6) in its two forms, then every other precision as the primary of its own run
-python bench.py > $O/${R}_bench_bf16x6.json 2>/dev/null
-python bench.py --steps 20 --warmup 5 > $O/${R}_bench_bf16x6_driver_form.json 2>/dev/null
+python bench.py --full > $O/${R}_bench_bf16x6.json 2>/dev/null
+python bench.py --full --steps 20 --warmup 5 > $O/${R}_bench_bf16x6_driver_form.json 2>/dev/null
 for P in f16x4 f16x3 bf16x3 f32; do
-  python bench.py --precision $P --no-cpu-baseline --no-side --no-extras > $O/${R}_bench_$P.json 2>/dev/null
+  python bench.py --full --precision $P --no-cpu-baseline --no-side --no-extras > $O/${R}_bench_$P.json 2>/dev/null
 done
-python bench.py --streams 2 --no-cpu-baseline --no-extras > $O/${R}_bench_bf16x6_2streams.json 2>/dev/null
+python bench.py --full --streams 2 --no-cpu-baseline --no-extras > $O/${R}_bench_bf16x6_2streams.json 2>/dev/null
 for P in bf16x6 f16x4 f16x3 bf16x3 f32; do
   rm -rf /tmp/ks_$P
-  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$P -o ks -- python $OLDPWD/bench.py --no-cpu-baseline --no-extras --precision $P > /tmp/ks_$P.log 2>&1)
+  (cd /tmp && rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ks_$P -o ks -- python $OLDPWD/bench.py --full --no-cpu-baseline --no-extras --precision $P > /tmp/ks_$P.log 2>&1)
   cp /tmp/ks_$P/ks_kernel_stats.csv $O/${R}_bench_${P}_kernel_stats.csv
 done
 for P in bf16x6 f16x4; do

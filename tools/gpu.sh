@@ -5,7 +5,8 @@
 #   tests[:K]         pytest -m gpu (optionally -k K), -x
 #   parity[:K]        tests/test_gpu_parity.py only
 #   train[:K]         tests/test_gpu_train.py only
-#   bench[:ARGS]      python bench.py ARGS (commas in ARGS become spaces), JSON line -> bench_<n>.json, one-line summary printed
+#   bench[:ARGS]      python bench.py ARGS (commas in ARGS become spaces; --full for stage_ms and the rest of the line), JSON line ->
+#                     bench_<n>.json, one-line summary printed
 #   ab:NAME[,NAME]    A/B of ab_libs/NAME.so builds against the in-tree library (tools/gpu_ab.sh)
 #   exe:PATH[,ARGS]   run a microbenchmark binary (ab_libs/...), stdout -> exe_<n>.txt
 #   py:SCRIPT[,ARGS]  python SCRIPT ARGS, stdout -> py_<n>.txt
