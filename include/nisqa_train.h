@@ -69,6 +69,20 @@ int nisqa_conv1_bn_act_pool_bwd(const float* mel_tm, const int32_t* frame_off, c
                                 const double* mom54, const float* gamma, const float* beta, const float* mean_rstd,
                                 const float* drop, const float* dy, const int32_t* arg, double* acc176, float* dgamma,
                                 float* dbeta, float* dw, void* stream);
+/* The same for StandardCNN's layer 1 (conv1 -> train-mode BatchNorm -> ReLU -> pool_first = MaxPool2d(2, stride 2, padding (0, 1)),
+ * 48 x 15 -> 24 x 8 -> per-channel dropout scale; NISQA_lib.py:712-836): arguments and moments as above, y / dy / arg are
+ * [S][192][16]; pooled pixel (oy, ox) reads bands 2 oy, 2 oy + 1 and frames 2 ox - 1, 2 ox (the padding column never wins),
+ * ties go to the first maximum in (band, frame) order as in PyTorch. */
+int nisqa_conv1_bn_act_pool_std_fwd(const float* mel_tm, const int32_t* frame_off, const int32_t* seg_off, const float* clip_floor,
+                                    int32_t n_clips, int32_t n_segments, int32_t seg_hop, const float* w, const float* bias,
+                                    const double* mom54, const float* gamma, const float* beta, float* running_mean,
+                                    float* running_var, double* sums32, float* mean_rstd, const float* drop, float* y,
+                                    int32_t* arg, void* stream);
+int nisqa_conv1_bn_act_pool_std_bwd(const float* mel_tm, const int32_t* frame_off, const int32_t* seg_off, const float* clip_floor,
+                                    int32_t n_clips, int32_t n_segments, int32_t seg_hop, const float* w, const float* bias,
+                                    const double* mom54, const float* gamma, const float* beta, const float* mean_rstd,
+                                    const float* drop, const float* dy, const int32_t* arg, double* acc176, float* dgamma,
+                                    float* dbeta, float* dw, void* stream);
 /* 3x3 patches, padding (1, pad_w): x[S][H*W][C] -> col[S*H*Wo][9*C], Wo = W + 2*pad_w - 2, k = (dy*3+dx)*C + c
  * (C % 4 == 0, 16-byte aligned buffers) */
 int nisqa_im2col3x3(const float* x, int32_t n_segments, int32_t h, int32_t w, int32_t c, int32_t pad_w, float* col,
@@ -245,6 +259,26 @@ int nisqa_dropout_mask(uint64_t seed, uint64_t offset, float p, int64_t n, float
 /* dst[table[e][1] + t] = (float)src[table[e][0] + t], t < table[e][2], for e < n_entries (table: int32 [n_entries][3]):
  * the float64 column sums of a step that ARE gradients (biases, LayerNorm parameters) move to the flat gradient buffer */
 int nisqa_cast_scatter(const double* src, const int32_t* table, int32_t n_entries, float* dst, void* stream);
+
+/* BiLSTM of the StandardCNN + BiLSTM models in training (csrc/train_lstm.hip; nn.LSTM(20, 128, bidirectional) over each clip's
+ * valid segments, NISQA_lib.py:897-943, then the reduction of PoolLastStepBi / PoolAvg / PoolMax, NL:1099-1115, 1185-1224).
+ * One workgroup per (clip, direction), one launch each; clip b owns tokens seg_off[b] .. seg_off[b+1]-1 (seg_off [n_clips+1]).
+ * Weights in PyTorch's gate order (i, f, g, o), both directions back to back: w_ih [2][512][20], w_hh [2][512][128],
+ * b_ih, b_hh [2][512].  pool_mode: NISQA_LSTM_POOL_* (nisqa_hip.h).
+ *   nisqa_lstm_train_fwd  x20 [tokens][20] -> save [tokens][2][640] (activated gates i, f, g, o and the cell state c of each
+ *                         step), hprev [tokens][2][128] (the hidden state each step read; 0 at a direction's first step),
+ *                         pooled [n_clips][256] (direction-major: the last step / the float64 mean / the maximum), argmax
+ *                         [n_clips][256] (pool_mode MAX only, else may be NULL: the step -- in the direction's own order -- of
+ *                         each maximum);
+ *   nisqa_lstm_train_bptt dpooled [n_clips][256] = d loss / d pooled -> dgates [tokens][2][512] = d loss / d (gate
+ *                         pre-activations); dbias (may be NULL; float64 [2][512], zeroed by the caller) += the sum of dgates
+ *                         over the tokens (the gradient of b_ih and of b_hh alike).  Parameter and input gradients then
+ *                         follow from nisqa_gemm_f32_one: dW_ih = dgates^T x20, dW_hh = dgates^T hprev, dx20 = dgates w_ih. */
+int nisqa_lstm_train_fwd(const float* x20, const int32_t* seg_off, int32_t n_clips, const float* w_ih, const float* w_hh,
+                         const float* b_ih, const float* b_hh, int32_t pool_mode, float* save, float* hprev, float* pooled,
+                         int32_t* argmax, void* stream);
+int nisqa_lstm_train_bptt(const int32_t* seg_off, int32_t n_clips, const float* w_hh, const float* save, int32_t pool_mode,
+                          const float* dpooled, const int32_t* argmax, float* dgates, double* dbias, void* stream);
 
 /* torch.optim.Adam (betas 0.9 / 0.999, eps 1e-8, no weight decay), step counter t >= 1, on flat buffers */
 int nisqa_adam_step(float* param, const float* grad, float* m, float* v, int64_t n, float lr, int32_t t, void* stream);

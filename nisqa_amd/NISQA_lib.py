@@ -9,8 +9,9 @@ argument meaning and error behaviour, with the arithmetic moved to the HIP engin
   NISQA_DE              (NL:272-424)               the same for the double-ended model (inference only)
 
 Evaluation statistics (eval_results and helpers, NL:1469-1852) are re-exported from nisqa_amd/evaluation.py.
-Out of scope here (raise NotImplementedError): training (NISQA_DE training included),
-alternative blocks no shipped checkpoint uses.
+Training runs through nisqa_amd/trainloop.py (CNN-SA-AP: nisqa_amd/train.py; StandardCNN + BiLSTM with pool last_step_bi / avg /
+max: nisqa_amd/train_lstm.py).  Out of scope here (raise NotImplementedError): NISQA_DE training, alternative blocks no shipped
+checkpoint uses.
 """
 import os
 import sys

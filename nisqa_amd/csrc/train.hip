@@ -933,7 +933,16 @@ __global__ void conv1_sums_kernel(const double* __restrict__ mom, const float* _
     sums[16 + c] = wpw + 2.0 * b * wp + n * b * b;
 }
 
-// one thread = four channels of one pooled value: y[s][oy * 7 + ox][c], arg = pixel index (band * 15 + frame) of the maximum
+// pooling window of layer 1 along one axis: AdaptCNN's adaptive windows (PADW = 0), or StandardCNN's pool_first along the frames
+// (PADW = 1: MaxPool2d(2, stride 2, padding (0, 1)) -- out column j reads input columns 2j-1 and 2j, the padding never wins)
+template <int PADW>
+NQ_DEV int c1_lo(int o, int n_in, int n_out) { return PADW ? (2 * o - 1 > 0 ? 2 * o - 1 : 0) : win_lo(o, n_in, n_out); }
+template <int PADW>
+NQ_DEV int c1_hi(int o, int n_in, int n_out) { return PADW ? (2 * o + 1 < n_in ? 2 * o + 1 : n_in) : win_hi(o, n_in, n_out); }
+
+// one thread = four channels of one pooled value: y[s][oy * WO + ox][c], arg = pixel index (band * 15 + frame) of the maximum;
+// <24, 7, 0> AdaptCNN (cnn_pool_1 = [24, 7]), <24, 8, 1> StandardCNN
+template <int HO, int WO, int PADW>
 __global__ __launch_bounds__(256) void conv1_bn_act_pool_fwd_kernel(
     const float* __restrict__ mel_tm, const int32_t* __restrict__ frame_off, const int32_t* __restrict__ seg_off,
     const float* __restrict__ clip_floor, int n_clips, int seg_hop, const float* __restrict__ w, const float* __restrict__ bias,
@@ -953,13 +962,13 @@ __global__ __launch_bounds__(256) void conv1_bn_act_pool_fwd_kernel(
         ws[176 + c] = beta[c] - mean_rstd[c] * g;
     }
     __syncthreads();
-    for (int i = tid; i < 168 * 4; i += 256) {
+    for (int i = tid; i < HO * WO * 4; i += 256) {
         const int o = i >> 2, ch = 4 * (i & 3);
-        const int oy = o / 7, ox = o % 7;
+        const int oy = o / WO, ox = o % WO;
         f32x4 best = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
         i32x4 bp = {0, 0, 0, 0};
-        for (int m = win_lo(oy, 48, 24); m < win_hi(oy, 48, 24); ++m)
-            for (int j = win_lo(ox, 15, 7); j < win_hi(ox, 15, 7); ++j) {
+        for (int m = win_lo(oy, 48, HO); m < win_hi(oy, 48, HO); ++m)
+            for (int j = c1_lo<PADW>(ox, 15, WO); j < c1_hi<PADW>(ox, 15, WO); ++j) {
                 float x[9];
 #pragma unroll
                 for (int t = 0; t < 9; ++t) x[t] = patch[j + t % 3][m + t / 3];
@@ -973,12 +982,14 @@ __global__ __launch_bounds__(256) void conv1_bn_act_pool_fwd_kernel(
                 }
             }
         if (drop) best *= *(const f32x4*)(drop + (int64_t)s * 16 + ch);
-        *(f32x4*)(y + ((int64_t)s * 168 + o) * 16 + ch) = best;
-        *(i32x4*)(arg + ((int64_t)s * 168 + o) * 16 + ch) = bp;
+        *(f32x4*)(y + ((int64_t)s * (HO * WO) + o) * 16 + ch) = best;
+        *(i32x4*)(arg + ((int64_t)s * (HO * WO) + o) * 16 + ch) = bp;
     }
 }
 
-// acc[c][0] = sum dyb, [1] = sum dyb * z, [2 + t] = sum dyb * patch[t] over all pooled values whose ReLU is open
+// acc[c][0] = sum dyb, [1] = sum dyb * z, [2 + t] = sum dyb * patch[t] over all pooled values whose ReLU is open (NPIX pooled pixels
+// per segment: 168 AdaptCNN, 192 StandardCNN)
+template <int NPIX>
 __global__ __launch_bounds__(256) void conv1_bn_act_pool_bwd_kernel(
     const float* __restrict__ mel_tm, const int32_t* __restrict__ frame_off, const int32_t* __restrict__ seg_off,
     const float* __restrict__ clip_floor, int n_clips, int n_segments, int seg_hop, const float* __restrict__ w,
@@ -1013,8 +1024,8 @@ __global__ __launch_bounds__(256) void conv1_bn_act_pool_bwd_kernel(
         C1_WSYNC();
         f32x4 dr = {1.f, 1.f, 1.f, 1.f};
         if (drop) dr = *(const f32x4*)(drop + (int64_t)s * 16 + ch);
-        for (int i = lane; i < 168 * 4; i += 64) {
-            const int64_t at = ((int64_t)s * 168 + (i >> 2)) * 16 + ch;
+        for (int i = lane; i < NPIX * 4; i += 64) {
+            const int64_t at = ((int64_t)s * NPIX + (i >> 2)) * 16 + ch;
             const f32x4 g = *(const f32x4*)(dy + at) * dr;
             const i32x4 ap = *(const i32x4*)(arg + at);
 #pragma unroll
@@ -1090,8 +1101,8 @@ extern "C" int nisqa_conv1_bn_act_pool_fwd(const float* mel_tm, const int32_t* f
     NQ_LAUNCH_BEGIN();
     hipLaunchKernelGGL(conv1_sums_kernel, dim3(1), dim3(64), 0, st, mom54, w, bias, rows, sums32);
     hipLaunchKernelGGL(bn_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)sums32, 16, rows, running_mean, running_var, mean_rstd);
-    hipLaunchKernelGGL(conv1_bn_act_pool_fwd_kernel, dim3(n_segments), dim3(256), 0, st, mel_tm, frame_off, seg_off, clip_floor, n_clips,
-                       seg_hop, w, bias, gamma, beta, (const float*)mean_rstd, drop, y, arg);
+    hipLaunchKernelGGL((conv1_bn_act_pool_fwd_kernel<24, 7, 0>), dim3(n_segments), dim3(256), 0, st, mel_tm, frame_off, seg_off, clip_floor,
+                       n_clips, seg_hop, w, bias, gamma, beta, (const float*)mean_rstd, drop, y, arg);
     return NQ_LAUNCH_STATUS();
 }
 
@@ -1105,8 +1116,46 @@ extern "C" int nisqa_conv1_bn_act_pool_bwd(const float* mel_tm, const int32_t* f
         return NISQA_ERR_ARG;
     hipStream_t st = (hipStream_t)stream;
     NQ_LAUNCH_BEGIN();
-    hipLaunchKernelGGL(conv1_bn_act_pool_bwd_kernel, dim3((n_segments + 3) / 4 < 512 ? (n_segments + 3) / 4 : 512), dim3(256), 0, st, mel_tm, frame_off,
-                       seg_off, clip_floor, n_clips, n_segments, seg_hop, w, bias, gamma, beta, mean_rstd, drop, dy, arg, acc176);
+    hipLaunchKernelGGL((conv1_bn_act_pool_bwd_kernel<168>), dim3((n_segments + 3) / 4 < 512 ? (n_segments + 3) / 4 : 512), dim3(256), 0, st, mel_tm,
+                       frame_off, seg_off, clip_floor, n_clips, n_segments, seg_hop, w, bias, gamma, beta, mean_rstd, drop, dy, arg, acc176);
+    hipLaunchKernelGGL(conv1_bwd_finalize_kernel, dim3(1), dim3(144), 0, st, (const double*)acc176, mom54, w, bias, gamma, mean_rstd,
+                       (int64_t)n_segments * 720, dgamma, dbeta, dw);
+    return NQ_LAUNCH_STATUS();
+}
+
+// StandardCNN's layer 1 (NISQA_lib.py:712-836: conv1 -> bn1 -> ReLU -> pool_first = MaxPool2d(2, 2, padding (0, 1)), 48 x 15 ->
+// 24 x 8): the moments, the statistics and the weight gradient of the AdaptCNN form; only the pooling windows differ
+extern "C" int nisqa_conv1_bn_act_pool_std_fwd(const float* mel_tm, const int32_t* frame_off, const int32_t* seg_off,
+                                               const float* clip_floor, int32_t n_clips, int32_t n_segments, int32_t seg_hop,
+                                               const float* w, const float* bias, const double* mom54, const float* gamma,
+                                               const float* beta, float* running_mean, float* running_var, double* sums32,
+                                               float* mean_rstd, const float* drop, float* y, int32_t* arg, void* stream) {
+    if (!mel_tm || !frame_off || !seg_off || !clip_floor || !w || !bias || !mom54 || !gamma || !beta || !running_mean || !running_var ||
+        !sums32 || !mean_rstd || !y || !arg || n_clips <= 0 || n_segments <= 0 || seg_hop <= 0)
+        return NISQA_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    const int64_t rows = (int64_t)n_segments * 720;
+    NQ_LAUNCH_BEGIN();
+    hipLaunchKernelGGL(conv1_sums_kernel, dim3(1), dim3(64), 0, st, mom54, w, bias, rows, sums32);
+    hipLaunchKernelGGL(bn_finalize_kernel, dim3(1), dim3(256), 0, st, (const double*)sums32, 16, rows, running_mean, running_var, mean_rstd);
+    hipLaunchKernelGGL((conv1_bn_act_pool_fwd_kernel<24, 8, 1>), dim3(n_segments), dim3(256), 0, st, mel_tm, frame_off, seg_off, clip_floor,
+                       n_clips, seg_hop, w, bias, gamma, beta, (const float*)mean_rstd, drop, y, arg);
+    return NQ_LAUNCH_STATUS();
+}
+
+extern "C" int nisqa_conv1_bn_act_pool_std_bwd(const float* mel_tm, const int32_t* frame_off, const int32_t* seg_off,
+                                               const float* clip_floor, int32_t n_clips, int32_t n_segments, int32_t seg_hop,
+                                               const float* w, const float* bias, const double* mom54, const float* gamma,
+                                               const float* beta, const float* mean_rstd, const float* drop, const float* dy,
+                                               const int32_t* arg, double* acc176, float* dgamma, float* dbeta, float* dw,
+                                               void* stream) {
+    if (!mel_tm || !frame_off || !seg_off || !clip_floor || !w || !bias || !mom54 || !gamma || !beta || !mean_rstd || !dy || !arg ||
+        !acc176 || !dgamma || !dbeta || !dw || n_clips <= 0 || n_segments <= 0 || seg_hop <= 0)
+        return NISQA_ERR_ARG;
+    hipStream_t st = (hipStream_t)stream;
+    NQ_LAUNCH_BEGIN();
+    hipLaunchKernelGGL((conv1_bn_act_pool_bwd_kernel<192>), dim3((n_segments + 3) / 4 < 512 ? (n_segments + 3) / 4 : 512), dim3(256), 0, st, mel_tm,
+                       frame_off, seg_off, clip_floor, n_clips, n_segments, seg_hop, w, bias, gamma, beta, mean_rstd, drop, dy, arg, acc176);
     hipLaunchKernelGGL(conv1_bwd_finalize_kernel, dim3(1), dim3(144), 0, st, (const double*)acc176, mom54, w, bias, gamma, mean_rstd,
                        (int64_t)n_segments * 720, dgamma, dbeta, dw);
     return NQ_LAUNCH_STATUS();

@@ -104,6 +104,10 @@ TRAIN_SYMBOLS = {
     'nisqa_conv1_bn_act_pool_fwd': (ctypes.c_int, [c_p] * 4 + [c_i32] * 3 + [c_p] * 13),
     'nisqa_conv1_bn_act_pool_bwd': (ctypes.c_int, [c_p] * 4 + [c_i32] * 3 + [c_p] * 14),
     'nisqa_im2col_mel': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p]),
+    'nisqa_conv1_bn_act_pool_std_fwd': (ctypes.c_int, [c_p] * 4 + [c_i32] * 3 + [c_p] * 13),
+    'nisqa_conv1_bn_act_pool_std_bwd': (ctypes.c_int, [c_p] * 4 + [c_i32] * 3 + [c_p] * 14),
+    'nisqa_lstm_train_fwd': (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p]),
+    'nisqa_lstm_train_bptt': (ctypes.c_int, [c_p, c_i32, c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_p]),
     'nisqa_im2col3x3': (ctypes.c_int, [c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p]),
     'nisqa_conv3x3_gemm': (ctypes.c_int, [c_i32, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_i32, c_p]),
     'nisqa_conv3x3_fwd_stats': (ctypes.c_int, [c_i32, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p]),

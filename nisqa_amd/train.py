@@ -77,7 +77,184 @@ def step_tables(L):
     return parts, tiles
 
 
-class HipTrainer(object):
+class _FlatTrainer(object):
+    """What the HIP training steps share: every parameter in ONE flat device buffer in kernel layout (``_to_kernel`` /
+    ``_from_kernel`` of the subclass convert to and from the reference's shapes), its gradient buffer, the BatchNorm buffers of
+    cnn.model.bn1..6, the float64 column sums that end as gradients, the dropout masks, the mel front end of the step
+    (``self.eng``), the data-parallel exchange and the Adam update (``_finish_step``).  Subclasses set ``self.eng``,
+    ``self.lib``, ``self.device``, ``self.args``, ``self.lr``, ``self.t`` and implement ``_step``."""
+
+    def _param_order(self, sd):
+        """Trainable keys in flat-buffer order (default: the state_dict's own order)."""
+        return [k for k in sd if k.split('.')[-1] not in ('running_mean', 'running_var', 'num_batches_tracked')]
+
+    def _layout(self, sd):
+        keys = self._param_order(sd)
+        self.keys, self.off, self.kshape = keys, {}, {}
+        n = 0
+        for k in keys:
+            shape = tuple(sd[k].shape)
+            if k.startswith('cnn.model.conv') and k.endswith('.weight'):
+                shape = (shape[0], 9 * shape[1])
+            self.off[k], self.kshape[k] = n, shape
+            n += int(np.prod(shape))
+            n = (n + 3) // 4 * 4
+        self.flat = torch.zeros(n, dtype=torch.float32, device=self.device)
+        self.gflat = torch.zeros_like(self.flat)
+        self.P = {k: self.flat[self.off[k]:self.off[k] + int(np.prod(self.kshape[k]))].view(self.kshape[k]) for k in keys}
+        self.G = {k: self.gflat[self.off[k]:self.off[k] + int(np.prod(self.kshape[k]))].view(self.kshape[k]) for k in keys}
+
+    def load_state_dict(self, sd):
+        self._ref_shape = {k: tuple(sd[k].shape) for k in sd}
+        for k in self.keys:
+            v = torch.as_tensor(np.asarray(sd[k]) if not torch.is_tensor(sd[k]) else sd[k]).float()
+            self.P[k].copy_(self._to_kernel(k, v).contiguous().to(self.device))
+        self.bn = {}
+        for i in range(1, 7):
+            p = 'cnn.model.bn%d.' % i
+            self.bn[i] = {'mean': torch.as_tensor(np.asarray(sd[p + 'running_mean'])).float().to(self.device).clone(),
+                          'var': torch.as_tensor(np.asarray(sd[p + 'running_var'])).float().to(self.device).clone(),
+                          'n': int(np.asarray(sd[p + 'num_batches_tracked'])) if p + 'num_batches_tracked' in sd else 0}
+
+    def state_dict(self):
+        """Reference keys and shapes (CPU tensors): loads into the reference's model and into HipNisqa."""
+        out = {}
+        for k, shape in self._ref_shape.items():
+            last = k.split('.')[-1]
+            if last in ('running_mean', 'running_var', 'num_batches_tracked'):
+                i = int(k.split('.')[2][2:])
+                out[k] = (torch.tensor(self.bn[i]['n']) if last == 'num_batches_tracked'
+                          else self.bn[i]['mean' if last == 'running_mean' else 'var'].cpu().clone())
+            else:
+                out[k] = self._from_kernel(k, self.P[k].cpu(), shape).contiguous().clone()
+        return out
+
+    def grads(self):
+        """Gradients of the last step in the reference's shapes (CPU tensors)."""
+        return {k: self._from_kernel(k, self.G[k].cpu(), self._ref_shape[k]).contiguous().clone() for k in self.keys}
+
+    def _st(self):
+        return torch.cuda.current_stream(self.device).cuda_stream
+
+    def _ck(self, rc, what):
+        _lib.check(rc, what)
+
+    def _new(self, *shape, dtype=torch.float32):
+        return torch.empty(shape, dtype=dtype, device=self.device)
+
+    def _gemm(self, A, B, C, M, N, K, lda, ldb, ldc, ta=0, tb=0, ksplit=1, ao=0, bo=0, co=0, bias=None, relu=0):
+        self._ck(self.lib.nisqa_gemm_f32_one(_ptr(A, ao), _ptr(B, bo), _ptr(C, co), M, N, K, lda, ldb, ldc, ta, tb, ksplit,
+                                             1.0, _ptr(bias) if bias is not None else None, relu, self._st()),
+                 'nisqa_gemm_f32_one')
+
+    def _coldot(self, a, b, rows, c):
+        s = self._sums[self._sum_i]
+        self._sum_i += 1
+        self._ck(self.lib.nisqa_col_dot(_ptr(a), _ptr(b), rows, c, s.data_ptr(), self._st()), 'nisqa_col_dot')
+        return s
+
+    def _defer_cast(self, s, lo, n, dst):
+        """float64 sums s[lo:lo+n] -> float32 gradient view dst, executed by one nisqa_cast_scatter at the end of backward"""
+        self._casts.append(((s.data_ptr() - self._sums.data_ptr()) // 8 + lo, (dst.data_ptr() - self.gflat.data_ptr()) // 4, n))
+
+    def _flush_casts(self):
+        if not self._casts:
+            return
+        key = tuple(self._casts)
+        if key != self._cast_key:
+            self._cast_key = key
+            self._cast_table = torch.tensor(self._casts, dtype=torch.int32, device=self.device)
+        self._ck(self.lib.nisqa_cast_scatter(self._sums.data_ptr(), self._cast_table.data_ptr(), len(self._casts),
+                                             _ptr(self.gflat), self._st()), 'nisqa_cast_scatter')
+
+    def _draw_masks(self):
+        self._mask_buf = self._new(self._mask_total)
+        for lo, hi, p in ((0, self._mask_split, self.p_cnn), (self._mask_split, self._mask_total, self.p_td)):
+            if hi > lo and p > 0:
+                self._ck(self.lib.nisqa_dropout_mask(self._rng_seed, self._rng_off, p, hi - lo, _ptr(self._mask_buf, lo),
+                                                     self._st()), 'nisqa_dropout_mask')
+                self._rng_off += (hi - lo + 3) // 4
+
+    def _mask(self, masks, key, shape, p):
+        """Dropout multipliers (0 or 1/(1-p)): explicit ``masks[key]`` (tests) or fresh Bernoulli draws."""
+        if masks is not None:
+            m = masks.get(key)
+            return None if m is None else torch.as_tensor(m, dtype=torch.float32).reshape(shape).contiguous().to(self.device)
+        if p <= 0:
+            return None
+        if self._mask_buf is None:
+            self._draw_masks()
+        o, n = self._mask_pos[key]
+        return self._mask_buf[o:o + n].view(shape)
+
+    def step_pcm(self, pcm, plan, sr, y, masks=None, bias=None):
+        """pcm: float32 device tensor (clips back to back), plan: BatchPlan -- mel front end fused into the step."""
+        mel, floor = self.eng.mel(pcm, plan, sr, clamp=False)
+        d = plan.to(self.device)
+        return self._step(mel, d['frame_off'], plan.n_wins, floor, y, masks, bias)
+
+    def step_spec(self, specs, y, masks=None, bias=None):
+        """specs: list of [48, T] dB spectrograms (the input of segment_specs) -- used by the parity tests."""
+        T = np.array([s.shape[1] for s in specs], dtype=np.int64)
+        hop = int(self.args['ms_seg_hop_length'])
+        n_wins = np.ceil((T - (SEG_LEN - 1)) / hop).astype(np.int64)
+        mel = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(s, np.float32).T for s in specs], 0))).to(self.device)
+        frame_off = torch.from_numpy(np.concatenate(([0], np.cumsum(T))).astype(np.int32)).to(self.device)
+        floor = torch.full((len(specs),), -3.0e38, dtype=torch.float32, device=self.device)
+        return self._step(mel, frame_off, n_wins, floor, y, masks, bias)
+
+    def _ksplit(self, rows, m=64, n=64):
+        """K-chunks of a weight-gradient GEMM (K = rows of the batch): enough workgroups to fill 256 CUs a few times
+        over (tiles x chunks ~ 2048), chunks of at least NISQA_HIP_TRAIN_KCHUNK rows (a K-tile of 32 rows takes a workgroup
+        ~1 us with its single-buffered loads: a 512-row chunk is a 16 us kernel however small the product)."""
+        tiles = ((m + 63) // 64) * ((n + 63) // 64)
+        return int(max(1, min(2048 // tiles, rows // self._kchunk, 4096)))
+
+    def _linear_fwd(self, X, wk, bk, rows, n_in, n_out, relu=False):
+        Y = self._new(rows, n_out)
+        self._gemm(X, self.P[wk], Y, rows, n_out, n_in, n_in, n_in, n_out, tb=1, bias=self.P[bk], relu=1 if relu else 0)
+        return Y
+
+    def _linear_bwd(self, dY, X, wk, bk, rows, n_in, n_out, need_dx=True):
+        s = self._coldot(dY, dY, rows, n_out)
+        self._defer_cast(s, 0, n_out, self.G[bk])
+        self._gemm(dY, X, self.G[wk], n_out, n_in, rows, n_out, n_in, n_in, ta=1, ksplit=self._ksplit(rows, n_out, n_in))
+        if not need_dx:
+            return None
+        dX = self._new(rows, n_in)
+        self._gemm(dY, self.P[wk], dX, rows, n_in, n_out, n_out, n_in, n_in)
+        return dX
+
+    def _finish_step(self, y_hat, loss):
+        """End of a step: the deferred gradient casts, the data-parallel exchange (one all-reduce of the flat gradient buffer,
+        rank 0's BatchNorm buffers broadcast) and the Adam update; records ``self.last``."""
+        L_ = self.lib
+        st = self._st()
+        self._flush_casts()
+
+        # ================= data parallel: one all-reduce of the flat gradient buffer =================
+        if _dist.world()[1] > 1:
+            _dist.all_reduce_sum_(self.gflat)
+            buf = torch.cat([torch.cat([self.bn[i]['mean'], self.bn[i]['var']]) for i in range(1, 7)])
+            _dist.broadcast_(buf, 0)
+            o = 0
+            for i in range(1, 7):
+                c = self.bn[i]['mean'].numel()
+                self.bn[i]['mean'].copy_(buf[o:o + c])
+                self.bn[i]['var'].copy_(buf[o + c:o + 2 * c])
+                o += 2 * c
+
+        # ================= Adam =================
+        self.t += 1
+        self._ck(L_.nisqa_adam_step(_ptr(self.flat), _ptr(self.gflat), _ptr(self.m), _ptr(self.v), self.flat.numel(), self.lr,
+                                    self.t, st), 'nisqa_adam_step')
+        self.last = {'y_hat': y_hat, 'loss': loss}
+        return loss
+
+
+class HipTrainer(_FlatTrainer):
+    LAYOUT = 'nisqa_amd flat buffer (HipTrainer.keys / kshape order)'
+
     def __init__(self, args, state_dict, device=None, lr=1e-3, precision=None):
         """precision of conv2..6 (everything else is fp32 in every mode); NISQA_HIP_TRAIN_PRECISION sets the default:
           'f32'    forward, dgrad and wgrad on exact fp32 MFMA: the reference's arithmetic;
@@ -159,22 +336,6 @@ class HipTrainer(object):
         self._debug = {} if os.environ.get('NISQA_HIP_TRAIN_DEBUG') == '1' else None
 
     # ---- parameters ------------------------------------------------------------------------------------
-    def _layout(self, sd):
-        keys = [k for k in sd if k.split('.')[-1] not in ('running_mean', 'running_var', 'num_batches_tracked')]
-        self.keys, self.off, self.kshape = keys, {}, {}
-        n = 0
-        for k in keys:
-            shape = tuple(sd[k].shape)
-            if k.startswith('cnn.model.conv') and k.endswith('.weight'):
-                shape = (shape[0], 9 * shape[1])
-            self.off[k], self.kshape[k] = n, shape
-            n += int(np.prod(shape))
-            n = (n + 3) // 4 * 4
-        self.flat = torch.zeros(n, dtype=torch.float32, device=self.device)
-        self.gflat = torch.zeros_like(self.flat)
-        self.P = {k: self.flat[self.off[k]:self.off[k] + int(np.prod(self.kshape[k]))].view(self.kshape[k]) for k in keys}
-        self.G = {k: self.gflat[self.off[k]:self.off[k] + int(np.prod(self.kshape[k]))].view(self.kshape[k]) for k in keys}
-
     def _td_param_offsets(self):
         """Offsets of the self-attention / pooling parameters in the flat buffers, in the order nisqa_tdtrain_* documents."""
         pfx = 'time_dependency.model.'
@@ -206,45 +367,7 @@ class HipTrainer(object):
             return v.reshape(v.shape[0], 6, 64).permute(0, 2, 1).reshape(v.shape[0], 384)
         return v
 
-    def load_state_dict(self, sd):
-        self._ref_shape = {k: tuple(sd[k].shape) for k in sd}
-        for k in self.keys:
-            v = torch.as_tensor(np.asarray(sd[k]) if not torch.is_tensor(sd[k]) else sd[k]).float()
-            self.P[k].copy_(self._to_kernel(k, v).contiguous().to(self.device))
-        self.bn = {}
-        for i in range(1, 7):
-            p = 'cnn.model.bn%d.' % i
-            self.bn[i] = {'mean': torch.as_tensor(np.asarray(sd[p + 'running_mean'])).float().to(self.device).clone(),
-                          'var': torch.as_tensor(np.asarray(sd[p + 'running_var'])).float().to(self.device).clone(),
-                          'n': int(np.asarray(sd[p + 'num_batches_tracked'])) if p + 'num_batches_tracked' in sd else 0}
-
-    def state_dict(self):
-        """Reference keys and shapes (CPU tensors): loads into the reference's model and into HipNisqa."""
-        out = {}
-        for k, shape in self._ref_shape.items():
-            last = k.split('.')[-1]
-            if last in ('running_mean', 'running_var', 'num_batches_tracked'):
-                i = int(k.split('.')[2][2:])
-                out[k] = (torch.tensor(self.bn[i]['n']) if last == 'num_batches_tracked'
-                          else self.bn[i]['mean' if last == 'running_mean' else 'var'].cpu().clone())
-            else:
-                out[k] = self._from_kernel(k, self.P[k].cpu(), shape).contiguous().clone()
-        return out
-
-    def grads(self):
-        """Gradients of the last step in the reference's shapes (CPU tensors)."""
-        return {k: self._from_kernel(k, self.G[k].cpu(), self._ref_shape[k]).contiguous().clone() for k in self.keys}
-
     # ---- thin wrappers over the C ABI ------------------------------------------------------------------------
-    def _st(self):
-        return torch.cuda.current_stream(self.device).cuda_stream
-
-    def _ck(self, rc, what):
-        _lib.check(rc, what)
-
-    def _new(self, *shape, dtype=torch.float32):
-        return torch.empty(shape, dtype=dtype, device=self.device)
-
     def _segconv_pack(self, geo):
         """Weight fragments of this step for every layer / direction csrc/train_conv.hip takes (mode 0 forward -- 'bf16x3'
         only --, mode 1 input gradient): ONE launch (nisqa_segconv_pack_many).  self._sc_frags[(mode, i)] is absent where the
@@ -292,11 +415,6 @@ class HipTrainer(object):
             self._ck(self._sc_pack_many(n, arr_i(0), arr_p(1), arr_i(2), arr_i(3), arr_p(4), self._st()),
                      'nisqa_segconv_pack_many')
 
-    def _gemm(self, A, B, C, M, N, K, lda, ldb, ldc, ta=0, tb=0, ksplit=1, ao=0, bo=0, co=0, bias=None, relu=0):
-        self._ck(self.lib.nisqa_gemm_f32_one(_ptr(A, ao), _ptr(B, bo), _ptr(C, co), M, N, K, lda, ldb, ldc, ta, tb, ksplit,
-                                             1.0, _ptr(bias) if bias is not None else None, relu, self._st()),
-                 'nisqa_gemm_f32_one')
-
     def _ggemm(self, kind, A, B, C, ta=0, tb=0, ao=0, bo=0, co=0):
         d, tiles = self._desc[kind]
         self._ck(self.lib.nisqa_gemm_f32(_ptr(A, ao), _ptr(B, bo), _ptr(C, co), d.data_ptr(), d.shape[0], tiles, ta, tb, 1,
@@ -310,34 +428,6 @@ class HipTrainer(object):
                                             _ptr(bias) if bias is not None else None, rows, cols, _ptr(out), self._st()),
                  'nisqa_elementwise')
         return out
-
-    def _coldot(self, a, b, rows, c):
-        s = self._sums[self._sum_i]
-        self._sum_i += 1
-        self._ck(self.lib.nisqa_col_dot(_ptr(a), _ptr(b), rows, c, s.data_ptr(), self._st()), 'nisqa_col_dot')
-        return s
-
-    def _ksplit(self, rows, m=64, n=64):
-        """K-chunks of a weight-gradient GEMM (K = rows of the batch): enough workgroups to fill 256 CUs a few times
-        over (tiles x chunks ~ 2048), chunks of at least NISQA_HIP_TRAIN_KCHUNK rows (a K-tile of 32 rows takes a workgroup
-        ~1 us with its single-buffered loads: a 512-row chunk is a 16 us kernel however small the product)."""
-        tiles = ((m + 63) // 64) * ((n + 63) // 64)
-        return int(max(1, min(2048 // tiles, rows // self._kchunk, 4096)))
-
-    def _linear_fwd(self, X, wk, bk, rows, n_in, n_out, relu=False):
-        Y = self._new(rows, n_out)
-        self._gemm(X, self.P[wk], Y, rows, n_out, n_in, n_in, n_in, n_out, tb=1, bias=self.P[bk], relu=1 if relu else 0)
-        return Y
-
-    def _linear_bwd(self, dY, X, wk, bk, rows, n_in, n_out, need_dx=True):
-        s = self._coldot(dY, dY, rows, n_out)
-        self._defer_cast(s, 0, n_out, self.G[bk])
-        self._gemm(dY, X, self.G[wk], n_out, n_in, rows, n_out, n_in, n_in, ta=1, ksplit=self._ksplit(rows, n_out, n_in))
-        if not need_dx:
-            return None
-        dX = self._new(rows, n_in)
-        self._gemm(dY, self.P[wk], dX, rows, n_in, n_out, n_out, n_in, n_in)
-        return dX
 
     def _ln_fwd(self, X, gk, bk, rows):
         y, xh, rs = self._new(rows, 64), self._new(rows, 64), self._new(rows)
@@ -408,57 +498,7 @@ class HipTrainer(object):
             o += (n + 3) // 4 * 4
         self._mask_total, self._mask_split = o, self._mask_pos['td0_p'][0] if self.n_layers else o
 
-    def _draw_masks(self):
-        self._mask_buf = self._new(self._mask_total)
-        for lo, hi, p in ((0, self._mask_split, self.p_cnn), (self._mask_split, self._mask_total, self.p_td)):
-            if hi > lo and p > 0:
-                self._ck(self.lib.nisqa_dropout_mask(self._rng_seed, self._rng_off, p, hi - lo, _ptr(self._mask_buf, lo),
-                                                     self._st()), 'nisqa_dropout_mask')
-                self._rng_off += (hi - lo + 3) // 4
-
-    def _defer_cast(self, s, lo, n, dst):
-        """float64 sums s[lo:lo+n] -> float32 gradient view dst, executed by one nisqa_cast_scatter at the end of backward"""
-        self._casts.append(((s.data_ptr() - self._sums.data_ptr()) // 8 + lo, (dst.data_ptr() - self.gflat.data_ptr()) // 4, n))
-
-    def _flush_casts(self):
-        if not self._casts:
-            return
-        key = tuple(self._casts)
-        if key != self._cast_key:
-            self._cast_key = key
-            self._cast_table = torch.tensor(self._casts, dtype=torch.int32, device=self.device)
-        self._ck(self.lib.nisqa_cast_scatter(self._sums.data_ptr(), self._cast_table.data_ptr(), len(self._casts),
-                                             _ptr(self.gflat), self._st()), 'nisqa_cast_scatter')
-
-    def _mask(self, masks, key, shape, p):
-        """Dropout multipliers (0 or 1/(1-p)): explicit ``masks[key]`` (tests) or fresh Bernoulli draws."""
-        if masks is not None:
-            m = masks.get(key)
-            return None if m is None else torch.as_tensor(m, dtype=torch.float32).reshape(shape).contiguous().to(self.device)
-        if p <= 0:
-            return None
-        if self._mask_buf is None:
-            self._draw_masks()
-        o, n = self._mask_pos[key]
-        return self._mask_buf[o:o + n].view(shape)
-
     # ---- the step ------------------------------------------------------------------------------------------
-    def step_pcm(self, pcm, plan, sr, y, masks=None, bias=None):
-        """pcm: float32 device tensor (clips back to back), plan: BatchPlan -- mel front end fused into the step."""
-        mel, floor = self.eng.mel(pcm, plan, sr, clamp=False)
-        d = plan.to(self.device)
-        return self._step(mel, d['frame_off'], plan.n_wins, floor, y, masks, bias)
-
-    def step_spec(self, specs, y, masks=None, bias=None):
-        """specs: list of [48, T] dB spectrograms (the input of segment_specs) -- used by the parity tests."""
-        T = np.array([s.shape[1] for s in specs], dtype=np.int64)
-        hop = int(self.args['ms_seg_hop_length'])
-        n_wins = np.ceil((T - (SEG_LEN - 1)) / hop).astype(np.int64)
-        mel = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(s, np.float32).T for s in specs], 0))).to(self.device)
-        frame_off = torch.from_numpy(np.concatenate(([0], np.cumsum(T))).astype(np.int32)).to(self.device)
-        floor = torch.full((len(specs),), -3.0e38, dtype=torch.float32, device=self.device)
-        return self._step(mel, frame_off, n_wins, floor, y, masks, bias)
-
     def _td_plan(self, L):
         """Tables of the fused self-attention block for clips of L[b] segments: padded token offsets (32 per tile), the clip of
         every tile, the prefix sum of L^2, and what nisqa_tdtrain_plan lays out (workspace / fragment sizes, the descriptors of
@@ -886,23 +926,4 @@ class HipTrainer(object):
                              'nisqa_conv3x3_gemm dgrad')
             c['x'] = None
 
-        self._flush_casts()
-
-        # ================= data parallel: one all-reduce of the flat gradient buffer =================
-        if _dist.world()[1] > 1:
-            _dist.all_reduce_sum_(self.gflat)
-            buf = torch.cat([torch.cat([self.bn[i]['mean'], self.bn[i]['var']]) for i in range(1, 7)])
-            _dist.broadcast_(buf, 0)
-            o = 0
-            for i in range(1, 7):
-                c = self.bn[i]['mean'].numel()
-                self.bn[i]['mean'].copy_(buf[o:o + c])
-                self.bn[i]['var'].copy_(buf[o + c:o + 2 * c])
-                o += 2 * c
-
-        # ================= Adam =================
-        self.t += 1
-        self._ck(L_.nisqa_adam_step(_ptr(self.flat), _ptr(self.gflat), _ptr(self.m), _ptr(self.v), self.flat.numel(), self.lr,
-                                    self.t, st), 'nisqa_adam_step')
-        self.last = {'y_hat': y_hat, 'loss': loss}
-        return loss
+        return self._finish_step(y_hat, loss)

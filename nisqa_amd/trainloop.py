@@ -1,7 +1,8 @@
 """Host side of ``nisqaModel.train()`` (reference nisqa/NISQA_model.py:83-570, ``_train_mos`` / ``_train_dim``): epochs,
 shuffled mini-batches, the bias-aware loss bookkeeping, per-epoch evaluation on the training and validation sets,
 ReduceLROnPlateau, early stopping, results CSV and checkpoints -- around the per-batch step, which runs as HIP kernels
-(``nisqa_amd.train.HipTrainer``: forward in train mode, backward, Adam).  WAV files reach the GPU through the same
+(``nisqa_amd.train.HipTrainer`` for CNN-SA-AP, ``nisqa_amd.train_lstm.HipTrainerLSTM`` for StandardCNN + BiLSTM: forward in
+train mode, backward, Adam).  WAV files reach the GPU through the same
 native ingest as prediction (``nisqa_amd.ingest``); the validation pass is the inference engine on the current weights.
 
 One loop serves both model types: ``targets`` is ['mos'] (well: csv_mos_train) for NISQA and
@@ -23,6 +24,7 @@ from . import dist as _dist
 from . import ingest as _ingest
 from .evaluation import eval_results
 from .train import HipTrainer
+from .train_lstm import HipTrainerLSTM
 
 
 # ---- mirrors of the reference's small training helpers ------------------------------------------------------------
@@ -119,6 +121,17 @@ class ReduceLROnPlateau(object):
 
 
 # ---- the loop -----------------------------------------------------------------------------------------------------
+def trainer_class(args):
+    """HipTrainerLSTM for cnn_model=standard / td=lstm, else HipTrainer (which refuses what it does not build)"""
+    if args.get('cnn_model') == 'standard' and args.get('td') == 'lstm':
+        return HipTrainerLSTM
+    return HipTrainer
+
+
+def make_trainer(args, state_dict, device, lr):
+    return trainer_class(args)(args, state_dict, device, lr=lr)
+
+
 _DIM = ['mos', 'noi', 'dis', 'col', 'loud']
 
 
@@ -150,7 +163,7 @@ def train(nm):
     preds = [n + '_pred' for n in names]
     sfx = [''] + ['_' + n for n in names[1:]]
     nm.runname = nm._makeRunnameAndWriteYAML()
-    tr = HipTrainer(a, nm.model.state_dict(), nm.dev, lr=a['tr_lr'])
+    tr = make_trainer(a, nm.model.state_dict(), nm.dev, lr=a['tr_lr'])
     scheduler = ReduceLROnPlateau(tr, a['tr_lr_patience'])
     stopper = earlyStopper(a['tr_early_stop'], tuple(sfx))
     losses = [biasLoss(nm.ds_train.df.db, anchor_db=a['tr_bias_anchor_db'], mapping=a['tr_bias_mapping'],
@@ -277,7 +290,7 @@ def _save_results(nm, tr, epoch, loss, ep_runtime, r, db_results, best):
         torch.save({'runname': nm.runname, 'epoch': epoch + 1, 'model_args': _plain(nm.model_args), 'args': _plain(a),
                     'model_state_dict': tr.state_dict(),
                     'optimizer_state_dict': {'step': tr.t, 'lr': tr.lr, 'exp_avg': tr.m.cpu(), 'exp_avg_sq': tr.v.cpu(),
-                                             'layout': 'nisqa_amd flat buffer (HipTrainer.keys / kshape order)'},
+                                             'layout': tr.LAYOUT},
                     'db_results': _plain(db_results), 'results': _plain(results), 'model_name': nm.model.name},
                    os.path.join(out_dir, filename))
 
