@@ -14,8 +14,10 @@
 //     transposes (row strides 72 complex / 80 B: conflict free for ds_write_b64 / ds_read_b128);
 //     every twiddle is either a per-lane register loaded once per wave or a compile-time constant;
 //   * real-input recombination X[K] = (Z[K] + conj Z[2048-K])/2 - i W4096^K (Z[K] - conj Z[2048-K])/2:
-//     the partner of Z_r[k] is Z_(4-r)[511-k] (Z_0[512-k] for r = 0), i.e. the SAME register index
-//     mirrored in lane 63-l (64-l): a lane shuffle, no spectrum buffer;
+//     the partner of Z_r[k] is Z_(4-r)[511-k] (Z_0[512-k] for r = 0), i.e. the mirrored register index
+//     in lane 63-l (64-l).  One lane holding both values produces BOTH bins of the pair, so no lane shuffle:
+//     Z_3 is read out of the FFT's last transpose lane-mirrored (lane l gets the partners of its Z_1), and the
+//     self-paired r = 0, 2 exchange half their registers through a planar wave-private LDS copy;
 //   * slaney filterbank in sparse form (each bin feeds <= 2 triangles): 4 bands per pass, one per
 //     16-lane row, weights shared in LDS by the workgroup, row totals by DPP butterflies;
 //   * 10*log10(max(amin^2, S^2)), coalesced 192-byte store per frame, running per-clip maximum kept
@@ -80,9 +82,12 @@ NQ_DEV void dft8(c32 (&v)[8]) {
     const c32 s1 = cadd_mi(o1, o1);                       // o1 * W8^1 = r (x + y, y - x) = r s1
     const c32 s3 = csub_mi(o3, o3);                       // o3 * W8^3 = r (y - x, -x - y) = -r s3
     v[0] = cadd(e0, o0); v[4] = csub(e0, o0);
-    v[1] = e1 + s1 * r; v[5] = e1 - s1 * r;
+    // explicit fmas: left to -ffp-contract, e + s * r fused in one instantiation and not in another once the magnitude code
+    // around the transforms changed shape; the specialised and the generic filter-bank kernels must agree bit for bit
+    const c32 rr = cmk(r, r);
+    v[1] = __builtin_elementwise_fma(s1, rr, e1); v[5] = __builtin_elementwise_fma(-s1, rr, e1);
     v[2] = cadd_mi(e2, o2); v[6] = csub_mi(e2, o2);       // o2 * W8^2 = -i o2
-    v[3] = e3 - s3 * r; v[7] = e3 + s3 * r;
+    v[3] = __builtin_elementwise_fma(-s3, rr, e3); v[7] = __builtin_elementwise_fma(s3, rr, e3);
 }
 
 // exp(-2 pi i m / 32) and exp(-2 pi i m / 16) as (cos, -sin)
@@ -98,7 +103,7 @@ __device__ constexpr float W16S[16] = {-0.000000000e+00f, -3.826834324e-01f, -7.
 #define MEL_WAVES_OF(NQ) ((NQ) == 1 ? 12 : 4)
 // per-frame phase clock (tools/mel_clock.py; empty macros unless the unit is built with -DNQ_EXPERIMENTAL): phases 0..6, [8] = frames
 NQ_CLK_EXPORT(g_mel_clk, nisqa_debug_mel_clock)
-#define MEL_TAB_BYTES (4096 + 2048 + 1536 + 6144)   /* window taps, W4096 / W2048 twiddles, per-(pass, lane) filter-bank offsets */
+#define MEL_TAB_BYTES (4096 + 2048 + 1536 + 6144 + 512)   /* window taps, W4096 / W2048 twiddles, per-(pass, lane) filter-bank offsets, W4096^(4 j + 4) */
 #define MEL_EXCH_BYTES 5120            /* exchange 1 [8][72] complex (4608 B) and exchange 2 64 x 80 B alias */
 
 // sum over the 16 lanes of a DPP row, result in every lane of the row
@@ -109,8 +114,6 @@ NQ_DEV float row16_sum(float v) {
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));  // row_mirror
     return v;
 }
-
-NQ_DEV c32 shfl_c(c32 v, int src) { return cmk(__shfl((float)v.x, src), __shfl((float)v.y, src)); }
 
 // |2 X[K]| for K = 4k + r from za = Z[K], zb = Z[2048-K], W4096^K = wl * wc (per-lane x constant part;
 // applied one after the other so that nothing loop-invariant can be hoisted into 64 extra registers)
@@ -144,8 +147,9 @@ struct mel_twiddles {
     c32 c[8];   // W64^((l&7) q1)
 };
 
-// 512-point FFT of u[a] = z[l + 64 a] * W2048^(r (l + 64 a)); returns Z_r[l + 64 q2] in u[q2]
-template <int R>
+// 512-point FFT of u[a] = z[l + 64 a] * W2048^(r (l + 64 a)); returns Z_r[l + 64 q2] in u[q2], or with REV the mirrored
+// lane's Z_r[63 - l + 64 q2] (the last transpose reads row 63 - l instead of row l: the lane reversal comes for free)
+template <int R, bool REV = false>
 NQ_DEV void fft512(c32 (&u)[8], const c32 (&z)[8], const mel_twiddles& tw, char* exch, int lane, const c32* tab_a) {
     const c32 aR = R ? tab_a[(R - 1) * 64 + lane] : cmk(1.f, 0.f);
 #pragma unroll
@@ -175,7 +179,7 @@ NQ_DEV void fft512(c32 (&u)[8], const c32 (&z)[8], const mel_twiddles& tw, char*
     MEL_WBAR();
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const f32x4 t4 = *(const f32x4*)(exch + lane * 80 + q * 16);
+        const f32x4 t4 = *(const f32x4*)(exch + (REV ? 63 - lane : lane) * 80 + q * 16);
         u[2 * q] = cmk(t4[0], t4[1]);
         u[2 * q + 1] = cmk(t4[2], t4[3]);
     }
@@ -218,6 +222,7 @@ __global__ __launch_bounds__(64 * MEL_WAVES_OF(NQ), NQ == 2 ? 2 : 1) void mel_fr
     c32* tab_d = (c32*)(smem + w_bytes + 4096);                   // W4096^(4 l + r), [4][64]
     c32* tab_a = (c32*)(smem + w_bytes + 4096 + 2048);            // W2048^(r l), r = 1..3, [3][64]
     int* tab_band = (int*)(smem + w_bytes + 4096 + 2048 + 1536);  // per (pass, lane): byte offsets of the first magnitude and the first weight
+    c32* tab_e = (c32*)(smem + w_bytes + 4096 + 2048 + 1536 + 6144);     // W4096^(4 (j + 1)), [64]: r = 0 twiddles of lane 64 - l at j = 63 - l
     float* mag = (float*)(smem + w_bytes + MEL_TAB_BYTES + wave * per_wave);   // |X[K]| at plane(K&3)*mag_stride + (K>>2), plane(r) = 0, 2, 1, 3
     char* exch = (char*)(mag + 2 * mag_stride);                   // = planes 1, 3 (+ extra)
     // the 1/2 of |X[K]| = |2 X[K]| / 2 rides on the band weights (a power of two: same bits), not on every bin
@@ -228,6 +233,7 @@ __global__ __launch_bounds__(64 * MEL_WAVES_OF(NQ), NQ == 2 ? 2 : 1) void mel_fr
         for (int i = tid; i < 1024; i += 64 * MEL_WAVES) tab_w[i] = (NQ == 1 && i < cfg.win) ? window[i] * sc_ : 0.f;
         for (int i = tid; i < 256; i += 64 * MEL_WAVES) { const float2 w = twg[4 * (i & 63) + (i >> 6)]; tab_d[i] = cmk(w.x, w.y); }
         for (int i = tid; i < 192; i += 64 * MEL_WAVES) { const float2 w = twg[(2 * (i / 64 + 1) * (i & 63)) & 4095]; tab_a[i] = cmk(w.x, w.y); }
+        for (int i = tid; i < 64; i += 64 * MEL_WAVES) { const float2 w = twg[4 * (i + 1)]; tab_e[i] = cmk(w.x, w.y); }
         for (int i = tid; i < 12 * 64; i += 64 * MEL_WAVES) {           // pass ps, lane l: band 4 ps + (l >> 4), first bin K0 + (l & 15)
             const int bnd = 4 * (i >> 6) + ((i & 63) >> 4), K0_ = band_start[bnd] + (i & 15);
             tab_band[2 * i] = 4 * ((((K0_ & 1) << 1) | ((K0_ >> 1) & 1)) * mag_stride + (K0_ >> 2));   // plane order 0, 2, 1, 3
@@ -258,8 +264,13 @@ __global__ __launch_bounds__(64 * MEL_WAVES_OF(NQ), NQ == 2 ? 2 : 1) void mel_fr
     // (a compile-time constant in the FB instantiations, which the launcher selects BY n_bins: the per-group guards below
     // then fold away and the eight magnitude groups of a transform become one basic block the scheduler can interleave)
     const int kmax = FB == 1 ? (1707 + 3) / 4 : FB == 2 ? (683 + 3) / 4 : (cfg.n_bins + 3) >> 2;
-    constexpr int ZG = FB != 0 ? 8 : 2, MG = FB != 0 ? 4 : 1;                   // magnitude groups whose partners are fetched ahead (registers: the generic
-                                                         // instantiation sits at the 168-register limit of three waves per SIMD)
+    // entries of the r = 0 plane above 511 (the Nyquist bin, 512) are written on their own
+    const int kmax0 = min(kmax, 512);
+    // everything a lane takes from its mirror lane is addressed by 63 - l: the partner twiddles W4096^K of the bins it produces
+    // for lane 63 - l (r = 2, 3) and for lane (64 - l) & 63 (r = 0: tab_e, whose entry 63 holds W4096^256 for lane 0, whose bins
+    // 64 (8 - q) are its own), and the partner values of the self-paired transforms below
+    // (formed where it is used: as a loop invariant it and the addresses derived from it would hold registers across the frame)
+    auto mirror_lane = [&] { int r_; asm volatile("v_sub_u32 %0, 63, %1" : "=v"(r_) : "v"(lane)); return r_; };
 
     int b = find_segment(frame_off, n_clips, f_begin);
     float runmax = -3.0e38f;
@@ -344,90 +355,75 @@ __global__ __launch_bounds__(64 * MEL_WAVES_OF(NQ), NQ == 2 ? 2 : 1) void mel_fr
         c32 z[8];
 
         c32 u[8], u1[8];
-        const int mir = 63 - lane;
+        // |2 X[K]| for a bin K = 4 (l + 64 q) + r AND for its partner 2048 - K, from the same two values (the real-input
+        // recombination of the pair needs Z[K] and Z[2048 - K] either way): a = Z[K] of this lane, b = Z[2048 - K], wa / wb their
+        // per-lane twiddle parts, ea / eb their plane entries; each side only where its group of 64 entries holds a wanted bin
+        auto mag_pair = [&](float* pl_a, float* pl_b, int q, int qb, c32 a, c32 b_, c32 wa, c32 wb, int ea, int eb, int ka, int kb) {
+            const bool lo = 64 * q < kmax, hi = 64 * qb < kmax;   // wave-uniform
+            if (lo && hi) {
+                float m0, m1;
+                xmag2(a, b_, wa, cmk(W16C[q], W16S[q]), b_, a, wb, cmk(W16C[qb], W16S[qb]), m0, m1);
+                if (ea < ka) pl_a[ea] = m0;
+                if (eb < kb) pl_b[eb] = m1;
+            } else if (lo) {
+                if (ea < ka) pl_a[ea] = xmag(a, b_, wa, cmk(W16C[q], W16S[q]));
+            } else if (hi) {
+                if (eb < kb) pl_b[eb] = xmag(b_, a, wb, cmk(W16C[qb], W16S[qb]));
+            }
+        };
+        // the self-paired transforms r = 0, 2: lane l combines its registers q < 4 with the partner lane's registers 7 - q,
+        // fetched through a planar LDS copy of registers 4..7 (ds_write / ds_read_b64, no lane shuffle); slot 4 = register 0
+        // serves lane 0 of r = 0, whose partners are its own registers 0, 7, 6, 5 (Z_0[512 - 64 q], read one slot up)
+        auto self_pair = [&](int r, float* pl) {
+            const int rl = mirror_lane();
+            c32* xs = (c32*)exch;
+#pragma unroll
+            for (int s_ = 0; s_ < 4; ++s_)
+                if (64 * (3 - s_) < kmax || 64 * (4 + s_) < kmax) xs[64 * s_ + lane] = u[4 + s_];
+            if (r == 0) xs[256 + lane] = u[0];
+            MEL_WBAR();
+            const c32* xr = xs + rl + (r == 0);       // r = 0: lane 64 - l, and for lane 0 slot 1 up in column 0
+            c32 p[4];
+#pragma unroll
+            for (int q = 0; q < 4; ++q)
+                if (64 * q < kmax || 64 * (7 - q) < kmax) p[q] = xr[64 * (3 - q)];
+            MEL_WBAR();
+            const c32 wa = tab_d[r * 64 + lane], wb = r == 0 ? tab_e[rl] : tab_d[2 * 64 + rl];
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int e = lane + 64 * q;
+                mag_pair(pl, pl, q, 7 - q, u[q], p[q], wa, wb, e, (r == 0 ? 512 : 511) - e, kmax, kmax0);
+            }
+        };
         NQ_SUM(0);                                   // window + prefetch
-        // r = 0: partner Z_0[512 - k] = lane (64 - l) & 63, register 7 - q2 (lane 0: register (8 - q2) & 7)
+        // r = 0: partner of Z_0[k] is Z_0[512 - k] = lane (64 - l) & 63, register 7 - q2 (lane 0: register (8 - q2) & 7)
         fold(0, z);
         fft512<0>(u, z, tw, exch, lane, tab_a);
-        {
-            const int src = (64 - lane) & 63;
-            // partners first (ZG groups ahead), then the magnitude chains two groups per call: the dependent chains of packed
-            // operations interleave instead of running one behind the other with s_nop between their links (round 3)
-#pragma unroll
-            for (int q0 = 0; q0 < 8; q0 += ZG) {
-                c32 zb[ZG];
-#pragma unroll
-                for (int e = 0; e < ZG; ++e) {
-                    const int q2 = q0 + e;
-                    if (64 * q2 >= kmax) continue;         // wave-uniform: bins above fmax are never produced
-                    zb[e] = shfl_c(u[7 - q2], src);
-                    if (lane == 0) zb[e] = u[(8 - q2) & 7];
-                }
-#pragma unroll
-                for (int e = 0; e < ZG; e += 2) {
-                    const int q2 = q0 + e;
-                    if (64 * q2 >= kmax) continue;
-                    const c32 wl = tab_d[0 * 64 + lane];
-                    if (64 * (q2 + 1) < kmax) {
-                        float m0, m1;
-                        xmag2(u[q2], zb[e], wl, cmk(W16C[q2], W16S[q2]), u[q2 + 1], zb[e + 1], wl, cmk(W16C[q2 + 1], W16S[q2 + 1]), m0, m1);
-                        if (lane + 64 * q2 < kmax) mag[0 * mag_stride + lane + 64 * q2] = m0;
-                        if (lane + 64 * (q2 + 1) < kmax) mag[0 * mag_stride + lane + 64 * (q2 + 1)] = m1;
-                    } else if (lane + 64 * q2 < kmax)
-                        mag[0 * mag_stride + lane + 64 * q2] = xmag(u[q2], zb[e], wl, cmk(W16C[q2], W16S[q2]));
-                }
-            }
-            if (lane == 0 && 512 < mag_stride) mag[512] = 2.0f * fabsf(u[0].x - u[0].y);   // Nyquist bin: 2 X[2048] = 2 (Re Z0 - Im Z0)
-
+        self_pair(0, mag);
+        if (lane == 0) {                             // the two bins of lane 0 that pair with themselves beyond q = 0
+            if (256 < kmax) mag[256] = xmag(u[4], u[4], tab_d[0], cmk(W16C[4], W16S[4]));   // 2 X[1024]
+            if (512 < mag_stride) mag[512] = 2.0f * fabsf(u[0].x - u[0].y);   // Nyquist bin: 2 X[2048] = 2 (Re Z0 - Im Z0)
         }
         NQ_SUM(1);                                   // FFT r = 0 + magnitudes
         // r = 2: partner Z_2[511 - k] = lane 63 - l, register 7 - q2
         fold(2, z);
         fft512<2>(u, z, tw, exch, lane, tab_a);
-#pragma unroll
-        for (int q0 = 0; q0 < 8; q0 += ZG) {
-            c32 zb[ZG];
-#pragma unroll
-            for (int e = 0; e < ZG; ++e)
-                if (64 * (q0 + e) < kmax) zb[e] = shfl_c(u[7 - q0 - e], mir);
-#pragma unroll
-            for (int e = 0; e < ZG; e += 2) {
-                const int q2 = q0 + e;
-                if (64 * q2 >= kmax) continue;
-                const c32 wl = tab_d[2 * 64 + lane];
-                if (64 * (q2 + 1) < kmax) {
-                    float m0, m1;
-                    xmag2(u[q2], zb[e], wl, cmk(W16C[q2], W16S[q2]), u[q2 + 1], zb[e + 1], wl, cmk(W16C[q2 + 1], W16S[q2 + 1]), m0, m1);
-                    if (lane + 64 * q2 < kmax) mag[1 * mag_stride + lane + 64 * q2] = m0;
-                    if (lane + 64 * (q2 + 1) < kmax) mag[1 * mag_stride + lane + 64 * (q2 + 1)] = m1;
-                } else if (lane + 64 * q2 < kmax)
-                    mag[1 * mag_stride + lane + 64 * q2] = xmag(u[q2], zb[e], wl, cmk(W16C[q2], W16S[q2]));
-            }
-        }
+        self_pair(2, mag + mag_stride);
         NQ_SUM(2);                                   // FFT r = 2 + magnitudes
-        // r = 1 and r = 3 are each other's partners
+        // r = 1 and r = 3 are each other's partners: Z_3 is read out lane-mirrored, so the partner of Z_1[l + 64 q] (u1[q]),
+        // Z_3[63 - l + 64 (7 - q)], is this lane's u[7 - q] and both bins of the pair are produced here
         fold(1, z);
         fft512<1>(u1, z, tw, exch, lane, tab_a);
         fold(3, z);
-        fft512<3>(u, z, tw, exch, lane, tab_a);
+        fft512<3, true>(u, z, tw, exch, lane, tab_a);
         NQ_SUM(3);                                   // FFTs r = 1, 3
+        {
+            const int rl = mirror_lane();
+            const c32 wa = tab_d[1 * 64 + lane], wb = tab_d[3 * 64 + rl];
 #pragma unroll
-        for (int q0 = 0; q0 < 8; q0 += MG) {               // MG groups at a time: 2 MG partners, then 2 MG chains
-            c32 z3m[MG], z1m[MG];
-#pragma unroll
-            for (int e = 0; e < MG; ++e)
-                if (64 * (q0 + e) < kmax) { z3m[e] = shfl_c(u[7 - q0 - e], mir); z1m[e] = shfl_c(u1[7 - q0 - e], mir); }
-#pragma unroll
-            for (int e = 0; e < MG; ++e) {
-                const int q2 = q0 + e;
-                if (64 * q2 >= kmax) continue;
-                const c32 w16 = cmk(W16C[q2], W16S[q2]);
-                float m1_, m3_;
-                xmag2(u1[q2], z3m[e], tab_d[1 * 64 + lane], w16, u[q2], z1m[e], tab_d[3 * 64 + lane], w16, m1_, m3_);
-                if (lane + 64 * q2 < kmax) {
-                    mag[2 * mag_stride + lane + 64 * q2] = m1_;
-                    mag[3 * mag_stride + lane + 64 * q2] = m3_;
-                }
+            for (int q = 0; q < 8; ++q) {
+                const int e = lane + 64 * q;
+                mag_pair(mag + 2 * mag_stride, mag + 3 * mag_stride, q, 7 - q, u1[q], u[7 - q], wa, wb, e, 511 - e, kmax, kmax);
             }
         }
         MEL_WBAR();
@@ -471,7 +467,9 @@ __global__ __launch_bounds__(64 * MEL_WAVES_OF(NQ), NQ == 2 ? 2 : 1) void mel_fr
         // ---- amplitude_to_db(ref=1, amin=1e-4): 10*log10(max(amin^2, S^2)); running per-clip max
         if (l16 < 12) {
             const float db = 10.0f * log10f(fmaxf(cfg.amin_sq, mine * mine));
-            mel_tm[(size_t)f * NISQA_N_MELS + 4 * l16 + row] = db;
+            int col;                                    // 4 l16 + row, formed here (a hoisted 64-bit lane address would hold 2 registers)
+            asm volatile("v_lshl_or_b32 %0, %1, 2, %2" : "=v"(col) : "v"(l16), "v"(row));
+            (mel_tm + (size_t)f * NISQA_N_MELS)[col] = db;
             runmax = fmaxf(runmax, db);
         }
         if (bn != b || fn >= f_end) {                   // wave-uniform: publish this clip's maximum
