@@ -30,7 +30,9 @@ from . import lib as _lib
 from .engine import HipNisqa, SEG_LEN
 
 _CONV = [(1, 16), (16, 32), (32, 64), (64, 64), (64, 64), (64, 64)]      # (C_in, C_out) of conv1..conv6
-_DROP_AFTER = {2: 'cnn_d1', 3: 'cnn_d2', 4: 'cnn_d3', 5: 'cnn_d4'}       # Dropout2d sites (NISQA_lib.py:696-705)
+_DROP_AFTER = {2: 'cnn_d1', 3: 'cnn_d2', 4: 'cnn_d3', 5: 'cnn_d4'}       # Dropout2d sites (NISQA_lib.py:696-705, 820-828)
+_BN_BUFFERS = ('running_mean', 'running_var', 'num_batches_tracked')
+_KCHUNK = 128                                                          # smallest split-K chunk of a weight gradient, rows
 
 
 def _ptr(t, off=0):
@@ -77,16 +79,29 @@ def step_tables(L):
     return parts, tiles
 
 
+def feat_to_kernel(w):
+    """Weight of a Linear on the flattened CNN output: columns c * pixels + pixel (the reference's flatten of [64][H][W])
+    -> columns pixel * 64 + c (the activations are [S][pixel][64])."""
+    return w.reshape(w.shape[0], 64, -1).permute(0, 2, 1).reshape(w.shape[0], -1)
+
+
+def feat_from_kernel(w):
+    return w.reshape(w.shape[0], -1, 64).permute(0, 2, 1).reshape(w.shape[0], -1)
+
+
 class _FlatTrainer(object):
     """What the HIP training steps share: every parameter in ONE flat device buffer in kernel layout (``_to_kernel`` /
-    ``_from_kernel`` of the subclass convert to and from the reference's shapes), its gradient buffer, the BatchNorm buffers of
+    ``_from_kernel`` convert to and from the reference's shapes), its gradient buffer, the BatchNorm buffers of
     cnn.model.bn1..6, the float64 column sums that end as gradients, the dropout masks, the mel front end of the step
-    (``self.eng``), the data-parallel exchange and the Adam update (``_finish_step``).  Subclasses set ``self.eng``,
-    ``self.lib``, ``self.device``, ``self.args``, ``self.lr``, ``self.t`` and implement ``_step``."""
+    (``self.eng``), the train-mode CNN (``_cnn_fwd`` / ``_cnn_bwd``), the data-parallel exchange and the Adam update
+    (``_finish_step``).  Subclasses set ``self.eng``, ``self.lib``, ``self.device``, ``self.args``, ``self.lr``,
+    ``self.precision``, ``self.p_cnn``, ``self.p_td``, call ``_init_params`` and ``_init_cnn`` and implement ``_step``."""
+    FEAT_W = None          # the subclass's Linear on the flattened CNN output: its columns are kept in (pixel, channel) order
+    _debug = None
 
     def _param_order(self, sd):
         """Trainable keys in flat-buffer order (default: the state_dict's own order)."""
-        return [k for k in sd if k.split('.')[-1] not in ('running_mean', 'running_var', 'num_batches_tracked')]
+        return [k for k in sd if k.split('.')[-1] not in _BN_BUFFERS]
 
     def _layout(self, sd):
         keys = self._param_order(sd)
@@ -103,6 +118,28 @@ class _FlatTrainer(object):
         self.gflat = torch.zeros_like(self.flat)
         self.P = {k: self.flat[self.off[k]:self.off[k] + int(np.prod(self.kshape[k]))].view(self.kshape[k]) for k in keys}
         self.G = {k: self.gflat[self.off[k]:self.off[k] + int(np.prod(self.kshape[k]))].view(self.kshape[k]) for k in keys}
+
+    def _init_params(self, state_dict, sum_rows):
+        """Flat buffers loaded from state_dict, Adam moments, sum_rows rows of float64 sums, the mask generator's seed."""
+        self.t = 0
+        self._layout(state_dict)
+        self.load_state_dict(state_dict)
+        self.m = torch.zeros_like(self.flat)
+        self.v = torch.zeros_like(self.flat)
+        self._sums = torch.zeros((sum_rows, 512), dtype=torch.float64, device=self.device)
+        self._cast_table, self._cast_key = None, None
+        self._rng_seed, self._rng_off = int(torch.initial_seed()) & (2 ** 64 - 1), 0     # torch.manual_seed governs the masks
+
+    def _to_kernel(self, k, v):
+        if k.startswith('cnn.model.conv') and k.endswith('.weight'):        # [C_out][C_in][3][3] -> [C_out][3*3*C_in]
+            return v.permute(0, 2, 3, 1).reshape(v.shape[0], -1)
+        return feat_to_kernel(v) if k == self.FEAT_W else v
+
+    def _from_kernel(self, k, v, ref_shape):
+        if k.startswith('cnn.model.conv') and k.endswith('.weight'):
+            co, ci = ref_shape[0], ref_shape[1]
+            return v.reshape(co, 3, 3, ci).permute(0, 3, 1, 2)
+        return feat_from_kernel(v) if k == self.FEAT_W else v
 
     def load_state_dict(self, sd):
         self._ref_shape = {k: tuple(sd[k].shape) for k in sd}
@@ -121,7 +158,7 @@ class _FlatTrainer(object):
         out = {}
         for k, shape in self._ref_shape.items():
             last = k.split('.')[-1]
-            if last in ('running_mean', 'running_var', 'num_batches_tracked'):
+            if last in _BN_BUFFERS:
                 i = int(k.split('.')[2][2:])
                 out[k] = (torch.tensor(self.bn[i]['n']) if last == 'num_batches_tracked'
                           else self.bn[i]['mean' if last == 'running_mean' else 'var'].cpu().clone())
@@ -147,9 +184,24 @@ class _FlatTrainer(object):
                                              1.0, _ptr(bias) if bias is not None else None, relu, self._st()),
                  'nisqa_gemm_f32_one')
 
+    def _sum_rows(self, n=1):
+        """The next n rows of the step's float64 sums (zeroed by _prepare), flat."""
+        s = self._sums[self._sum_i:self._sum_i + n].view(-1)
+        self._sum_i += n
+        return s
+
+    def _upload(self, a, cols):
+        """Labels (and bias coefficients) [B][cols] through page-locked memory: a pageable .to(device) blocks the host until the
+        previous step has drained, and the GPU then idles while this step's first launches are being issued."""
+        a = np.ascontiguousarray(np.asarray(a, np.float32).reshape(self.B, cols))
+        if self.device.type != 'cuda':
+            return torch.from_numpy(a).to(self.device)
+        h = torch.empty(a.shape, dtype=torch.float32, pin_memory=True)     # caching host allocator: reuse is stream-safe
+        h.numpy()[...] = a
+        return h.to(self.device, non_blocking=True)
+
     def _coldot(self, a, b, rows, c):
-        s = self._sums[self._sum_i]
-        self._sum_i += 1
+        s = self._sum_rows()
         self._ck(self.lib.nisqa_col_dot(_ptr(a), _ptr(b), rows, c, s.data_ptr(), self._st()), 'nisqa_col_dot')
         return s
 
@@ -205,10 +257,10 @@ class _FlatTrainer(object):
 
     def _ksplit(self, rows, m=64, n=64):
         """K-chunks of a weight-gradient GEMM (K = rows of the batch): enough workgroups to fill 256 CUs a few times
-        over (tiles x chunks ~ 2048), chunks of at least NISQA_HIP_TRAIN_KCHUNK rows (a K-tile of 32 rows takes a workgroup
-        ~1 us with its single-buffered loads: a 512-row chunk is a 16 us kernel however small the product)."""
+        over (tiles x chunks ~ 2048), chunks of at least _KCHUNK rows (a K-tile of 32 rows takes a workgroup ~1 us with its
+        single-buffered loads: a 512-row chunk is a 16 us kernel however small the product)."""
         tiles = ((m + 63) // 64) * ((n + 63) // 64)
-        return int(max(1, min(2048 // tiles, rows // self._kchunk, 4096)))
+        return int(max(1, min(2048 // tiles, rows // _KCHUNK, 4096)))
 
     def _linear_fwd(self, X, wk, bk, rows, n_in, n_out, relu=False):
         Y = self._new(rows, n_out)
@@ -224,6 +276,177 @@ class _FlatTrainer(object):
         dX = self._new(rows, n_in)
         self._gemm(dY, self.P[wk], dX, rows, n_in, n_out, n_out, n_in, n_in)
         return dX
+
+    # ---- the train-mode CNN: six conv -> BatchNorm -> ReLU -> pool -> Dropout2d layers ----------------------------------
+    def _init_cnn(self, geo, pad6, l1_fwd, l1_bwd):
+        """geo[i - 1]: conv i's output (H, W) and the pool after it; pad6: conv6's padding along W (conv1..5 pad 1); l1_fwd /
+        l1_bwd: the layer-1 entry points (nisqa_conv1_bn_act_pool_fwd / _bwd or a twin of theirs).  Reads the switches that
+        _choose_convs acts on: segment-resident split-bf16 / three-term / f16 convolutions (never for 'f32', whose
+        segment-resident kernels are exact fp32) and the BatchNorm backward folded into the weight gradient."""
+        self._geo, self._pad6, self._l1_fwd, self._l1_bwd = geo, pad6, l1_fwd, l1_bwd
+        self.segconv = os.environ.get('NISQA_HIP_TRAIN_SEGCONV', '1') != '0' and self.precision != 'f32'
+        self.fold_bn_wgrad = os.environ.get('NISQA_HIP_TRAIN_FOLD_BN_WGRAD', '1') != '0'
+        self._convs = None
+
+    def _choose_convs(self):
+        """The kernels of conv2..6, chosen once (at the first step, which allocates the weight fragments) from self.precision,
+        the switches of _init_cnn and nisqa_segconv_supported: self._convs[i] = (fwd, dgrad, wgrad, fold) --
+          fwd / dgrad  (entry, weight fragments) of a segment-resident convolution (csrc/train_conv.hip), or None: the implicit
+                       GEMM (nisqa_conv3x3_fwd_stats / self._conv_bwd);
+          wgrad        the segment-resident weight-gradient entry, or None: the implicit GEMM with split-K atomics;
+          fold         the BatchNorm / ReLU / pool / dropout backward runs inside wgrad (nisqa_bn_pool_bwd_sums in front).
+        self._packs: the launches that fill the fragments from the weights of a step (at most two: fp32, then 16-bit)."""
+        L, p = self.lib, self.precision
+        x6, h4 = p == 'bf16x6', p == 'f16x4'
+        frag_bytes, pack, conv = ((L.nisqa_segconv_frag_bytes_x6, L.nisqa_segconv_pack_x6_many, L.nisqa_segconv_bf16x6) if x6 else
+                                  (L.nisqa_segconv_frag_bytes_f16, L.nisqa_segconv_pack_f16_many, L.nisqa_segconv_f16) if h4 else
+                                  (L.nisqa_segconv_frag_bytes, L.nisqa_segconv_pack_many, L.nisqa_segconv_bf16))
+        wgrad_bn = (L.nisqa_segconv_wgrad_f32 if p == 'f32' else L.nisqa_segconv_wgrad_bf16x6 if x6 or h4 else
+                    L.nisqa_segconv_wgrad_bn_bf16)                    # the entries that can take the BatchNorm backward
+        wgrad_plain = L.nisqa_segconv_wgrad_bf16 if p in ('mixed', 'bf16x3') else wgrad_bn
+        self._gemm_split = 1 if p == 'bf16x3' else 0                 # nisqa_conv3x3_fwd_stats arithmetic
+        self._conv_bwd = L.nisqa_conv3x3_gemm if p in ('f32', 'bf16x6', 'f16x4') else L.nisqa_conv3x3_gemm_bf16
+        supported = [i for i in range(2, 7)
+                     if L.nisqa_segconv_supported(*self._geo[i - 2][2], *_CONV[i - 1], self._pad6 if i == 6 else 1)]
+        # exact fp32 fragments: forward of 'f32' and 'mixed', input gradient of 'f32'; 16-bit ones: forward of the other split
+        # modes, input gradient of all of them
+        self._sc32_frags, self._sc_frags, self._packs = {}, {}, []
+        for frags, fn, nbytes, dtype, modes in (
+                (self._sc32_frags, L.nisqa_segconv_pack_f32_many, L.nisqa_segconv_frag_bytes_f32, torch.float32,
+                 {'f32': (0, 1), 'mixed': (0,)}.get(p, ())),
+                (self._sc_frags, pack, frag_bytes, torch.int16, ((0, 1) if p != 'mixed' else (1,)) if self.segconv else ())):
+            jobs = []
+            for i in supported:
+                ci, co = _CONV[i - 1]
+                for mode in modes:
+                    frags[(mode, i)] = buf = self._new(nbytes(mode, ci, co) // (4 if dtype == torch.float32 else 2), dtype=dtype)
+                    jobs.append((mode, self.P['cnn.model.conv%d.weight' % i].data_ptr(), ci, co, buf.data_ptr()))
+            if jobs:
+                n = len(jobs)
+                self._packs.append((fn, n, [((ctypes.c_void_p if k in (1, 4) else ctypes.c_int32) * n)(*[j[k] for j in jobs])
+                                            for k in range(5)]))
+        self._convs = {}
+        for i in range(2, 7):
+            fwd, dgrad = [(conv, self._sc_frags[(m, i)]) if (m, i) in self._sc_frags else
+                          (L.nisqa_segconv_f32, self._sc32_frags[(m, i)]) if (m, i) in self._sc32_frags else None for m in (0, 1)]
+            fold = dgrad is not None and self.fold_bn_wgrad
+            self._convs[i] = (fwd, dgrad, None if dgrad is None else wgrad_bn if fold else wgrad_plain, fold)
+
+    def _pack_frags(self):
+        if self._convs is None:
+            self._choose_convs()
+        for fn, n, arrays in self._packs:
+            self._ck(fn(n, *arrays, self._st()), fn.__name__)
+
+    def _cnn_fwd(self, mel, frame_off, floor, masks, out6=None):
+        """The CNN in train mode from the [frames][48] spectrogram (BatchNorm on the batch statistics of the valid segments,
+        the buffers updated) -> (per-layer records for _cnn_bwd, conv6's pooled activation [S][pixels][64]); out6: the buffer
+        that activation goes to (default: a new one)."""
+        L_, P, B, S, st = self.lib, self.P, self.B, self.S, self._st()
+        self._pack_frags()
+        cnn, act = [], None
+        for i in range(1, 7):
+            ci, co = _CONV[i - 1]
+            h, w, (ho, wo) = self._geo[i - 1]
+            wk, bk = 'cnn.model.conv%d.weight' % i, 'cnn.model.conv%d.bias' % i
+            g, b_ = P['cnn.model.bn%d.weight' % i], P['cnn.model.bn%d.bias' % i]
+            drop = self._mask(masks, _DROP_AFTER[i], (S, co), self.p_cnn) if i in _DROP_AFTER else None
+            dp = _ptr(drop) if drop is not None else None
+            out = self._new(S, ho * wo, co) if i < 6 or out6 is None else out6.view(S, ho * wo, co)
+            arg = self._new(S, ho * wo, co, dtype=torch.int32)
+            mr = self._new(2 * co)
+            if i == 1:
+                # straight from the spectrogram: its activations are never written (csrc/train.hip, "Layer 1 without its
+                # activations"): patch moments -> batch statistics -> recomputed pooling windows
+                hop = int(self.args['ms_seg_hop_length'])
+                mom, sums = self._sum_rows()[:54], self._sum_rows()[:32]
+                self._ck(L_.nisqa_conv1_moments(_ptr(mel), _ptr(frame_off), _ptr(self.seg_off), _ptr(floor), B, S, hop,
+                                                mom.data_ptr(), st), 'nisqa_conv1_moments')
+                self._ck(self._l1_fwd(_ptr(mel), _ptr(frame_off), _ptr(self.seg_off), _ptr(floor), B, S, hop, _ptr(P[wk]),
+                                      _ptr(P[bk]), mom.data_ptr(), _ptr(g), _ptr(b_), _ptr(self.bn[1]['mean']),
+                                      _ptr(self.bn[1]['var']), sums.data_ptr(), _ptr(mr), dp, _ptr(out), arg.data_ptr(), st),
+                         self._l1_fwd.__name__)
+                cnn.append(dict(arg=arg, mr=mr, drop=drop, mom=mom, src=(mel, frame_off, floor, hop)))
+            else:
+                hi, wi = self._geo[i - 2][2]
+                pad = self._pad6 if i == 6 else 1
+                z = self._new(S * h * w, co)
+                sums = self._sum_rows()                                        # sum z, sum z^2 from the convolution's epilogue
+                fwd = self._convs[i][0]
+                if fwd is not None:
+                    self._ck(fwd[0](0, _ptr(act), _ptr(fwd[1]), _ptr(z), S, hi, wi, ci, co, pad, _ptr(P[bk]), sums.data_ptr(),
+                                    st), fwd[0].__name__)
+                else:                                                          # implicit GEMM: patches gathered by the loaders
+                    self._ck(L_.nisqa_conv3x3_fwd_stats(self._gemm_split, _ptr(act), _ptr(P[wk]), _ptr(z), S, hi, wi, ci, co, pad,
+                                                        _ptr(P[bk]), sums.data_ptr(), st), 'nisqa_conv3x3_fwd_stats')
+                self._ck(L_.nisqa_bn_act_pool_fwd(_ptr(z), sums.data_ptr(), _ptr(g), _ptr(b_), _ptr(self.bn[i]['mean']),
+                                                  _ptr(self.bn[i]['var']), _ptr(mr), S, h, w, co, ho, wo, dp, _ptr(out),
+                                                  arg.data_ptr(), st), 'nisqa_bn_act_pool_fwd')
+                cnn.append(dict(x=act, z=z, arg=arg, mr=mr, drop=drop))
+            self.bn[i]['n'] += 1
+            act = out
+        return cnn, act
+
+    def _cnn_bwd(self, cnn, box):
+        """Backward of _cnn_fwd from box = [d loss / d (its last activation)]: the gradients of conv1..6.weight and
+        bn1..6.weight / .bias.  The conv biases' gradients are exactly zero under train-mode BatchNorm and stay at the
+        cleared value.  The gradient comes in a list that is emptied here, so that it is freed once layer 6 has used it
+        (an argument would stay referenced by the caller until the call returns)."""
+        L_, P, G, B, S, st = self.lib, self.P, self.G, self.B, self.S, self._st()
+        da = box.pop()
+        for i in range(6, 1, -1):
+            c = cnn[i - 1]
+            ci, co = _CONV[i - 1]
+            h, w, (ho, wo) = self._geo[i - 1]
+            hi, wi = self._geo[i - 2][2]
+            pad = self._pad6 if i == 6 else 1
+            rows = S * h * w
+            wk = 'cnn.model.conv%d.weight' % i
+            g, b_ = P['cnn.model.bn%d.weight' % i], P['cnn.model.bn%d.bias' % i]
+            dg, db = G['cnn.model.bn%d.weight' % i], G['cnn.model.bn%d.bias' % i]
+            dp = _ptr(c['drop']) if c['drop'] is not None else None
+            _, dgrad, wgrad, fold = self._convs[i]
+            dz = self._new(rows, co)
+            s2 = self._sum_rows()
+            if fold:
+                # BatchNorm / ReLU / pool / dropout backward folded into the weight-gradient kernel's staging: the sums over the
+                # pooled values first, then the kernel computes dz on the fly (and writes it for the dgrad)
+                self._ck(L_.nisqa_bn_pool_bwd_sums(_ptr(da), c['arg'].data_ptr(), dp, _ptr(c['z']), _ptr(c['mr']), _ptr(g),
+                                                   _ptr(b_), S, h, w, co, ho, wo, s2.data_ptr(), st), 'nisqa_bn_pool_bwd_sums')
+                self._ck(wgrad(_ptr(c['x']), _ptr(c['z']), _ptr(da), c['arg'].data_ptr(), dp, _ptr(c['mr']), _ptr(g), _ptr(b_),
+                               s2.data_ptr(), _ptr(dz), _ptr(dg), _ptr(db), _ptr(G[wk]), S, hi, wi, ci, co, pad, ho, wo, st),
+                         wgrad.__name__)
+            else:
+                # reductions over the pooled values first, then ONE dense pass z -> dz (csrc/train.hip)
+                self._ck(L_.nisqa_bn_act_pool_bwd(_ptr(da), c['arg'].data_ptr(), dp, _ptr(c['z']), _ptr(c['mr']), _ptr(g),
+                                                  _ptr(b_), S, h, w, co, ho, wo, s2.data_ptr(), _ptr(dz), _ptr(dg), _ptr(db), st),
+                         'nisqa_bn_act_pool_bwd')
+                if wgrad is None:
+                    self._ck(self._conv_bwd(2, _ptr(c['x']), _ptr(dz), _ptr(G[wk]), S, hi, wi, ci, co, pad, None,
+                                            self._ksplit(rows, co, 9 * ci), st), 'nisqa_conv3x3_gemm wgrad')
+                elif wgrad is L_.nisqa_segconv_wgrad_bf16:                     # the one without BatchNorm operands
+                    self._ck(wgrad(_ptr(c['x']), _ptr(dz), _ptr(G[wk]), S, hi, wi, ci, co, pad, st), wgrad.__name__)
+                else:
+                    self._ck(wgrad(_ptr(c['x']), None, None, None, None, None, None, None, None, _ptr(dz), None, None, _ptr(G[wk]),
+                                   S, hi, wi, ci, co, pad, ho, wo, st), wgrad.__name__)
+            if self._debug is not None:                                        # tools/diag_cfg5.py: intermediates of the backward
+                self._debug['da%d' % i], self._debug['dz%d' % i], self._debug['z%d' % i] = da, dz, c['z']
+            da = self._new(S, hi * wi, ci)
+            if dgrad is not None:
+                self._ck(dgrad[0](1, _ptr(dz), _ptr(dgrad[1]), _ptr(da), S, hi, wi, ci, co, pad, None, None, st), dgrad[0].__name__)
+            else:
+                self._ck(self._conv_bwd(1, _ptr(dz), _ptr(P[wk]), _ptr(da), S, hi, wi, ci, co, pad, None, 1, st),
+                         'nisqa_conv3x3_gemm dgrad')
+            c['x'] = None
+        c = cnn[0]                                                             # layer 1: sparse sums + patch moments
+        mel, frame_off, floor, hop = c['src']
+        acc = self._sum_rows()[:176]
+        self._ck(self._l1_bwd(_ptr(mel), _ptr(frame_off), _ptr(self.seg_off), _ptr(floor), B, S, hop,
+                              _ptr(P['cnn.model.conv1.weight']), _ptr(P['cnn.model.conv1.bias']), c['mom'].data_ptr(),
+                              _ptr(P['cnn.model.bn1.weight']), _ptr(P['cnn.model.bn1.bias']), _ptr(c['mr']),
+                              _ptr(c['drop']) if c['drop'] is not None else None, _ptr(da), c['arg'].data_ptr(), acc.data_ptr(),
+                              _ptr(G['cnn.model.bn1.weight']), _ptr(G['cnn.model.bn1.bias']), _ptr(G['cnn.model.conv1.weight']),
+                              st), self._l1_bwd.__name__)
 
     def _finish_step(self, y_hat, loss):
         """End of a step: the deferred gradient casts, the data-parallel exchange (one all-reduce of the flat gradient buffer,
@@ -254,6 +477,7 @@ class _FlatTrainer(object):
 
 class HipTrainer(_FlatTrainer):
     LAYOUT = 'nisqa_amd flat buffer (HipTrainer.keys / kshape order)'
+    FEAT_W = 'time_dependency.model.linear.weight'
 
     def __init__(self, args, state_dict, device=None, lr=1e-3, precision=None):
         """precision of conv2..6 (everything else is fp32 in every mode); NISQA_HIP_TRAIN_PRECISION sets the default:
@@ -282,36 +506,9 @@ class HipTrainer(_FlatTrainer):
                                       'pool=att (config/train_nisqa_cnn_sa_ap.yaml)')
         self.eng = HipNisqa(args, state_dict, device, precision='f32')       # mel front end + geometry checks
         self.lib, self.device, self.args = self.eng.lib, self.eng.device, args
-        fast, exact = self.lib.nisqa_conv3x3_gemm_bf16, self.lib.nisqa_conv3x3_gemm
-        self.fused_l1 = os.environ.get('NISQA_HIP_TRAIN_FUSED_L1', '1') != '0'
-        self._kchunk = int(os.environ.get('NISQA_HIP_TRAIN_KCHUNK', '128'))
-        self.fused_bn_bwd = os.environ.get('NISQA_HIP_TRAIN_FUSED_BN_BWD', '1') != '0'
-        self.fused_fwd_stats = os.environ.get('NISQA_HIP_TRAIN_FUSED_FWD_STATS', '1') != '0'
-        self.fold_bn_wgrad = os.environ.get('NISQA_HIP_TRAIN_FOLD_BN_WGRAD', '1') != '0'
-        # precision 'f32': the weight gradients of layers 2..6 segment-resident on exact fp32 MFMA (csrc/train_conv.hip,
-        # nisqa_segconv_wgrad_f32) instead of the implicit GEMM with split-K atomics
-        self.segconv_f32 = os.environ.get('NISQA_HIP_TRAIN_SEGCONV_F32', '1') != '0' and self.precision == 'f32'
-        # ... and the fp32 FORWARD convolutions of 'f32' and 'mixed' / the fp32 input gradients of 'f32' segment-resident too
-        # (nisqa_segconv_f32) instead of the implicit GEMMs
-        self.segconv_f32_fwd = os.environ.get('NISQA_HIP_TRAIN_SEGCONV_F32_FWD', '1') != '0' and self.precision in ('f32', 'mixed')
-        self._sc32_frags, self._sc32_bufs = {}, {}
-        self._conv_fwd = fast if self.precision == 'bf16x3' else exact
-        self._conv_bwd = exact if self.precision in ('f32', 'bf16x6', 'f16x4') else fast     # (layer shapes train_conv.hip does not instantiate)
-        # 'bf16x6' walks the control flow of 'bf16x3' -- segment-resident kernels on uint16 fragments for forward, dgrad and wgrad --
-        # through the three-term entry points
-        # 'f16x4' (round 5): the control flow of 'bf16x6' with the forward and input-gradient convolutions on two f16 terms of the
-        # per-group scaled tensors and all four products (nisqa_segconv_f16); the weight gradients stay on the three-term kernels
-        x6, h4 = self.precision == 'bf16x6', self.precision == 'f16x4'
-        self._sc_frag_bytes = self.lib.nisqa_segconv_frag_bytes_x6 if x6 else self.lib.nisqa_segconv_frag_bytes_f16 if h4 else self.lib.nisqa_segconv_frag_bytes
-        self._sc_pack_many = self.lib.nisqa_segconv_pack_x6_many if x6 else self.lib.nisqa_segconv_pack_f16_many if h4 else self.lib.nisqa_segconv_pack_many
-        self._sc_conv = self.lib.nisqa_segconv_bf16x6 if x6 else self.lib.nisqa_segconv_f16 if h4 else self.lib.nisqa_segconv_bf16
-        # split-bf16 forward / input-gradient convolutions segment-resident (csrc/train_conv.hip) where the layer shape is
-        # one of the reference configuration's; weight fragments are packed once per step (_segconv_pack)
-        self.segconv = os.environ.get('NISQA_HIP_TRAIN_SEGCONV', '1') != '0' and self.precision != 'f32'
         # self-attention block + pooling heads + loss, forward and backward, as one C call of a dozen launches (csrc/train_td.hip)
         self.fused_td = os.environ.get('NISQA_HIP_TRAIN_FUSED_TD', '1') != '0'
         self._td_ws = self._td_frags = None
-        self._sc_frags, self._sc_bufs = {}, {}
         self._prep_key = None
         self.lr = float(lr)
         self.n_layers = int(a['td_sa_num_layers'])
@@ -320,19 +517,14 @@ class HipTrainer(_FlatTrainer):
             # csrc/train_td.hip is laid out for TDT_MAX_LAYERS = 4 / TDT_MAX_HEADS = 8 (the reference configurations use 2 / 5);
             # deeper stacks take the operator-by-operator path, which has no such limit
             self.fused_td = False
-        self.pools = [tuple(a['cnn_pool_1']), tuple(a['cnn_pool_2']), tuple(a['cnn_pool_3'])]
+        pools = [tuple(a['cnn_pool_1']), tuple(a['cnn_pool_2']), tuple(a['cnn_pool_3'])]
         self.p_cnn, self.p_td, self.p_pool = float(a['cnn_dropout']), float(a['td_sa_dropout']), float(a['pool_att_dropout'] or 0)
         if self.p_pool:
             raise NotImplementedError('pool_att_dropout > 0 is not built (0 in every shipped config)')
-        self.t = 0
-        self._layout(state_dict)
+        self._init_params(state_dict, 96 + 24 * len(self.heads))
         self._td_poff = self._td_param_offsets()
-        self.load_state_dict(state_dict)
-        self.m = torch.zeros_like(self.flat)
-        self.v = torch.zeros_like(self.flat)
-        self._sums = torch.zeros((96 + 24 * len(self.heads), 512), dtype=torch.float64, device=self.device)
-        self._cast_table, self._cast_key = None, None
-        self._rng_seed, self._rng_off = int(torch.initial_seed()) & (2 ** 64 - 1), 0     # torch.manual_seed governs the masks
+        geo = [(48, 15, pools[0]), (24, 7, pools[1]), (12, 5, (12, 5)), (12, 5, pools[2]), (6, 3, (6, 3)), (6, 1, (6, 1))]
+        self._init_cnn(geo, 0, self.lib.nisqa_conv1_bn_act_pool_fwd, self.lib.nisqa_conv1_bn_act_pool_bwd)
         self._debug = {} if os.environ.get('NISQA_HIP_TRAIN_DEBUG') == '1' else None
 
     # ---- parameters ------------------------------------------------------------------------------------
@@ -350,71 +542,7 @@ class HipTrainer(_FlatTrainer):
                      hp + 'linear3.bias']
         return np.array([self.off[k] for k in keys], dtype=np.int32)
 
-    @staticmethod
-    def _to_kernel(k, v):
-        if k.startswith('cnn.model.conv') and k.endswith('.weight'):
-            return v.permute(0, 2, 3, 1).reshape(v.shape[0], -1)
-        if k == 'time_dependency.model.linear.weight':                         # columns c*6+y -> y*64+c
-            return v.reshape(v.shape[0], 64, 6).permute(0, 2, 1).reshape(v.shape[0], 384)
-        return v
-
-    @staticmethod
-    def _from_kernel(k, v, ref_shape):
-        if k.startswith('cnn.model.conv') and k.endswith('.weight'):
-            co, ci = ref_shape[0], ref_shape[1]
-            return v.reshape(co, 3, 3, ci).permute(0, 3, 1, 2)
-        if k == 'time_dependency.model.linear.weight':
-            return v.reshape(v.shape[0], 6, 64).permute(0, 2, 1).reshape(v.shape[0], 384)
-        return v
-
     # ---- thin wrappers over the C ABI ------------------------------------------------------------------------
-    def _segconv_pack(self, geo):
-        """Weight fragments of this step for every layer / direction csrc/train_conv.hip takes (mode 0 forward -- 'bf16x3'
-        only --, mode 1 input gradient): ONE launch (nisqa_segconv_pack_many).  self._sc_frags[(mode, i)] is absent where the
-        layer shape is not instantiated; the implicit GEMM stays there."""
-        self._sc_frags, self._sc32_frags = {}, {}
-        if self.segconv_f32_fwd:                                # fp32 fragments: forward ('f32', 'mixed'), input gradient ('f32')
-            jobs = []
-            for i in range(2, 7):
-                ci, co = _CONV[i - 1]
-                hi, wi = geo[i - 2][2]
-                if not self.lib.nisqa_segconv_supported(hi, wi, ci, co, 0 if i == 6 else 1):
-                    continue
-                for mode in ((0, 1) if self.precision == 'f32' else (0,)):
-                    buf = self._sc32_bufs.get((mode, i))
-                    if buf is None:
-                        buf = self._sc32_bufs[(mode, i)] = torch.empty(self.lib.nisqa_segconv_frag_bytes_f32(mode, ci, co) // 4,
-                                                                       dtype=torch.float32, device=self.device)
-                    jobs.append((mode, self.P['cnn.model.conv%d.weight' % i].data_ptr(), ci, co, buf.data_ptr()))
-                    self._sc32_frags[(mode, i)] = buf
-            if jobs:
-                n = len(jobs)
-                arr_i = lambda k: (ctypes.c_int32 * n)(*[j[k] for j in jobs])
-                arr_p = lambda k: (ctypes.c_void_p * n)(*[j[k] for j in jobs])
-                self._ck(self.lib.nisqa_segconv_pack_f32_many(n, arr_i(0), arr_p(1), arr_i(2), arr_i(3), arr_p(4), self._st()),
-                         'nisqa_segconv_pack_f32_many')
-        if not self.segconv:
-            return
-        jobs = []
-        for i in range(2, 7):
-            ci, co = _CONV[i - 1]
-            hi, wi = geo[i - 2][2]
-            if not self.lib.nisqa_segconv_supported(hi, wi, ci, co, 0 if i == 6 else 1):
-                continue
-            for mode in ((0, 1) if self.precision in ('bf16x3', 'bf16x6', 'f16x4') else (1,)):
-                buf = self._sc_bufs.get((mode, i))
-                if buf is None:
-                    buf = self._sc_bufs[(mode, i)] = torch.empty(self._sc_frag_bytes(mode, ci, co) // 2,
-                                                                 dtype=torch.int16, device=self.device)
-                jobs.append((mode, self.P['cnn.model.conv%d.weight' % i].data_ptr(), ci, co, buf.data_ptr()))
-                self._sc_frags[(mode, i)] = buf
-        if jobs:
-            n = len(jobs)
-            arr_i = lambda k: (ctypes.c_int32 * n)(*[j[k] for j in jobs])
-            arr_p = lambda k: (ctypes.c_void_p * n)(*[j[k] for j in jobs])
-            self._ck(self._sc_pack_many(n, arr_i(0), arr_p(1), arr_i(2), arr_i(3), arr_p(4), self._st()),
-                     'nisqa_segconv_pack_many')
-
     def _ggemm(self, kind, A, B, C, ta=0, tb=0, ao=0, bo=0, co=0):
         d, tiles = self._desc[kind]
         self._ck(self.lib.nisqa_gemm_f32(_ptr(A, ao), _ptr(B, bo), _ptr(C, co), d.data_ptr(), d.shape[0], tiles, ta, tb, 1,
@@ -456,7 +584,7 @@ class HipTrainer(_FlatTrainer):
         # pageable .to(device) calls each blocked the host behind everything queued on the stream -- and kept while the
         # batch's segment counts repeat
         key = L.tobytes()
-        if key != self._prep_key or os.environ.get('NISQA_HIP_TRAIN_NO_PREP_CACHE') == '1':     # (the switch: timing of the rebuild)
+        if key != self._prep_key:
             parts, tiles = step_tables(L)
             td_plan = None
             if self.fused_td:
@@ -707,223 +835,21 @@ class HipTrainer(_FlatTrainer):
         return y_hat, loss, da
 
     def _step(self, mel, frame_off, n_wins, floor, y, masks, bias):
-        L_ = self.lib
         self._prepare(n_wins)
-        B, S, st = self.B, self.S, self._st()
-        hop = int(self.args['ms_seg_hop_length'])
         self.gflat.zero_()
-        # labels (and bias coefficients) through page-locked memory: a pageable .to(device) blocks the host until the
-        # previous step has drained, and the GPU then idles while this step's first launches are being issued
-        def up(a, cols):
-            a = np.ascontiguousarray(np.asarray(a, np.float32).reshape(B, cols))
-            if self.device.type != 'cuda':
-                return torch.from_numpy(a).to(self.device)
-            h = torch.empty(a.shape, dtype=torch.float32, pin_memory=True)     # caching host allocator: reuse is stream-safe
-            h.numpy()[...] = a
-            return h.to(self.device, non_blocking=True)
-        y_dev = bias_dev = None
+        y_dev = bias_dev = feat_out = None
         if not self.fused_td:
-            y_dev = up(y, len(self.heads))
-            bias_dev = None if bias is None else up(bias, 4)
-        else:
+            y_dev = self._upload(y, len(self.heads))
+            bias_dev = None if bias is None else self._upload(bias, 4)
+        else:                                               # the CNN writes its features straight into the fused block's workspace
             pl = self._td_buffers()
-
-        # ================= forward: AdaptCNN in train mode =================
-        geo = [(48, 15, self.pools[0]), (24, 7, self.pools[1]), (12, 5, (12, 5)), (12, 5, self.pools[2]), (6, 3, (6, 3)),
-               (6, 1, (6, 1))]                                               # conv output (H, W) and the pool after it
-        self._segconv_pack(geo)
-        cnn = []
-        act = None
-        for i in range(1, 7):
-            ci, co = _CONV[i - 1]
-            h, w, (ho, wo) = geo[i - 1]
-            rows = S * h * w
-            wk, bk = 'cnn.model.conv%d.weight' % i, 'cnn.model.conv%d.bias' % i
-            drop = self._mask(masks, _DROP_AFTER.get(i), (S, co), self.p_cnn) if i in _DROP_AFTER else None
-            if i == 6 and self.fused_td:                  # the features go straight into the fused block's workspace
-                out = self._td_ws[pl['feat']:pl['feat'] + S * ho * wo * co].view(S, ho * wo, co)
-            else:
-                out = self._new(S, ho * wo, co)
-            arg = self._new(S, ho * wo, co, dtype=torch.int32)
-            mr = self._new(2 * co)
-            if i == 1 and self.fused_l1:
-                # layer 1 straight from the spectrogram: its 720-pixel activations are never written (csrc/train.hip,
-                # "Layer 1 without its activations"): patch moments -> batch statistics -> recomputed pooling windows
-                mom = self._sums[self._sum_i][:54]
-                sums = self._sums[self._sum_i + 1][:32]
-                self._sum_i += 2
-                self._ck(L_.nisqa_conv1_moments(_ptr(mel), _ptr(frame_off), _ptr(self.seg_off), _ptr(floor), B, S, hop,
-                                                mom.data_ptr(), st), 'nisqa_conv1_moments')
-                self._ck(L_.nisqa_conv1_bn_act_pool_fwd(_ptr(mel), _ptr(frame_off), _ptr(self.seg_off), _ptr(floor), B, S, hop,
-                                                        _ptr(self.P[wk]), _ptr(self.P[bk]), mom.data_ptr(),
-                                                        _ptr(self.P['cnn.model.bn1.weight']), _ptr(self.P['cnn.model.bn1.bias']),
-                                                        _ptr(self.bn[1]['mean']), _ptr(self.bn[1]['var']), sums.data_ptr(), _ptr(mr),
-                                                        _ptr(drop) if drop is not None else None, _ptr(out), arg.data_ptr(), st),
-                         'nisqa_conv1_bn_act_pool_fwd')
-                self.bn[i]['n'] += 1
-                cnn.append(dict(x=None, z=None, arg=arg, mr=mr, drop=drop, h=h, w=w, ho=ho, wo=wo, ci=ci, co=co, rows=rows, mom=mom))
-                act = out
-                continue
-            z = self._new(rows, co)
-            if i == 1:                                                         # straight from the spectrogram, no patches
-                self._ck(L_.nisqa_conv1_fwd(_ptr(mel), _ptr(frame_off), _ptr(self.seg_off), _ptr(floor), B, S, hop,
-                                            _ptr(self.P[wk]), _ptr(self.P[bk]), _ptr(z), st), 'nisqa_conv1_fwd')
-            else:                                                              # implicit GEMM: patches gathered by the loaders
-                hi, wi = geo[i - 2][2]
-                fr = self._sc_frags.get((0, i))
-                fr32 = self._sc32_frags.get((0, i))
-                if fr is None and fr32 is not None:                              # exact fp32, segment-resident
-                    sums = None
-                    if self.fused_fwd_stats:
-                        sums = self._sums[self._sum_i]
-                        self._sum_i += 1
-                    self._ck(L_.nisqa_segconv_f32(0, _ptr(act), _ptr(fr32), _ptr(z), S, hi, wi, ci, co, 0 if i == 6 else 1,
-                                                  _ptr(self.P[bk]), sums.data_ptr() if sums is not None else None, st),
-                             'nisqa_segconv_f32 fwd')
-                elif fr is not None:
-                    sums = None
-                    if self.fused_fwd_stats:
-                        sums = self._sums[self._sum_i]
-                        self._sum_i += 1
-                    self._ck(self._sc_conv(0, _ptr(act), fr.data_ptr(), _ptr(z), S, hi, wi, ci, co, 0 if i == 6 else 1,
-                                                   _ptr(self.P[bk]), sums.data_ptr() if sums is not None else None, st),
-                             'nisqa_segconv_bf16 fwd')
-                elif self.fused_fwd_stats:                                     # sum z, sum z^2 from the convolution's epilogue
-                    sums = self._sums[self._sum_i]
-                    self._sum_i += 1
-                    self._ck(L_.nisqa_conv3x3_fwd_stats(1 if self.precision == 'bf16x3' else 0, _ptr(act), _ptr(self.P[wk]), _ptr(z),
-                                                        S, hi, wi, ci, co, 0 if i == 6 else 1, _ptr(self.P[bk]), sums.data_ptr(),
-                                                        st), 'nisqa_conv3x3_fwd_stats')
-                else:
-                    self._ck(self._conv_fwd(0, _ptr(act), _ptr(self.P[wk]), _ptr(z), S, hi, wi, ci, co, 0 if i == 6 else 1,
-                                            _ptr(self.P[bk]), 1, st), 'nisqa_conv3x3_gemm fwd')
-            if i == 1 or not self.fused_fwd_stats:
-                sums = self._coldot(z, z, rows, co)
-            self._ck(L_.nisqa_bn_act_pool_fwd(_ptr(z), sums.data_ptr(), _ptr(self.P['cnn.model.bn%d.weight' % i]),
-                                              _ptr(self.P['cnn.model.bn%d.bias' % i]), _ptr(self.bn[i]['mean']),
-                                              _ptr(self.bn[i]['var']), _ptr(mr), S, h, w, co, ho, wo,
-                                              _ptr(drop) if drop is not None else None, _ptr(out), arg.data_ptr(), st),
-                     'nisqa_bn_act_pool_fwd')
-            self.bn[i]['n'] += 1
-            cnn.append(dict(x=act, z=z, arg=arg, mr=mr, drop=drop, h=h, w=w, ho=ho, wo=wo, ci=ci, co=co, rows=rows))
-            act = out
-        feat = act                                                             # [S][6][64] = [S][384] in (y, c) order
-
+            feat_out = self._td_ws[pl['feat']:pl['feat'] + self.S * 384]
+        cnn, feat = self._cnn_fwd(mel, frame_off, floor, masks, feat_out)     # [S][6][64] = [S][384] in (y, c) order
         # ================= self-attention block, pooling heads, loss: forward and backward =================
         if self.fused_td:
             y_hat, loss, da = self._td_fused(y, bias, masks)
         else:
             y_hat, loss, da = self._td_unfused(feat, y, y_dev, bias_dev, masks)
-
-        # ================= backward: AdaptCNN =================
-        for i in range(6, 0, -1):
-            c = cnn[i - 1]
-            rows, co, ci = c['rows'], c['co'], c['ci']
-            g, b_ = self.P['cnn.model.bn%d.weight' % i], self.P['cnn.model.bn%d.bias' % i]
-            if i == 1 and c['z'] is None:                                      # fused layer 1: sparse sums + patch moments
-                acc = self._sums[self._sum_i][:176]
-                self._sum_i += 1
-                self._ck(L_.nisqa_conv1_bn_act_pool_bwd(_ptr(mel), _ptr(frame_off), _ptr(self.seg_off), _ptr(floor), B, S, hop,
-                                                        _ptr(self.P['cnn.model.conv1.weight']), _ptr(self.P['cnn.model.conv1.bias']),
-                                                        c['mom'].data_ptr(), _ptr(g), _ptr(b_), _ptr(c['mr']),
-                                                        _ptr(c['drop']) if c['drop'] is not None else None, _ptr(da),
-                                                        c['arg'].data_ptr(), acc.data_ptr(), _ptr(self.G['cnn.model.bn1.weight']),
-                                                        _ptr(self.G['cnn.model.bn1.bias']), _ptr(self.G['cnn.model.conv1.weight']),
-                                                        st), 'nisqa_conv1_bn_act_pool_bwd')
-                continue                                                       # conv1.bias: exactly zero (gflat was cleared)
-            dz = self._new(rows, co)
-            wk, bk = 'cnn.model.conv%d.weight' % i, 'cnn.model.conv%d.bias' % i
-            fold = self.fused_bn_bwd and self.fold_bn_wgrad and i > 1 and (1, i) in self._sc_frags
-            seg32 = self.segconv_f32 and i > 1 and bool(L_.nisqa_segconv_supported(geo[i - 2][2][0], geo[i - 2][2][1], ci, co, 0 if i == 6 else 1))
-            fold32 = seg32 and self.fused_bn_bwd and self.fold_bn_wgrad
-            if fold32:
-                hi, wi = geo[i - 2][2]
-                s2 = self._sums[self._sum_i]
-                self._sum_i += 1
-                dp = _ptr(c['drop']) if c['drop'] is not None else None
-                self._ck(L_.nisqa_bn_pool_bwd_sums(_ptr(da), c['arg'].data_ptr(), dp, _ptr(c['z']), _ptr(c['mr']), _ptr(g), _ptr(b_), S,
-                                                   c['h'], c['w'], co, c['ho'], c['wo'], s2.data_ptr(), st), 'nisqa_bn_pool_bwd_sums')
-                self._ck(L_.nisqa_segconv_wgrad_f32(_ptr(c['x']), _ptr(c['z']), _ptr(da), c['arg'].data_ptr(), dp, _ptr(c['mr']),
-                                                    _ptr(g), _ptr(b_), s2.data_ptr(), _ptr(dz),
-                                                    _ptr(self.G['cnn.model.bn%d.weight' % i]), _ptr(self.G['cnn.model.bn%d.bias' % i]),
-                                                    _ptr(self.G[wk]), S, hi, wi, ci, co, 0 if i == 6 else 1, c['ho'], c['wo'], st),
-                         'nisqa_segconv_wgrad_f32 (BatchNorm backward inside)')
-                sb = None
-            elif fold:
-                # BatchNorm / ReLU / pool / dropout backward folded into the weight-gradient kernel's staging: the sums over the
-                # pooled values first, then nisqa_segconv_wgrad_bn_bf16 computes dz on the fly (and writes it for the dgrad)
-                hi, wi = geo[i - 2][2]
-                s2 = self._sums[self._sum_i]
-                self._sum_i += 1
-                dp = _ptr(c['drop']) if c['drop'] is not None else None
-                self._ck(L_.nisqa_bn_pool_bwd_sums(_ptr(da), c['arg'].data_ptr(), dp, _ptr(c['z']), _ptr(c['mr']), _ptr(g), _ptr(b_), S,
-                                                   c['h'], c['w'], co, c['ho'], c['wo'], s2.data_ptr(), st), 'nisqa_bn_pool_bwd_sums')
-                self._ck((L_.nisqa_segconv_wgrad_bf16x6 if self.precision in ('bf16x6', 'f16x4') else L_.nisqa_segconv_wgrad_bn_bf16)(
-                    _ptr(c['x']), _ptr(c['z']), _ptr(da), c['arg'].data_ptr(), dp, _ptr(c['mr']),
-                                                        _ptr(g), _ptr(b_), s2.data_ptr(), _ptr(dz),
-                                                        _ptr(self.G['cnn.model.bn%d.weight' % i]), _ptr(self.G['cnn.model.bn%d.bias' % i]),
-                                                        _ptr(self.G[wk]), S, hi, wi, ci, co, 0 if i == 6 else 1, c['ho'], c['wo'], st),
-                         'nisqa_segconv_wgrad_bn_bf16')
-                sb = None
-            elif self.fused_bn_bwd:
-                # reductions over the pooled values first, then ONE dense pass z -> dz (csrc/train.hip); the conv bias
-                # gradient (column sums of dz) is exactly zero under train-mode BatchNorm and stays at the cleared value
-                s2 = self._sums[self._sum_i]
-                self._sum_i += 1
-                self._ck(L_.nisqa_bn_act_pool_bwd(_ptr(da), c['arg'].data_ptr(), _ptr(c['drop']) if c['drop'] is not None else None,
-                                                  _ptr(c['z']), _ptr(c['mr']), _ptr(g), _ptr(b_), S, c['h'], c['w'], co, c['ho'],
-                                                  c['wo'], s2.data_ptr(), _ptr(dz), _ptr(self.G['cnn.model.bn%d.weight' % i]),
-                                                  _ptr(self.G['cnn.model.bn%d.bias' % i]), st), 'nisqa_bn_act_pool_bwd')
-                sb = None
-            else:
-                s2 = self._sums[self._sum_i]
-                sb = self._sums[self._sum_i + 1]
-                self._sum_i += 2
-                self._ck(L_.nisqa_bn_act_pool_bwd1(_ptr(da), c['arg'].data_ptr(), _ptr(c['drop']) if c['drop'] is not None else None,
-                                                   _ptr(c['z']), _ptr(c['mr']), _ptr(g), _ptr(b_), S, c['h'], c['w'], co, c['ho'],
-                                                   c['wo'], _ptr(dz), s2.data_ptr(), st), 'nisqa_bn_act_pool_bwd1')
-                self._ck(L_.nisqa_bn_bwd2(_ptr(dz), _ptr(c['z']), s2.data_ptr(), _ptr(c['mr']), _ptr(g), rows, co,
-                                          _ptr(self.G['cnn.model.bn%d.weight' % i]), _ptr(self.G['cnn.model.bn%d.bias' % i]),
-                                          sb.data_ptr(), st), 'nisqa_bn_bwd2')
-            wk, bk = 'cnn.model.conv%d.weight' % i, 'cnn.model.conv%d.bias' % i
-            if self._debug is not None:                                      # tools/diag_cfg5.py: intermediates of the backward pass
-                self._debug['da%d' % i], self._debug['dz%d' % i], self._debug['z%d' % i] = da, dz, c['z']
-            if sb is not None:
-                self._defer_cast(sb, 0, co, self.G[bk])
-            if i == 1:
-                self._ck(L_.nisqa_conv1_wgrad(_ptr(mel), _ptr(frame_off), _ptr(self.seg_off), _ptr(floor), B, S, hop, _ptr(dz),
-                                              _ptr(self.G[wk]), st), 'nisqa_conv1_wgrad')
-            else:
-                hi, wi = geo[i - 2][2]
-                pad = 0 if i == 6 else 1
-                if fold or fold32:
-                    pass                                                       # the weight gradient ran with the BatchNorm backward
-                elif seg32:
-                    self._ck(L_.nisqa_segconv_wgrad_f32(_ptr(c['x']), None, None, None, None, None, None, None, None, _ptr(dz), None, None,
-                                                        _ptr(self.G[wk]), S, hi, wi, ci, co, pad, c['ho'], c['wo'], st),
-                             'nisqa_segconv_wgrad_f32')
-                elif (1, i) in self._sc_frags and self.precision in ('bf16x6', 'f16x4'):
-                    self._ck(L_.nisqa_segconv_wgrad_bf16x6(_ptr(c['x']), None, None, None, None, None, None, None, None, _ptr(dz), None, None,
-                                                           _ptr(self.G[wk]), S, hi, wi, ci, co, pad, c['ho'], c['wo'], st),
-                             'nisqa_segconv_wgrad_bf16x6')
-                elif (1, i) in self._sc_frags:
-                    self._ck(L_.nisqa_segconv_wgrad_bf16(_ptr(c['x']), _ptr(dz), _ptr(self.G[wk]), S, hi, wi, ci, co, pad, st),
-                             'nisqa_segconv_wgrad_bf16')
-                else:
-                    self._ck(self._conv_bwd(2, _ptr(c['x']), _ptr(dz), _ptr(self.G[wk]), S, hi, wi, ci, co, pad, None,
-                                            self._ksplit(rows, co, 9 * ci), st), 'nisqa_conv3x3_gemm wgrad')
-                da = self._new(S, hi * wi, ci)
-                fr = self._sc_frags.get((1, i))
-                fr32 = self._sc32_frags.get((1, i))
-                if fr is None and fr32 is not None:
-                    self._ck(L_.nisqa_segconv_f32(1, _ptr(dz), _ptr(fr32), _ptr(da), S, hi, wi, ci, co, pad, None, None, st),
-                             'nisqa_segconv_f32 dgrad')
-                elif fr is not None:
-                    self._ck(self._sc_conv(1, _ptr(dz), fr.data_ptr(), _ptr(da), S, hi, wi, ci, co, pad, None, None, st),
-                             'nisqa_segconv_bf16 dgrad')
-                else:
-                    self._ck(self._conv_bwd(1, _ptr(dz), _ptr(self.P[wk]), _ptr(da), S, hi, wi, ci, co, pad, None, 1, st),
-                             'nisqa_conv3x3_gemm dgrad')
-            c['x'] = None
-
+        da = [da]
+        self._cnn_bwd(cnn, da)
         return self._finish_step(y_hat, loss)

@@ -5,9 +5,11 @@ What the reference does per batch at nisqa/NISQA_model.py:131-152 for ``model`` 
 StandardCNN in train mode (NISQA_lib.py:712-836: batch-statistics BatchNorm over the valid segments, ReLU, pool_first =
 MaxPool2d(2, 2, padding (0, 1)), 2 x 2 pools, Dropout2d at four sites, fc_out 768 -> 20), the BiLSTM over each clip's n_wins
 segments (NL:897-943), PoolLastStepBi / PoolAvg / PoolMax and the linear layer (NL:1099-1115, 1185-1224), biasLoss.get_loss,
-backward and Adam -- with every operator a HIP kernel:
+backward and Adam -- with every operator a HIP kernel; the CNN runs through train._FlatTrainer's loop (_cnn_fwd / _cnn_bwd)
+with the geometry GEO, conv6 padded like conv1..5 and the _std_ layer-1 entry points:
   * layer 1: nisqa_conv1_moments + nisqa_conv1_bn_act_pool_std_fwd / _bwd (conv1 from the spectrogram, never written);
-  * layers 2..6: nisqa_conv3x3_fwd_stats / nisqa_conv3x3_gemm (exact fp32 MFMA, padding (1, 1)) and nisqa_bn_act_pool_fwd /
+  * layers 2..6: nisqa_conv3x3_fwd_stats / nisqa_conv3x3_gemm (exact fp32 MFMA, padding (1, 1): what the loop picks for 'f32'
+    at shapes nisqa_segconv_supported refuses) and nisqa_bn_act_pool_fwd /
     nisqa_bn_act_pool_bwd (2 x 2 pools after conv2 and conv4: the adaptive windows of 24 x 8 -> 12 x 4 and 12 x 4 -> 6 x 2 are
     exactly the 2 x 2 windows, tests/test_gpu_train_lstm.py);
   * fc_out, the pooling's linear layer and every weight / input gradient of the LSTM: nisqa_gemm_f32_one;
@@ -27,10 +29,8 @@ import torch
 
 from . import dist as _dist
 from .engine import HipNisqa, check_lstm_args, LSTM_POOL_MODE
-from .train import _FlatTrainer, _ptr
+from .train import _FlatTrainer, _BN_BUFFERS, _ptr, feat_to_kernel, feat_from_kernel
 
-_CONV = [(1, 16), (16, 32), (32, 64), (64, 64), (64, 64), (64, 64)]      # (C_in, C_out) of conv1..conv6
-_DROP_AFTER = {2: 'cnn_d1', 3: 'cnn_d2', 4: 'cnn_d3', 5: 'cnn_d4'}       # Dropout2d sites (NISQA_lib.py:820-828)
 # conv output (H, W) and the pool after it: pool_first 48 x 15 -> 24 x 8, pool after conv2 and conv4, identity elsewhere
 GEO = [(48, 15, (24, 8)), (24, 8, (12, 4)), (12, 4, (12, 4)), (12, 4, (6, 2)), (6, 2, (6, 2)), (6, 2, (6, 2))]
 LSTM_PFX = 'time_dependency.model.lstm.'
@@ -40,13 +40,8 @@ POOL_KEYS = ['pool.model.linear.weight', 'pool.model.linear.bias']
 FC_W = 'cnn.model.fc_out.weight'
 
 
-def fc_to_kernel(w):
-    """fc_out.weight [20][768] with columns c * 12 + pixel (the reference's flatten of [64][6][2]) -> columns pixel * 64 + c"""
-    return w.reshape(w.shape[0], 64, 12).permute(0, 2, 1).reshape(w.shape[0], 768)
-
-
-def fc_from_kernel(w):
-    return w.reshape(w.shape[0], 12, 64).permute(0, 2, 1).reshape(w.shape[0], 768)
+# fc_out.weight [20][768]: columns c * 12 + pixel (the reference's flatten of [64][6][2]) <-> columns pixel * 64 + c
+fc_to_kernel, fc_from_kernel = feat_to_kernel, feat_from_kernel
 
 
 def check_train_lstm_args(args, precision=None):
@@ -64,6 +59,7 @@ def check_train_lstm_args(args, precision=None):
 
 class HipTrainerLSTM(_FlatTrainer):
     LAYOUT = 'nisqa_amd flat buffer (HipTrainerLSTM.keys / kshape order)'
+    FEAT_W = FC_W
 
     def __init__(self, args, state_dict, device=None, lr=1e-3, precision=None):
         """args / state_dict: a NISQA model with cnn_model=standard, td=lstm (engine.check_lstm_args); precision: 'f32' only."""
@@ -76,45 +72,20 @@ class HipTrainerLSTM(_FlatTrainer):
         self.lib, self.device, self.args = self.eng.lib, self.eng.device, args
         self.lr = float(lr)
         self.p_cnn, self.p_td = float(args.get('cnn_dropout') or 0.0), 0.0
-        self._kchunk = int(os.environ.get('NISQA_HIP_TRAIN_KCHUNK', '128'))      # split-K chunk of the weight gradients
-        self.t = 0
-        self._layout(state_dict)
+        self._init_params(state_dict, 24)
         for a_, b_ in zip(LSTM_KEYS[0::2], LSTM_KEYS[1::2]):       # both directions back to back: one pointer per tensor kind
             assert self.off[b_] == self.off[a_] + int(np.prod(self.kshape[a_])), 'LSTM directions must be adjacent'
-        self.load_state_dict(state_dict)
-        self.m = torch.zeros_like(self.flat)
-        self.v = torch.zeros_like(self.flat)
-        self._sums = torch.zeros((24, 512), dtype=torch.float64, device=self.device)
-        self._cast_table, self._cast_key = None, None
-        self._rng_seed, self._rng_off = int(torch.initial_seed()) & (2 ** 64 - 1), 0     # torch.manual_seed governs the masks
+        self._init_cnn(GEO, 1, self.lib.nisqa_conv1_bn_act_pool_std_fwd, self.lib.nisqa_conv1_bn_act_pool_std_bwd)
         self._prep_key = None
 
     # ---- parameters ------------------------------------------------------------------------------------
     def _param_order(self, sd):
-        cnn = [k for k in sd if k.startswith('cnn.model.') and k.split('.')[-1] not in ('running_mean', 'running_var',
-                                                                                         'num_batches_tracked')]
+        cnn = [k for k in sd if k.startswith('cnn.model.') and k.split('.')[-1] not in _BN_BUFFERS]
         keys = cnn + LSTM_KEYS + POOL_KEYS
-        extra = [k for k in sd if k not in keys and k.split('.')[-1] not in ('running_mean', 'running_var', 'num_batches_tracked')]
+        extra = [k for k in sd if k not in keys and k.split('.')[-1] not in _BN_BUFFERS]
         if extra:
             raise NotImplementedError('HIP LSTM training step: unexpected parameters {}'.format(extra))
         return keys
-
-    @staticmethod
-    def _to_kernel(k, v):
-        if k.startswith('cnn.model.conv') and k.endswith('.weight'):
-            return v.permute(0, 2, 3, 1).reshape(v.shape[0], -1)
-        if k == FC_W:
-            return fc_to_kernel(v)
-        return v
-
-    @staticmethod
-    def _from_kernel(k, v, ref_shape):
-        if k.startswith('cnn.model.conv') and k.endswith('.weight'):
-            co, ci = ref_shape[0], ref_shape[1]
-            return v.reshape(co, 3, 3, ci).permute(0, 3, 1, 2)
-        if k == FC_W:
-            return fc_from_kernel(v)
-        return v
 
     # ---- batch bookkeeping ---------------------------------------------------------------------------------
     def _prepare(self, n_wins):
@@ -136,66 +107,16 @@ class HipTrainerLSTM(_FlatTrainer):
             o += (self.S * c + 3) // 4 * 4
         self._mask_total = self._mask_split = o
 
-    def _sum_rows(self, n=1):
-        s = self._sums[self._sum_i:self._sum_i + n].view(-1)
-        self._sum_i += n
-        return s
-
-    def _upload(self, a, cols):
-        a = np.ascontiguousarray(np.asarray(a, np.float32).reshape(self.B, cols))
-        if self.device.type != 'cuda':
-            return torch.from_numpy(a).to(self.device)
-        h = torch.empty(a.shape, dtype=torch.float32, pin_memory=True)
-        h.numpy()[...] = a
-        return h.to(self.device, non_blocking=True)
-
     # ---- the step ------------------------------------------------------------------------------------------
     def _step(self, mel, frame_off, n_wins, floor, y, masks, bias):
         L_ = self.lib
         self._prepare(n_wins)
         B, S, st = self.B, self.S, self._st()
-        hop = int(self.args['ms_seg_hop_length'])
         P, G = self.P, self.G
         self.gflat.zero_()
         y_dev = self._upload(y, 1)
         bias_dev = None if bias is None else self._upload(bias, 4)
-
-        # ================= forward: StandardCNN in train mode =================
-        cnn = []
-        act = None
-        for i in range(1, 7):
-            ci, co = _CONV[i - 1]
-            h, w, (ho, wo) = GEO[i - 1]
-            rows = S * h * w
-            wk, bk = 'cnn.model.conv%d.weight' % i, 'cnn.model.conv%d.bias' % i
-            gk, bek = 'cnn.model.bn%d.weight' % i, 'cnn.model.bn%d.bias' % i
-            drop = self._mask(masks, _DROP_AFTER[i], (S, co), self.p_cnn) if i in _DROP_AFTER else None
-            out = self._new(S, ho * wo, co)
-            arg = self._new(S, ho * wo, co, dtype=torch.int32)
-            mr = self._new(2 * co)
-            dp = _ptr(drop) if drop is not None else None
-            if i == 1:
-                mom, sums = self._sum_rows()[:54], self._sum_rows()[:32]
-                self._ck(L_.nisqa_conv1_moments(_ptr(mel), _ptr(frame_off), _ptr(self.seg_off), _ptr(floor), B, S, hop,
-                                                mom.data_ptr(), st), 'nisqa_conv1_moments')
-                self._ck(L_.nisqa_conv1_bn_act_pool_std_fwd(_ptr(mel), _ptr(frame_off), _ptr(self.seg_off), _ptr(floor), B, S, hop,
-                                                            _ptr(P[wk]), _ptr(P[bk]), mom.data_ptr(), _ptr(P[gk]), _ptr(P[bek]),
-                                                            _ptr(self.bn[1]['mean']), _ptr(self.bn[1]['var']), sums.data_ptr(),
-                                                            _ptr(mr), dp, _ptr(out), arg.data_ptr(), st),
-                         'nisqa_conv1_bn_act_pool_std_fwd')
-                cnn.append(dict(z=None, x=None, arg=arg, mr=mr, drop=drop, mom=mom))
-            else:
-                hi, wi = GEO[i - 2][2]
-                z = self._new(rows, co)
-                sums = self._sum_rows()
-                self._ck(L_.nisqa_conv3x3_fwd_stats(0, _ptr(act), _ptr(P[wk]), _ptr(z), S, hi, wi, ci, co, 1, _ptr(P[bk]),
-                                                    sums.data_ptr(), st), 'nisqa_conv3x3_fwd_stats')
-                self._ck(L_.nisqa_bn_act_pool_fwd(_ptr(z), sums.data_ptr(), _ptr(P[gk]), _ptr(P[bek]), _ptr(self.bn[i]['mean']),
-                                                  _ptr(self.bn[i]['var']), _ptr(mr), S, h, w, co, ho, wo, dp, _ptr(out),
-                                                  arg.data_ptr(), st), 'nisqa_bn_act_pool_fwd')
-                cnn.append(dict(z=z, x=act, arg=arg, mr=mr, drop=drop))
-            self.bn[i]['n'] += 1
-            act = out
+        cnn, act = self._cnn_fwd(mel, frame_off, floor, masks)
         feat = act.view(S, 768)                                               # [S][12 pixels][64] in (pixel, c) order
         x20 = self._linear_fwd(feat, FC_W, 'cnn.model.fc_out.bias', S, 768, 20)
 
@@ -241,36 +162,5 @@ class HipTrainerLSTM(_FlatTrainer):
                        ksplit=self._ksplit(S, 512, 128))
         dx20 = self._new(S, 20)                                               # sum over both directions: K = 1024
         self._gemm(dgates, wih, dx20, S, 20, 1024, 1024, 20, 20)
-        da = self._linear_bwd(dx20, feat, FC_W, 'cnn.model.fc_out.bias', S, 768, 20).view(S, 12, 64)
-
-        # ================= backward: StandardCNN =================
-        for i in range(6, 0, -1):
-            c = cnn[i - 1]
-            ci, co = _CONV[i - 1]
-            h, w, (ho, wo) = GEO[i - 1]
-            g, b_ = P['cnn.model.bn%d.weight' % i], P['cnn.model.bn%d.bias' % i]
-            dg, db = G['cnn.model.bn%d.weight' % i], G['cnn.model.bn%d.bias' % i]
-            dp = _ptr(c['drop']) if c['drop'] is not None else None
-            if i == 1:
-                acc = self._sum_rows()[:176]
-                self._ck(L_.nisqa_conv1_bn_act_pool_std_bwd(_ptr(mel), _ptr(frame_off), _ptr(self.seg_off), _ptr(floor), B, S, hop,
-                                                            _ptr(P['cnn.model.conv1.weight']), _ptr(P['cnn.model.conv1.bias']),
-                                                            c['mom'].data_ptr(), _ptr(g), _ptr(b_), _ptr(c['mr']), dp, _ptr(da),
-                                                            c['arg'].data_ptr(), acc.data_ptr(), _ptr(dg), _ptr(db),
-                                                            _ptr(G['cnn.model.conv1.weight']), st), 'nisqa_conv1_bn_act_pool_std_bwd')
-                break                                                         # conv biases: exactly zero (gflat was cleared)
-            rows = S * h * w
-            hi, wi = GEO[i - 2][2]
-            dz = self._new(rows, co)
-            s2 = self._sum_rows()
-            self._ck(L_.nisqa_bn_act_pool_bwd(_ptr(da), c['arg'].data_ptr(), dp, _ptr(c['z']), _ptr(c['mr']), _ptr(g), _ptr(b_), S,
-                                              h, w, co, ho, wo, s2.data_ptr(), _ptr(dz), _ptr(dg), _ptr(db), st),
-                     'nisqa_bn_act_pool_bwd')
-            wk = 'cnn.model.conv%d.weight' % i
-            self._ck(L_.nisqa_conv3x3_gemm(2, _ptr(c['x']), _ptr(dz), _ptr(G[wk]), S, hi, wi, ci, co, 1, None,
-                                           self._ksplit(rows, co, 9 * ci), st), 'nisqa_conv3x3_gemm wgrad')
-            da = self._new(S, hi * wi, ci)
-            self._ck(L_.nisqa_conv3x3_gemm(1, _ptr(dz), _ptr(P[wk]), _ptr(da), S, hi, wi, ci, co, 1, None, 1, st),
-                     'nisqa_conv3x3_gemm dgrad')
-            c['x'] = None
+        self._cnn_bwd(cnn, [self._linear_bwd(dx20, feat, FC_W, 'cnn.model.fc_out.bias', S, 768, 20)])     # [S][12][64]
         return self._finish_step(y_hat, loss)
