@@ -108,15 +108,21 @@ int nisqa_conv3x3_fwd_stats(int32_t split_bf16, const float* x, const float* w_,
  * inference kernel over them; arithmetic = nisqa_conv3x3_gemm_bf16 (three products per term, fp32 accumulation).
  * Replaces, for the five layer shapes of config/train_nisqa_cnn_sa_ap.yaml, what PyTorch does inside
  * nisqa/NISQA_lib.py:690-705 (conv forward) and in autograd's convolution backward (NISQA_model.py:142-143).
- *   nisqa_segconv_supported  1 if (h, w, ci, co, pad_w) is one of those shapes ((24,7,16,32,1) (12,5,32,64,1) (12,5,64,64,1)
- *                            (6,3,64,64,1) (6,3,64,64,0)); otherwise callers use nisqa_conv3x3_gemm_bf16
+ *   nisqa_segconv_supported  1 if (h, w, ci, co, pad_w) is one of those shapes; otherwise callers use nisqa_conv3x3_gemm_bf16.
+ *                            The shapes, each with the pooled size (ho, wo) that the folded weight gradients below take:
+ *                              (24,7,16,32,1) -> (12,5)   (12,5,32,64,1) -> (12,5)   (12,5,64,64,1) -> (6,3)
+ *                              (6,3,64,64,1) -> (6,3)     (6,3,64,64,0) -> (6,1)
+ *                            Every nisqa_segconv_* entry below takes exactly these and returns NISQA_ERR_ARG for anything else.
  *   nisqa_segconv_frag_bytes size of the packed weight fragments of one layer and mode (-1: bad arguments)
  *   nisqa_segconv_pack       w[co][9*ci] -> fragments (bf16 hi / lo, MFMA B-operand order); mode 0 forward, mode 1 input
  *                            gradient (taps mirrored, matrix transposed).  Once per optimiser step.
  *   nisqa_segconv_bf16       mode 0: z[S*h*wo][co] = conv(x[S][h*w][ci]) + bias (may be NULL); stats2c (may be NULL; float64,
  *                            zeroed by the caller) += sum z, sum z^2 per channel;
  *                            mode 1: dx[S*h*w][ci] = conv^T(dz[S][h*wo][co]); bias and stats2c must be NULL.
- *                            frags = nisqa_segconv_pack of the same mode. */
+ *                            frags = nisqa_segconv_pack of the same mode.
+ * The other operand formats (_f32, _bf16x6, _f16 below) each have their own nisqa_segconv_frag_bytes* / nisqa_segconv_pack*_many /
+ * convolution entry with the arguments of nisqa_segconv_frag_bytes / nisqa_segconv_pack_many / nisqa_segconv_bf16; fragments of
+ * one format are read by that format's convolution only. */
 int nisqa_segconv_supported(int32_t h, int32_t w, int32_t ci, int32_t co, int32_t pad_w);
 int64_t nisqa_segconv_frag_bytes(int32_t mode, int32_t ci, int32_t co);
 int nisqa_segconv_pack(int32_t mode, const float* w, int32_t ci, int32_t co, uint16_t* frags, void* stream);
@@ -129,8 +135,7 @@ int nisqa_segconv_bf16(int32_t mode, const float* src, const uint16_t* frags, fl
 /* The same two products in EXACT fp32 (v_mfma_f32_32x32x2_f32; fp32 planes in LDS, fp32 fragments): the forward convolutions of
  * the precision modes 'f32' and 'mixed' and the input gradients of 'f32'.  The implicit GEMMs (nisqa_conv3x3_gemm) reach the
  * fp32-MFMA peak on none of these shapes but the 64 -> 64 one at 12 x 5 (narrow outputs, gathers per K-tile); here every
- * activation is fetched once.  nisqa_segconv_frag_bytes_f32 / nisqa_segconv_pack_f32_many / nisqa_segconv_f32 mirror
- * nisqa_segconv_frag_bytes / nisqa_segconv_pack_many / nisqa_segconv_bf16 argument for argument (frags are floats). */
+ * activation is fetched once.  Fragments are floats. */
 int64_t nisqa_segconv_frag_bytes_f32(int32_t mode, int32_t ci, int32_t co);
 int nisqa_segconv_pack_f32_many(int32_t n_jobs, const int32_t* modes, const float* const* w, const int32_t* ci, const int32_t* co,
                                 float* const* frags, void* stream);
@@ -138,16 +143,14 @@ int nisqa_segconv_f32(int32_t mode, const float* src, const float* frags, float*
                       int32_t ci, int32_t co, int32_t pad_w, const float* bias, double* stats2c, void* stream);
 /* The same two products at fp32 OPERAND precision on the bf16 matrix pipe (precision mode 'bf16x6'): activations and weights
  * as three exact bf16 terms (hi + mid + lo), six MFMA products per term pair, fp32 accumulation -- the accuracy of
- * nisqa_segconv_f32 at 2.7 x its matrix-pipe rate.  nisqa_segconv_frag_bytes_x6 / nisqa_segconv_pack_x6_many /
- * nisqa_segconv_bf16x6 mirror nisqa_segconv_frag_bytes / nisqa_segconv_pack_many / nisqa_segconv_bf16 argument for argument
- * (three-term fragments: 1.5 x the bytes). */
+ * nisqa_segconv_f32 at 2.7 x its matrix-pipe rate.  Three-term fragments: 1.5 x the bytes. */
 int64_t nisqa_segconv_frag_bytes_x6(int32_t mode, int32_t ci, int32_t co);
 /* The same two products on TWO f16 terms per operand, all four term products (precision mode 'f16x4'): the staged tensor of a
  * workgroup's group of segments as f16 hi + lo of x * 2^e, e from the group's own largest magnitude (measured while the values are
  * in registers); the weights as f16 hi + lo of W * 2^kw, kw from the layer's largest |W| of this optimiser step (computed on the
  * device by the packer, stored behind the fragments: the buffer is 16 bytes longer).  11 + 11 significand bits and the low term's
  * sign: the fp32 value itself for ~75 % of the operands, one fp32 ulp off otherwise; held to the bounds of nisqa_segconv_f32 by the
- * same test.  Mirrors nisqa_segconv_frag_bytes / nisqa_segconv_pack_many / nisqa_segconv_bf16 argument for argument. */
+ * same test. */
 int64_t nisqa_segconv_frag_bytes_f16(int32_t mode, int32_t ci, int32_t co);
 int nisqa_segconv_pack_f16_many(int32_t n_jobs, const int32_t* modes, const float* const* w, const int32_t* ci, const int32_t* co,
                                 uint16_t* const* frags, void* stream);
@@ -198,8 +201,8 @@ int nisqa_bn_act_pool_bwd(const float* dy, const int32_t* arg, const float* drop
  * pooled gradient dy (+ arg, drop) instead of dz, computes dz = gamma rstd (dyb - mean(dyb) - xhat mean(dyb xhat)) per element
  * while it stages a group of segments, writes dz (for the input-gradient kernel that runs next), dgamma and dbeta, and adds dw
  * like nisqa_segconv_wgrad_bf16.  The dense z -> dz pass of layers 2..6 (memory-bound, 0.29 ms of a 3.4 ms step) disappears.
- * Shapes: the five nisqa_segconv_supported layers with their pooling sizes (ho, wo) = (12,5) (12,5) (6,3) (6,3) (6,1); anything
- * else returns NISQA_ERR_ARG (run nisqa_bn_act_pool_bwd + nisqa_segconv_wgrad_bf16 instead). */
+ * Shapes: the nisqa_segconv_supported layers, each with its own pooled size (ho, wo) listed there; anything else returns
+ * NISQA_ERR_ARG (run nisqa_bn_act_pool_bwd + nisqa_segconv_wgrad_bf16 instead). */
 int nisqa_bn_pool_bwd_sums(const float* dy, const int32_t* arg, const float* drop, const float* z, const float* mean_rstd,
                            const float* gamma, const float* beta, int32_t n_segments, int32_t h, int32_t w, int32_t c, int32_t ho,
                            int32_t wo, double* sums2, void* stream);

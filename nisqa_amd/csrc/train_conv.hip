@@ -31,8 +31,6 @@
 #define SC_BASE 2176u                      /* hi plane; the lo plane follows */
 // per-phase clock of the segment-conv kernels (tools/bench_segconv.py; empty macros unless built with -DNQ_EXPERIMENTAL): phases 0..5, [6] = groups, [7] = waves
 NQ_CLK_EXPORT(g_sc_clk, nisqa_debug_segconv_clock)
-#define SC_W_MSPLIT 1         /* weight gradient of the 64 -> 64 layers: 1 = a wave takes both M tiles and every 8th N tile, 2 = one M tile, every 4th */
-#define SC_SEGS60 4            /* segments per workgroup of the 12 x 5 layers (two 32-row tiles per wave at 4, one at 2) */
 #define SC_WGS 2
 #define SC_RING 3            /* weight-fragment ring of the K loop (slots) */
 #define SC_FENCE() __builtin_amdgcn_sched_barrier(0)
@@ -88,7 +86,7 @@ __global__ __launch_bounds__(256) void segconv_pack_many_kernel(segconv_pack_job
 // ---- f16 formats (precision mode 'f16x4'): fragments of W * 2^kw as f16 hi + lo in the two-term layout, kw from the layer's largest
 //      |W| of THIS optimiser step (the largest lands in [2^14, 2^15)), stored as one int32 behind the fragments (the buffer is 16 bytes
 //      longer): segconv_wmax_kernel writes it, the packer and the convolution read it
-__global__ __launch_bounds__(256) void segconv_wmax_kernel(segconv_pack_jobs jobs, int frag_u16_unused) {
+__global__ __launch_bounds__(256) void segconv_wmax_kernel(segconv_pack_jobs jobs) {
     const int j = blockIdx.x;
     const float* __restrict__ w = jobs.w[j];
     const int n = jobs.ci[j] * jobs.co[j] * 9;
@@ -142,39 +140,32 @@ extern "C" int nisqa_segconv_pack(int32_t mode, const float* w, int32_t ci, int3
     return NQ_LAUNCH_STATUS();
 }
 
-extern "C" int64_t nisqa_segconv_frag_bytes_f16(int32_t mode, int32_t ci, int32_t co) {
-    const int64_t b = nisqa_segconv_frag_bytes(mode, ci, co);
-    return b < 0 ? b : b + 16;                                  // + the layer's scale exponent (int32) behind the fragments
-}
-extern "C" int nisqa_segconv_pack_f16_many(int32_t n_jobs, const int32_t* modes, const float* const* w, const int32_t* ci,
-                                           const int32_t* co, uint16_t* const* frags, void* stream) {
-    if (n_jobs < 1 || n_jobs > 10 || !modes || !w || !ci || !co || !frags) return NISQA_ERR_ARG;
-    segconv_pack_jobs jobs = {};
-    jobs.terms = 2;
+// the job list of the *_pack_*_many entries (JOBS = segconv_pack_jobs or segconv_pack_f32_jobs, declared with its kernel below;
+// the 16-bit and the fp32 fragment sizes are defined for the same (mode, ci, co)): false = bad arguments
+template <typename JOBS, typename FRAG>
+static bool segconv_pack_fill(JOBS& jobs, int32_t n_jobs, const int32_t* modes, const float* const* w, const int32_t* ci,
+                              const int32_t* co, FRAG* const* frags) {
+    if (n_jobs < 1 || n_jobs > 10 || !modes || !w || !ci || !co || !frags) return false;
     for (int j = 0; j < n_jobs; ++j) {
-        if (!w[j] || !frags[j] || nisqa_segconv_frag_bytes(modes[j], ci[j], co[j]) < 0) return NISQA_ERR_ARG;
+        if (!w[j] || !frags[j] || nisqa_segconv_frag_bytes(modes[j], ci[j], co[j]) < 0) return false;
         jobs.w[j] = w[j]; jobs.out[j] = frags[j]; jobs.ci[j] = ci[j]; jobs.co[j] = co[j]; jobs.mode[j] = modes[j];
     }
-    NQ_LAUNCH_BEGIN();
-    hipLaunchKernelGGL(segconv_wmax_kernel, dim3(n_jobs), dim3(256), 0, (hipStream_t)stream, jobs, 0);
-    hipLaunchKernelGGL(segconv_pack_f16_many_kernel, dim3(36, n_jobs), dim3(256), 0, (hipStream_t)stream, jobs);
-    return NQ_LAUNCH_STATUS();
+    return true;
 }
-
-extern "C" int nisqa_segconv_pack_many(int32_t n_jobs, const int32_t* modes, const float* const* w, const int32_t* ci,
-                                       const int32_t* co, uint16_t* const* frags, void* stream) {
-    if (n_jobs < 1 || n_jobs > 10 || !modes || !w || !ci || !co || !frags) return NISQA_ERR_ARG;
+// bf16 fragments of `terms` terms (2: nisqa_segconv_pack_many, 3: nisqa_segconv_pack_x6_many), one launch for all jobs
+static int segconv_pack_terms(int terms, int32_t n_jobs, const int32_t* modes, const float* const* w, const int32_t* ci,
+                              const int32_t* co, uint16_t* const* frags, void* stream) {
     segconv_pack_jobs jobs = {};
-    jobs.terms = 2;
-    for (int j = 0; j < n_jobs; ++j) {
-        if (!w[j] || !frags[j] || nisqa_segconv_frag_bytes(modes[j], ci[j], co[j]) < 0) return NISQA_ERR_ARG;
-        jobs.w[j] = w[j]; jobs.out[j] = frags[j]; jobs.ci[j] = ci[j]; jobs.co[j] = co[j]; jobs.mode[j] = modes[j];
-    }
+    jobs.terms = terms;
+    if (!segconv_pack_fill(jobs, n_jobs, modes, w, ci, co, frags)) return NISQA_ERR_ARG;
     NQ_LAUNCH_BEGIN();
     hipLaunchKernelGGL(segconv_pack_many_kernel, dim3(36, n_jobs), dim3(256), 0, (hipStream_t)stream, jobs);
     return NQ_LAUNCH_STATUS();
 }
-
+extern "C" int nisqa_segconv_pack_many(int32_t n_jobs, const int32_t* modes, const float* const* w, const int32_t* ci,
+                                       const int32_t* co, uint16_t* const* frags, void* stream) {
+    return segconv_pack_terms(2, n_jobs, modes, w, ci, co, frags, stream);
+}
 // three-term fragments (nisqa_segconv_bf16x6): 1.5 x the bytes
 extern "C" int64_t nisqa_segconv_frag_bytes_x6(int32_t mode, int32_t ci, int32_t co) {
     const int64_t b = nisqa_segconv_frag_bytes(mode, ci, co);
@@ -182,15 +173,21 @@ extern "C" int64_t nisqa_segconv_frag_bytes_x6(int32_t mode, int32_t ci, int32_t
 }
 extern "C" int nisqa_segconv_pack_x6_many(int32_t n_jobs, const int32_t* modes, const float* const* w, const int32_t* ci,
                                           const int32_t* co, uint16_t* const* frags, void* stream) {
-    if (n_jobs < 1 || n_jobs > 10 || !modes || !w || !ci || !co || !frags) return NISQA_ERR_ARG;
+    return segconv_pack_terms(3, n_jobs, modes, w, ci, co, frags, stream);
+}
+
+extern "C" int64_t nisqa_segconv_frag_bytes_f16(int32_t mode, int32_t ci, int32_t co) {
+    const int64_t b = nisqa_segconv_frag_bytes(mode, ci, co);
+    return b < 0 ? b : b + 16;                                  // + the layer's scale exponent (int32) behind the fragments
+}
+extern "C" int nisqa_segconv_pack_f16_many(int32_t n_jobs, const int32_t* modes, const float* const* w, const int32_t* ci,
+                                           const int32_t* co, uint16_t* const* frags, void* stream) {
     segconv_pack_jobs jobs = {};
-    jobs.terms = 3;
-    for (int j = 0; j < n_jobs; ++j) {
-        if (!w[j] || !frags[j] || nisqa_segconv_frag_bytes(modes[j], ci[j], co[j]) < 0) return NISQA_ERR_ARG;
-        jobs.w[j] = w[j]; jobs.out[j] = frags[j]; jobs.ci[j] = ci[j]; jobs.co[j] = co[j]; jobs.mode[j] = modes[j];
-    }
+    jobs.terms = 2;
+    if (!segconv_pack_fill(jobs, n_jobs, modes, w, ci, co, frags)) return NISQA_ERR_ARG;
     NQ_LAUNCH_BEGIN();
-    hipLaunchKernelGGL(segconv_pack_many_kernel, dim3(36, n_jobs), dim3(256), 0, (hipStream_t)stream, jobs);
+    hipLaunchKernelGGL(segconv_wmax_kernel, dim3(n_jobs), dim3(256), 0, (hipStream_t)stream, jobs);
+    hipLaunchKernelGGL(segconv_pack_f16_many_kernel, dim3(36, n_jobs), dim3(256), 0, (hipStream_t)stream, jobs);
     return NQ_LAUNCH_STATUS();
 }
 
@@ -264,12 +261,8 @@ extern "C" int64_t nisqa_segconv_frag_bytes_f32(int32_t mode, int32_t ci, int32_
 }
 extern "C" int nisqa_segconv_pack_f32_many(int32_t n_jobs, const int32_t* modes, const float* const* w, const int32_t* ci,
                                            const int32_t* co, float* const* frags, void* stream) {
-    if (n_jobs < 1 || n_jobs > 10 || !modes || !w || !ci || !co || !frags) return NISQA_ERR_ARG;
     segconv_pack_f32_jobs jobs = {};
-    for (int j = 0; j < n_jobs; ++j) {
-        if (!w[j] || !frags[j] || nisqa_segconv_frag_bytes_f32(modes[j], ci[j], co[j]) < 0) return NISQA_ERR_ARG;
-        jobs.w[j] = w[j]; jobs.out[j] = frags[j]; jobs.ci[j] = ci[j]; jobs.co[j] = co[j]; jobs.mode[j] = modes[j];
-    }
+    if (!segconv_pack_fill(jobs, n_jobs, modes, w, ci, co, frags)) return NISQA_ERR_ARG;
     NQ_LAUNCH_BEGIN();
     hipLaunchKernelGGL(segconv_pack_f32_many_kernel, dim3(36, n_jobs), dim3(256), 0, (hipStream_t)stream, jobs);
     return NQ_LAUNCH_STATUS();
@@ -528,19 +521,14 @@ __global__ __launch_bounds__(256, SC_WGS) void segconv_bf16_kernel(
     }
 }
 
-// Launch state that depends on the DEVICE (CU count, resident workgroups per CU, the > 64 KB dynamic-LDS opt-in) is cached
-// per device ordinal: a process that drives a second GPU asks again for that GPU.  Atomics make the caches safe to fill
-// from several host threads (the worst case is two threads asking the runtime the same question once).
-#include <atomic>
-static constexpr int SC_MAX_DEV = 64;
-static int sc_device() {
+// Launch state that depends on the DEVICE (CU count, resident workgroups per CU, the > 64 KB dynamic-LDS opt-in of
+// nq_lds_opt_in) is cached per device ordinal: a process that drives a second GPU asks again for that GPU.  Atomics make the
+// caches safe to fill from several host threads (the worst case is two threads asking the runtime the same question once).
+static int sc_cu_count(int* ordinal = nullptr) {
+    static std::atomic<int> n[64];
     int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= SC_MAX_DEV) dev = 0;
-    return dev;
-}
-static int sc_cu_count() {
-    static std::atomic<int> n[SC_MAX_DEV];
-    const int dev = sc_device();
+    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
+    if (ordinal) *ordinal = dev;
     int v = n[dev].load(std::memory_order_relaxed);
     if (!v) {
         hipDeviceProp_t p;
@@ -550,155 +538,114 @@ static int sc_cu_count() {
     return v;
 }
 
-template <int CIN, int NT, int NOUT, int HR, int WR, int HS, int WS, int PADX, int SEGS, int MT, bool FWD, bool F32 = false, int TERMS = 2, int FMT = NQ_FMT_BF16X3>
-static void segconv_launch(hipStream_t st, const float* src, const uint16_t* frags, float* out, int n_segments,
-                           const float* bias, double* stats) {
+// 0, or 2 when the kernel cannot have its 50-80 KB of dynamic LDS (a runtime that enforces the 64 KB default would refuse the launch)
+template <int CIN, int NT, int NOUT, int HR, int WR, int HS, int WS, int PADX, int SEGS, int MT, bool FWD, bool F32, int TERMS, int FMT>
+static int segconv_launch(hipStream_t st, const float* src, const uint16_t* frags, float* out, int n_segments,
+                          const float* bias, double* stats) {
     typedef segconv_cfg<CIN, NT, NOUT, HR, WR, HS, WS, PADX, SEGS, MT, FWD, F32, TERMS, FMT> C;
-    static std::atomic<int> per_cu_dev[SC_MAX_DEV];             // resident workgroups per CU (registers and LDS), asked once per device
-    const int dev = sc_device();
+    const auto kernel = segconv_bf16_kernel<CIN, NT, NOUT, HR, WR, HS, WS, PADX, SEGS, MT, FWD, F32, TERMS, FMT>;
+    static std::atomic<bool> lds_ok[64];
+    static std::atomic<int> per_cu_dev[64];                     // resident workgroups per CU (registers and LDS), asked once per device
+    if (nq_lds_opt_in((const void*)kernel, (int)C::LDS, lds_ok)) return 2;
+    int dev = 0;
+    const int cus = sc_cu_count(&dev);
     int per_cu = per_cu_dev[dev].load(std::memory_order_relaxed);
     if (!per_cu) {
-        // 50-80 KB of dynamic LDS: opt in explicitly (a runtime that enforces the 64 KB default would refuse the launch)
-        (void)hipFuncSetAttribute((const void*)segconv_bf16_kernel<CIN, NT, NOUT, HR, WR, HS, WS, PADX, SEGS, MT, FWD, F32, TERMS, FMT>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS);
-        int nb = 0;
-        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, segconv_bf16_kernel<CIN, NT, NOUT, HR, WR, HS, WS, PADX, SEGS, MT, FWD, F32, TERMS, FMT>, 256,
-                                                         C::LDS) != hipSuccess || nb < 1)
-            nb = 2;
-        per_cu = nb;
-        per_cu_dev[dev].store(nb, std::memory_order_relaxed);
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, 256, C::LDS) != hipSuccess || per_cu < 1) per_cu = 2;
+        per_cu_dev[dev].store(per_cu, std::memory_order_relaxed);
     }
     const int n_groups = (n_segments + SEGS - 1) / SEGS;
-    const int grid = n_groups < per_cu * sc_cu_count() ? n_groups : per_cu * sc_cu_count();
-    hipLaunchKernelGGL((segconv_bf16_kernel<CIN, NT, NOUT, HR, WR, HS, WS, PADX, SEGS, MT, FWD, F32, TERMS, FMT>), dim3(grid), dim3(256), C::LDS, st, src,
-                       frags, out, n_segments, bias, stats);
+    hipLaunchKernelGGL(kernel, dim3(n_groups < per_cu * cus ? n_groups : per_cu * cus), dim3(256), C::LDS, st, src, frags, out,
+                       n_segments, bias, stats);
+    return 0;
 }
 
-// the five layer shapes of the AdaptCNN at the reference's pooling sizes (config/train_nisqa_cnn_sa_ap.yaml:
-// cnn_pool_1 [24, 7], cnn_pool_2 [12, 5], cnn_pool_3 [6, 3]); for anything else nisqa_segconv_supported says 0 and the
-// caller keeps nisqa_conv3x3_gemm_bf16
-#define SC_KEY(h_, w_, ci_, co_) ((((h_) * 100 + (w_)) * 100 + (ci_)) * 100 + (co_))
+// THE layer shapes of this file: the five 3 x 3 convolutions of the AdaptCNN behind its first at the reference's pooling sizes
+// (config/train_nisqa_cnn_sa_ap.yaml: cnn_pool_1 [24, 7], cnn_pool_2 [12, 5], cnn_pool_3 [6, 3]), each with the pooled size
+// (PH, PW) its BatchNorm / max-pool block produces (what the folded weight gradients take as (ho, wo)).  I is the shape's row in
+// the tile tables below.  nisqa_segconv_supported and every dispatch go through sc_shapes::for_shape, so a new shape is one line here
+// plus one row per tile table; for anything else nisqa_segconv_supported says 0 and the caller keeps the implicit GEMM.
+template <int I_, int H_, int W_, int CI_, int CO_, int PADW_, int PH_, int PW_>
+struct sc_shape {
+    static constexpr int I = I_, H = H_, W = W_, CI = CI_, CO = CO_, PADW = PADW_, PH = PH_, PW = PW_;
+    static constexpr int WO = W + 2 * PADW - 2;               // width of the convolution's output
+};
+// for_shape: f(shape tag) of the shape that (h, w, ci, co, pad_w) names; NISQA_ERR_ARG when it names none
+template <typename... S>
+struct sc_shape_list {
+    static constexpr int N = sizeof...(S);
+    template <typename F>
+    static int for_shape(int h, int w, int ci, int co, int pad_w, F&& f) {
+        int rc = NISQA_ERR_ARG;
+        (void)((h == S::H && w == S::W && ci == S::CI && co == S::CO && pad_w == S::PADW && (rc = f(S{}), true)) || ...);
+        return rc;
+    }
+};
+typedef sc_shape_list<sc_shape<0, 24, 7, 16, 32, 1, 12, 5>,
+                      sc_shape<1, 12, 5, 32, 64, 1, 12, 5>,
+                      sc_shape<2, 12, 5, 64, 64, 1, 6, 3>,
+                      sc_shape<3, 6, 3, 64, 64, 1, 6, 3>,
+                      sc_shape<4, 6, 3, 64, 64, 0, 6, 1>> sc_shapes;
 extern "C" int nisqa_segconv_supported(int32_t h, int32_t w, int32_t ci, int32_t co, int32_t pad_w) {
-    const int key = SC_KEY(h, w, ci, co);
-    if (pad_w == 0) return key == SC_KEY(6, 3, 64, 64);
-    return pad_w == 1 && (key == SC_KEY(24, 7, 16, 32) || key == SC_KEY(12, 5, 32, 64) || key == SC_KEY(12, 5, 64, 64) ||
-                          key == SC_KEY(6, 3, 64, 64));
+    return sc_shapes::for_shape(h, w, ci, co, pad_w, [](auto) { return 0; }) == 0;
 }
+
+// Segments per workgroup and 32-row tiles per wave of the forward / input-gradient kernel, [three-term][dgrad][shape]: as many
+// segments as leave two workgroups per CU their LDS (segconv_cfg asserts it) with the rows filling the four waves' tiles (the
+// 12 x 5 layers: two 32-row tiles per wave at 4 segments, one at 2).  Three planes per staged tensor: fewer segments.
+struct segconv_tile { int segs, mt; };
+static constexpr segconv_tile SEGCONV_TILE[2][2][sc_shapes::N] = {
+    //  24x7 16>32  12x5 32>64  12x5 64>64  6x3 64>64   6x3 64>64 pad 0
+    {{{3, 4}, {4, 2}, {4, 2}, {14, 2}, {15, 1}},            // two terms (bf16 hi / lo, f16 hi / lo) and fp32: forward
+     {{2, 3}, {4, 2}, {4, 2}, {14, 2}, {14, 2}}},           //                                                 input gradient
+    {{{3, 4}, {4, 2}, {2, 1}, {7, 1}, {7, 1}},              // three terms: forward
+     {{1, 2}, {2, 1}, {2, 1}, {7, 1}, {14, 2}}},            //              input gradient
+};
+
+// mode 0: z = conv(x) + bias, statistics riding along: the staged tensor is x [S][h * w][ci], the rows are the h * wo output pixels;
+// mode 1: dx = conv^T(dz): the staged tensor is dz [S][h * wo][co], the rows are the h * w input pixels, horizontal padding 2 - pad_w
+template <bool F32, int TERMS, int FMT>
+static int segconv_dispatch(int32_t mode, const float* src, const void* frags, float* out, int32_t n_segments, int32_t h, int32_t w,
+                            int32_t ci, int32_t co, int32_t pad_w, const float* bias, double* stats2c, void* stream) {
+    if (mode < 0 || mode > 1 || !src || !frags || !out || n_segments <= 0 || (mode == 1 && (bias || stats2c))) return NISQA_ERR_ARG;
+    return sc_shapes::for_shape(h, w, ci, co, pad_w, [&](auto shape) -> int {
+        typedef decltype(shape) S;
+        constexpr segconv_tile TF = SEGCONV_TILE[TERMS == 3][0][S::I], TD = SEGCONV_TILE[TERMS == 3][1][S::I];
+        hipStream_t st = (hipStream_t)stream;
+        const uint16_t* fr = (const uint16_t*)frags;
+        NQ_LAUNCH_BEGIN();
+        const int rc =
+            mode == 0 ? segconv_launch<S::CI, (S::CO + 31) / 32, S::CO, S::H, S::WO, S::H, S::W, S::PADW, TF.segs, TF.mt, true, F32, TERMS, FMT>(
+                            st, src, fr, out, n_segments, bias, stats2c)
+                      : segconv_launch<S::CO, (S::CI + 31) / 32, S::CI, S::H, S::W, S::H, S::WO, 2 - S::PADW, TD.segs, TD.mt, false, F32, TERMS, FMT>(
+                            st, src, fr, out, n_segments, nullptr, nullptr);
+        return rc ? rc : NQ_LAUNCH_STATUS();
+    });
+}
+
+// split bf16, hi + lo, three products per term pair (frags = nisqa_segconv_pack / nisqa_segconv_pack_many of the same mode)
 extern "C" int nisqa_segconv_bf16(int32_t mode, const float* src, const uint16_t* frags, float* out, int32_t n_segments,
                                   int32_t h, int32_t w, int32_t ci, int32_t co, int32_t pad_w, const float* bias,
                                   double* stats2c, void* stream) {
-    if (mode < 0 || mode > 1 || !src || !frags || !out || n_segments <= 0 || (mode == 1 && (bias || stats2c)) ||
-        !nisqa_segconv_supported(h, w, ci, co, pad_w))
-        return NISQA_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    NQ_LAUNCH_BEGIN();
-    const int key = ((h * 100 + w) * 100 + ci) * 100 + co;
-    const int n = n_segments;
-    if (mode == 0) {
-        if (key == SC_KEY(24, 7, 16, 32) && pad_w == 1) segconv_launch<16, 1, 32, 24, 7, 24, 7, 1, 3, 4, true>(st, src, frags, out, n, bias, stats2c);
-        else if (key == SC_KEY(12, 5, 32, 64) && pad_w == 1) segconv_launch<32, 2, 64, 12, 5, 12, 5, 1, SC_SEGS60, SC_SEGS60 / 2, true>(st, src, frags, out, n, bias, stats2c);
-        else if (key == SC_KEY(12, 5, 64, 64) && pad_w == 1) segconv_launch<64, 2, 64, 12, 5, 12, 5, 1, SC_SEGS60, SC_SEGS60 / 2, true>(st, src, frags, out, n, bias, stats2c);
-        else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 1) segconv_launch<64, 2, 64, 6, 3, 6, 3, 1, 14, 2, true>(st, src, frags, out, n, bias, stats2c);
-        else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 0) segconv_launch<64, 2, 64, 6, 1, 6, 3, 0, 15, 1, true>(st, src, frags, out, n, bias, stats2c);
-        else return NISQA_ERR_ARG;
-    } else {                                                  // staged tensor = dz [S][h * wo][co], rows = the h * w input pixels
-        if (key == SC_KEY(24, 7, 16, 32) && pad_w == 1) segconv_launch<32, 1, 16, 24, 7, 24, 7, 1, 2, 3, false>(st, src, frags, out, n, nullptr, nullptr);
-        else if (key == SC_KEY(12, 5, 32, 64) && pad_w == 1) segconv_launch<64, 1, 32, 12, 5, 12, 5, 1, SC_SEGS60, SC_SEGS60 / 2, false>(st, src, frags, out, n, nullptr, nullptr);
-        else if (key == SC_KEY(12, 5, 64, 64) && pad_w == 1) segconv_launch<64, 2, 64, 12, 5, 12, 5, 1, SC_SEGS60, SC_SEGS60 / 2, false>(st, src, frags, out, n, nullptr, nullptr);
-        else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 1) segconv_launch<64, 2, 64, 6, 3, 6, 3, 1, 14, 2, false>(st, src, frags, out, n, nullptr, nullptr);
-        else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 0) segconv_launch<64, 2, 64, 6, 3, 6, 1, 2, 14, 2, false>(st, src, frags, out, n, nullptr, nullptr);
-        else return NISQA_ERR_ARG;
-    }
-    return NQ_LAUNCH_STATUS();
+    return segconv_dispatch<false, 2, NQ_FMT_BF16X3>(mode, src, frags, out, n_segments, h, w, ci, co, pad_w, bias, stats2c, stream);
 }
-
-// the same two products on f16 hi + lo of the per-group scaled tensors, four term products (precision mode 'f16x4'; frags =
-// nisqa_segconv_pack_f16_many of the same mode, nisqa_segconv_frag_bytes_f16 bytes)
+// f16 hi + lo of the per-group scaled tensors, four term products (precision mode 'f16x4'; frags = nisqa_segconv_pack_f16_many of
+// the same mode, nisqa_segconv_frag_bytes_f16 bytes)
 extern "C" int nisqa_segconv_f16(int32_t mode, const float* src, const uint16_t* frags, float* out, int32_t n_segments,
                                   int32_t h, int32_t w, int32_t ci, int32_t co, int32_t pad_w, const float* bias,
                                   double* stats2c, void* stream) {
-    if (mode < 0 || mode > 1 || !src || !frags || !out || n_segments <= 0 || (mode == 1 && (bias || stats2c)) ||
-        !nisqa_segconv_supported(h, w, ci, co, pad_w))
-        return NISQA_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    NQ_LAUNCH_BEGIN();
-    const int key = ((h * 100 + w) * 100 + ci) * 100 + co;
-    const int n = n_segments;
-    if (mode == 0) {
-        if (key == SC_KEY(24, 7, 16, 32) && pad_w == 1) segconv_launch<16, 1, 32, 24, 7, 24, 7, 1, 3, 4, true, false, 2, NQ_FMT_F16X4>(st, src, frags, out, n, bias, stats2c);
-        else if (key == SC_KEY(12, 5, 32, 64) && pad_w == 1) segconv_launch<32, 2, 64, 12, 5, 12, 5, 1, SC_SEGS60, SC_SEGS60 / 2, true, false, 2, NQ_FMT_F16X4>(st, src, frags, out, n, bias, stats2c);
-        else if (key == SC_KEY(12, 5, 64, 64) && pad_w == 1) segconv_launch<64, 2, 64, 12, 5, 12, 5, 1, SC_SEGS60, SC_SEGS60 / 2, true, false, 2, NQ_FMT_F16X4>(st, src, frags, out, n, bias, stats2c);
-        else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 1) segconv_launch<64, 2, 64, 6, 3, 6, 3, 1, 14, 2, true, false, 2, NQ_FMT_F16X4>(st, src, frags, out, n, bias, stats2c);
-        else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 0) segconv_launch<64, 2, 64, 6, 1, 6, 3, 0, 15, 1, true, false, 2, NQ_FMT_F16X4>(st, src, frags, out, n, bias, stats2c);
-        else return NISQA_ERR_ARG;
-    } else {                                                  // staged tensor = dz [S][h * wo][co], rows = the h * w input pixels
-        if (key == SC_KEY(24, 7, 16, 32) && pad_w == 1) segconv_launch<32, 1, 16, 24, 7, 24, 7, 1, 2, 3, false, false, 2, NQ_FMT_F16X4>(st, src, frags, out, n, nullptr, nullptr);
-        else if (key == SC_KEY(12, 5, 32, 64) && pad_w == 1) segconv_launch<64, 1, 32, 12, 5, 12, 5, 1, SC_SEGS60, SC_SEGS60 / 2, false, false, 2, NQ_FMT_F16X4>(st, src, frags, out, n, nullptr, nullptr);
-        else if (key == SC_KEY(12, 5, 64, 64) && pad_w == 1) segconv_launch<64, 2, 64, 12, 5, 12, 5, 1, SC_SEGS60, SC_SEGS60 / 2, false, false, 2, NQ_FMT_F16X4>(st, src, frags, out, n, nullptr, nullptr);
-        else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 1) segconv_launch<64, 2, 64, 6, 3, 6, 3, 1, 14, 2, false, false, 2, NQ_FMT_F16X4>(st, src, frags, out, n, nullptr, nullptr);
-        else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 0) segconv_launch<64, 2, 64, 6, 3, 6, 1, 2, 14, 2, false, false, 2, NQ_FMT_F16X4>(st, src, frags, out, n, nullptr, nullptr);
-        else return NISQA_ERR_ARG;
-    }
-    return NQ_LAUNCH_STATUS();
+    return segconv_dispatch<false, 2, NQ_FMT_F16X4>(mode, src, frags, out, n_segments, h, w, ci, co, pad_w, bias, stats2c, stream);
 }
-
-// the same two products in exact fp32 (frags = nisqa_segconv_pack_f32_many of the same mode)
+// exact fp32 (frags = nisqa_segconv_pack_f32_many of the same mode)
 extern "C" int nisqa_segconv_f32(int32_t mode, const float* src, const float* frags, float* out, int32_t n_segments, int32_t h,
                                  int32_t w, int32_t ci, int32_t co, int32_t pad_w, const float* bias, double* stats2c, void* stream) {
-    if (mode < 0 || mode > 1 || !src || !frags || !out || n_segments <= 0 || (mode == 1 && (bias || stats2c)) ||
-        !nisqa_segconv_supported(h, w, ci, co, pad_w))
-        return NISQA_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    const uint16_t* fr = (const uint16_t*)frags;
-    NQ_LAUNCH_BEGIN();
-    const int key = ((h * 100 + w) * 100 + ci) * 100 + co;
-    const int n = n_segments;
-    if (mode == 0) {
-        if (key == SC_KEY(24, 7, 16, 32) && pad_w == 1) segconv_launch<16, 1, 32, 24, 7, 24, 7, 1, 3, 4, true, true>(st, src, fr, out, n, bias, stats2c);
-        else if (key == SC_KEY(12, 5, 32, 64) && pad_w == 1) segconv_launch<32, 2, 64, 12, 5, 12, 5, 1, SC_SEGS60, SC_SEGS60 / 2, true, true>(st, src, fr, out, n, bias, stats2c);
-        else if (key == SC_KEY(12, 5, 64, 64) && pad_w == 1) segconv_launch<64, 2, 64, 12, 5, 12, 5, 1, SC_SEGS60, SC_SEGS60 / 2, true, true>(st, src, fr, out, n, bias, stats2c);
-        else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 1) segconv_launch<64, 2, 64, 6, 3, 6, 3, 1, 14, 2, true, true>(st, src, fr, out, n, bias, stats2c);
-        else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 0) segconv_launch<64, 2, 64, 6, 1, 6, 3, 0, 15, 1, true, true>(st, src, fr, out, n, bias, stats2c);
-        else return NISQA_ERR_ARG;
-    } else {
-        if (key == SC_KEY(24, 7, 16, 32) && pad_w == 1) segconv_launch<32, 1, 16, 24, 7, 24, 7, 1, 2, 3, false, true>(st, src, fr, out, n, nullptr, nullptr);
-        else if (key == SC_KEY(12, 5, 32, 64) && pad_w == 1) segconv_launch<64, 1, 32, 12, 5, 12, 5, 1, SC_SEGS60, SC_SEGS60 / 2, false, true>(st, src, fr, out, n, nullptr, nullptr);
-        else if (key == SC_KEY(12, 5, 64, 64) && pad_w == 1) segconv_launch<64, 2, 64, 12, 5, 12, 5, 1, SC_SEGS60, SC_SEGS60 / 2, false, true>(st, src, fr, out, n, nullptr, nullptr);
-        else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 1) segconv_launch<64, 2, 64, 6, 3, 6, 3, 1, 14, 2, false, true>(st, src, fr, out, n, nullptr, nullptr);
-        else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 0) segconv_launch<64, 2, 64, 6, 3, 6, 1, 2, 14, 2, false, true>(st, src, fr, out, n, nullptr, nullptr);
-        else return NISQA_ERR_ARG;
-    }
-    return NQ_LAUNCH_STATUS();
+    return segconv_dispatch<true, 2, NQ_FMT_BF16X3>(mode, src, frags, out, n_segments, h, w, ci, co, pad_w, bias, stats2c, stream);
 }
-
-// the same two products at fp32 OPERAND precision on the bf16 matrix pipe (precision mode 'bf16x6'): activations and weights
-// as three exact bf16 terms, six products per term pair (conv_k_terms; frags = nisqa_segconv_pack_x6_many of the same mode).
-// Three planes per staged tensor: fewer segments per workgroup than the two-term table above, still two workgroups per CU.
+// fp32 OPERAND precision on the bf16 matrix pipe (precision mode 'bf16x6'): activations and weights as three exact bf16 terms, six
+// products per term pair (conv_k_terms; frags = nisqa_segconv_pack_x6_many of the same mode)
 extern "C" int nisqa_segconv_bf16x6(int32_t mode, const float* src, const uint16_t* frags, float* out, int32_t n_segments, int32_t h,
                                     int32_t w, int32_t ci, int32_t co, int32_t pad_w, const float* bias, double* stats2c, void* stream) {
-    if (mode < 0 || mode > 1 || !src || !frags || !out || n_segments <= 0 || (mode == 1 && (bias || stats2c)) ||
-        !nisqa_segconv_supported(h, w, ci, co, pad_w))
-        return NISQA_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    NQ_LAUNCH_BEGIN();
-    const int key = ((h * 100 + w) * 100 + ci) * 100 + co;
-    const int n = n_segments;
-    if (mode == 0) {
-        if (key == SC_KEY(24, 7, 16, 32) && pad_w == 1) segconv_launch<16, 1, 32, 24, 7, 24, 7, 1, 3, 4, true, false, 3>(st, src, frags, out, n, bias, stats2c);
-        else if (key == SC_KEY(12, 5, 32, 64) && pad_w == 1) segconv_launch<32, 2, 64, 12, 5, 12, 5, 1, 4, 2, true, false, 3>(st, src, frags, out, n, bias, stats2c);
-        else if (key == SC_KEY(12, 5, 64, 64) && pad_w == 1) segconv_launch<64, 2, 64, 12, 5, 12, 5, 1, 2, 1, true, false, 3>(st, src, frags, out, n, bias, stats2c);
-        else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 1) segconv_launch<64, 2, 64, 6, 3, 6, 3, 1, 7, 1, true, false, 3>(st, src, frags, out, n, bias, stats2c);
-        else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 0) segconv_launch<64, 2, 64, 6, 1, 6, 3, 0, 7, 1, true, false, 3>(st, src, frags, out, n, bias, stats2c);
-        else return NISQA_ERR_ARG;
-    } else {
-        if (key == SC_KEY(24, 7, 16, 32) && pad_w == 1) segconv_launch<32, 1, 16, 24, 7, 24, 7, 1, 1, 2, false, false, 3>(st, src, frags, out, n, nullptr, nullptr);
-        else if (key == SC_KEY(12, 5, 32, 64) && pad_w == 1) segconv_launch<64, 1, 32, 12, 5, 12, 5, 1, 2, 1, false, false, 3>(st, src, frags, out, n, nullptr, nullptr);
-        else if (key == SC_KEY(12, 5, 64, 64) && pad_w == 1) segconv_launch<64, 2, 64, 12, 5, 12, 5, 1, 2, 1, false, false, 3>(st, src, frags, out, n, nullptr, nullptr);
-        else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 1) segconv_launch<64, 2, 64, 6, 3, 6, 3, 1, 7, 1, false, false, 3>(st, src, frags, out, n, nullptr, nullptr);
-        else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 0) segconv_launch<64, 2, 64, 6, 3, 6, 1, 2, 14, 2, false, false, 3>(st, src, frags, out, n, nullptr, nullptr);
-        else return NISQA_ERR_ARG;
-    }
-    return NQ_LAUNCH_STATUS();
+    return segconv_dispatch<false, 3, NQ_FMT_BF16X3>(mode, src, frags, out, n_segments, h, w, ci, co, pad_w, bias, stats2c, stream);
 }
 
 // ======================================================================================================================
@@ -998,91 +945,72 @@ __global__ __launch_bounds__(512, 1) void segwgrad_bf16_kernel(const float* __re
     NQ_SUM_END(g_sc_clk, blockIdx.x * 8 + wave, lane0 == 0);
 }
 
-template <int CI, int CO, int H, int W, int WO, int PADW, int SEGS, int MSPLIT, int PH = 0, int PW = 0, int TERMS = 2>
-static void segwgrad_launch(hipStream_t st, const float* x, const float* dz, float* dw, int n_segments, segw_bn bn = segw_bn{}) {
+template <int CI, int CO, int H, int W, int WO, int PADW, int SEGS, int MSPLIT, int PH, int PW, int TERMS>
+static int segwgrad_launch(hipStream_t st, const float* x, const float* dz, float* dw, int n_segments, segw_bn bn) {
     typedef segwgrad_cfg<CI, CO, H, W, WO, PADW, SEGS, MSPLIT, TERMS> C;
-    static std::atomic<bool> attr[SC_MAX_DEV];
-    const int dev = sc_device();
-    if (!attr[dev].load(std::memory_order_relaxed)) {           // more than 64 KB of dynamic LDS, per device
-        (void)hipFuncSetAttribute((const void*)segwgrad_bf16_kernel<CI, CO, H, W, WO, PADW, SEGS, MSPLIT, PH, PW, TERMS>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS);
-        attr[dev].store(true, std::memory_order_relaxed);
-    }
+    const auto kernel = segwgrad_bf16_kernel<CI, CO, H, W, WO, PADW, SEGS, MSPLIT, PH, PW, TERMS>;
+    static std::atomic<bool> lds_ok[64];
+    if (nq_lds_opt_in((const void*)kernel, (int)C::LDS, lds_ok)) return 2;
     const int n_groups = (n_segments + SEGS - 1) / SEGS;
-    const int grid = n_groups < sc_cu_count() ? n_groups : sc_cu_count();
-    hipLaunchKernelGGL((segwgrad_bf16_kernel<CI, CO, H, W, WO, PADW, SEGS, MSPLIT, PH, PW, TERMS>), dim3(grid), dim3(512), C::LDS, st, x, dz, dw,
-                       n_segments, bn);
+    hipLaunchKernelGGL(kernel, dim3(n_groups < sc_cu_count() ? n_groups : sc_cu_count()), dim3(512), C::LDS, st, x, dz, dw, n_segments, bn);
+    return 0;
 }
 
-// dw[co][9 * ci] += dz^T * patches(x)  (dw zeroed by the caller, as for nisqa_conv3x3_gemm mode 2); same five shapes
+// The arguments of a weight gradient, for both kernels.  bn == NULL: the plain form, dz is read.  Otherwise the BatchNorm / ReLU /
+// max-pool / Dropout2d backward of the layer is folded into the staging (see segw_bn): everything in bn but drop is needed.
+static bool segw_args_ok(const float* x, const float* dz, const float* dw, int n_segments, const segw_bn* bn) {
+    if (!x || !dw || n_segments <= 0) return false;
+    if (!bn) return dz != nullptr;
+    return bn->z && bn->dy && bn->arg && bn->mean_rstd && bn->gamma && bn->beta && bn->sums2 && bn->dz_out && bn->dgamma && bn->dbeta;
+}
+
+// Segments per group and M split of the eight waves (1 = a wave takes both M tiles and every 8th N tile, 2 = one M tile, every 4th),
+// [three-term][shape].  Three planes per tensor and two buffers: half the segments where the two-term group does not fit 160 KB.
+struct segwgrad_tile { int segs, msplit; };
+static constexpr segwgrad_tile SEGWGRAD_TILE[2][sc_shapes::N] = {
+    //  24x7 16>32  12x5 32>64  12x5 64>64  6x3 64>64   6x3 64>64 pad 0
+    {{1, 1}, {1, 2}, {1, 1}, {4, 1}, {8, 1}},
+    {{1, 1}, {1, 2}, {1, 1}, {2, 1}, {4, 1}},
+};
+// dw[co][9 * ci] += dz^T * patches(x)  (dw zeroed by the caller, as for nisqa_conv3x3_gemm mode 2).  Folded (bn != NULL): (ho, wo)
+// must be the shape's own pooled size, dz is computed from bn and written to bn->dz_out.
+template <int TERMS>
+static int segwgrad_dispatch(const float* x, const float* dz, float* dw, int32_t n_segments, int32_t h, int32_t w, int32_t ci,
+                             int32_t co, int32_t pad_w, const segw_bn* bn, int32_t ho, int32_t wo, void* stream) {
+    if (!segw_args_ok(x, dz, dw, n_segments, bn)) return NISQA_ERR_ARG;
+    return sc_shapes::for_shape(h, w, ci, co, pad_w, [&](auto shape) -> int {
+        typedef decltype(shape) S;
+        constexpr segwgrad_tile T = SEGWGRAD_TILE[TERMS == 3][S::I];
+        if (bn && (ho != S::PH || wo != S::PW)) return NISQA_ERR_ARG;
+        hipStream_t st = (hipStream_t)stream;
+        NQ_LAUNCH_BEGIN();
+        const int rc = bn ? segwgrad_launch<S::CI, S::CO, S::H, S::W, S::WO, S::PADW, T.segs, T.msplit, S::PH, S::PW, TERMS>(st, x, nullptr, dw, n_segments, *bn)
+                          : segwgrad_launch<S::CI, S::CO, S::H, S::W, S::WO, S::PADW, T.segs, T.msplit, 0, 0, TERMS>(st, x, dz, dw, n_segments, segw_bn{});
+        return rc ? rc : NQ_LAUNCH_STATUS();
+    });
+}
+
 extern "C" int nisqa_segconv_wgrad_bf16(const float* x, const float* dz, float* dw, int32_t n_segments, int32_t h, int32_t w,
                                         int32_t ci, int32_t co, int32_t pad_w, void* stream) {
-    if (!x || !dz || !dw || n_segments <= 0 || !nisqa_segconv_supported(h, w, ci, co, pad_w)) return NISQA_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    NQ_LAUNCH_BEGIN();
-    const int key = SC_KEY(h, w, ci, co);
-    if (key == SC_KEY(24, 7, 16, 32)) segwgrad_launch<16, 32, 24, 7, 7, 1, 1, 1>(st, x, dz, dw, n_segments);
-    else if (key == SC_KEY(12, 5, 32, 64)) segwgrad_launch<32, 64, 12, 5, 5, 1, 1, 2>(st, x, dz, dw, n_segments);
-    else if (key == SC_KEY(12, 5, 64, 64)) segwgrad_launch<64, 64, 12, 5, 5, 1, 1, SC_W_MSPLIT>(st, x, dz, dw, n_segments);
-    else if (pad_w == 1) segwgrad_launch<64, 64, 6, 3, 3, 1, 4, SC_W_MSPLIT>(st, x, dz, dw, n_segments);
-    else segwgrad_launch<64, 64, 6, 3, 1, 0, 8, SC_W_MSPLIT>(st, x, dz, dw, n_segments);
-    return NQ_LAUNCH_STATUS();
+    return segwgrad_dispatch<2>(x, dz, dw, n_segments, h, w, ci, co, pad_w, nullptr, 0, 0, stream);
 }
-
-// The same with the BatchNorm / ReLU / max-pool / Dropout2d backward of the layer folded into the staging (see segw_bn): for
-// the five layers of the reference configuration with their pooling sizes (ho, wo) = (12, 5) (12, 5) (6, 3) (6, 3) (6, 1).
-// Returns NISQA_ERR_ARG for anything else (callers then run nisqa_bn_act_pool_bwd + nisqa_segconv_wgrad_bf16).
+// The folded form only: NISQA_ERR_ARG for anything else (callers then run nisqa_bn_act_pool_bwd + nisqa_segconv_wgrad_bf16).
 extern "C" int nisqa_segconv_wgrad_bn_bf16(const float* x, const float* z, const float* dy, const int32_t* arg, const float* drop,
                                            const float* mean_rstd, const float* gamma, const float* beta, const double* sums2,
                                            float* dz_out, float* dgamma, float* dbeta, float* dw, int32_t n_segments, int32_t h,
                                            int32_t w, int32_t ci, int32_t co, int32_t pad_w, int32_t ho, int32_t wo, void* stream) {
-    if (!x || !z || !dy || !arg || !mean_rstd || !gamma || !beta || !sums2 || !dz_out || !dgamma || !dbeta || !dw || n_segments <= 0 ||
-        !nisqa_segconv_supported(h, w, ci, co, pad_w))
-        return NISQA_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
     const segw_bn bn = {z, dy, arg, drop, mean_rstd, gamma, beta, sums2, dz_out, dgamma, dbeta};
-    const int key = SC_KEY(h, w, ci, co);
-    NQ_LAUNCH_BEGIN();
-    if (key == SC_KEY(24, 7, 16, 32) && ho == 12 && wo == 5) segwgrad_launch<16, 32, 24, 7, 7, 1, 1, 1, 12, 5>(st, x, nullptr, dw, n_segments, bn);
-    else if (key == SC_KEY(12, 5, 32, 64) && ho == 12 && wo == 5) segwgrad_launch<32, 64, 12, 5, 5, 1, 1, 2, 12, 5>(st, x, nullptr, dw, n_segments, bn);
-    else if (key == SC_KEY(12, 5, 64, 64) && ho == 6 && wo == 3) segwgrad_launch<64, 64, 12, 5, 5, 1, 1, SC_W_MSPLIT, 6, 3>(st, x, nullptr, dw, n_segments, bn);
-    else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 1 && ho == 6 && wo == 3) segwgrad_launch<64, 64, 6, 3, 3, 1, 4, SC_W_MSPLIT, 6, 3>(st, x, nullptr, dw, n_segments, bn);
-    else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 0 && ho == 6 && wo == 1) segwgrad_launch<64, 64, 6, 3, 1, 0, 8, SC_W_MSPLIT, 6, 1>(st, x, nullptr, dw, n_segments, bn);
-    else return NISQA_ERR_ARG;
-    return NQ_LAUNCH_STATUS();
+    return segwgrad_dispatch<2>(x, nullptr, dw, n_segments, h, w, ci, co, pad_w, &bn, ho, wo, stream);
 }
-
-
 // The weight gradient at fp32 OPERAND precision on the bf16 matrix pipe (precision mode 'bf16x6'): x and dz as three exact bf16
 // terms, six products; the contract of nisqa_segconv_wgrad_f32 (z == NULL: dz_out holds dz on entry and nothing is folded;
-// otherwise the BatchNorm backward runs inside the staging and dz_out, dgamma, dbeta are written).  Three planes per tensor
-// and two buffers: half the segments per group of the two-term table where that does not fit 160 KB.
+// otherwise the BatchNorm backward runs inside the staging and dz_out, dgamma, dbeta are written).
 extern "C" int nisqa_segconv_wgrad_bf16x6(const float* x, const float* z, const float* dy, const int32_t* arg, const float* drop,
                                           const float* mean_rstd, const float* gamma, const float* beta, const double* sums2,
                                           float* dz_out, float* dgamma, float* dbeta, float* dw, int32_t n_segments, int32_t h, int32_t w,
                                           int32_t ci, int32_t co, int32_t pad_w, int32_t ho, int32_t wo, void* stream) {
-    if (!x || !dz_out || !dw || n_segments <= 0 || !nisqa_segconv_supported(h, w, ci, co, pad_w)) return NISQA_ERR_ARG;
-    const bool fold = z != nullptr;
-    if (fold && (!dy || !arg || !mean_rstd || !gamma || !beta || !sums2 || !dgamma || !dbeta)) return NISQA_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
     const segw_bn bn = {z, dy, arg, drop, mean_rstd, gamma, beta, sums2, dz_out, dgamma, dbeta};
-    const int key = SC_KEY(h, w, ci, co);
-    NQ_LAUNCH_BEGIN();
-    if (!fold) {
-        if (key == SC_KEY(24, 7, 16, 32)) segwgrad_launch<16, 32, 24, 7, 7, 1, 1, 1, 0, 0, 3>(st, x, dz_out, dw, n_segments);
-        else if (key == SC_KEY(12, 5, 32, 64)) segwgrad_launch<32, 64, 12, 5, 5, 1, 1, 2, 0, 0, 3>(st, x, dz_out, dw, n_segments);
-        else if (key == SC_KEY(12, 5, 64, 64)) segwgrad_launch<64, 64, 12, 5, 5, 1, 1, SC_W_MSPLIT, 0, 0, 3>(st, x, dz_out, dw, n_segments);
-        else if (pad_w == 1) segwgrad_launch<64, 64, 6, 3, 3, 1, 2, SC_W_MSPLIT, 0, 0, 3>(st, x, dz_out, dw, n_segments);
-        else segwgrad_launch<64, 64, 6, 3, 1, 0, 4, SC_W_MSPLIT, 0, 0, 3>(st, x, dz_out, dw, n_segments);
-        return NQ_LAUNCH_STATUS();
-    }
-    if (key == SC_KEY(24, 7, 16, 32) && ho == 12 && wo == 5) segwgrad_launch<16, 32, 24, 7, 7, 1, 1, 1, 12, 5, 3>(st, x, nullptr, dw, n_segments, bn);
-    else if (key == SC_KEY(12, 5, 32, 64) && ho == 12 && wo == 5) segwgrad_launch<32, 64, 12, 5, 5, 1, 1, 2, 12, 5, 3>(st, x, nullptr, dw, n_segments, bn);
-    else if (key == SC_KEY(12, 5, 64, 64) && ho == 6 && wo == 3) segwgrad_launch<64, 64, 12, 5, 5, 1, 1, SC_W_MSPLIT, 6, 3, 3>(st, x, nullptr, dw, n_segments, bn);
-    else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 1 && ho == 6 && wo == 3) segwgrad_launch<64, 64, 6, 3, 3, 1, 2, SC_W_MSPLIT, 6, 3, 3>(st, x, nullptr, dw, n_segments, bn);
-    else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 0 && ho == 6 && wo == 1) segwgrad_launch<64, 64, 6, 3, 1, 0, 4, SC_W_MSPLIT, 6, 1, 3>(st, x, nullptr, dw, n_segments, bn);
-    else return NISQA_ERR_ARG;
-    return NQ_LAUNCH_STATUS();
+    return segwgrad_dispatch<3>(x, dz_out, dw, n_segments, h, w, ci, co, pad_w, z ? &bn : nullptr, ho, wo, stream);
 }
 
 // ======================================================================================================================
@@ -1310,48 +1238,40 @@ __global__ __launch_bounds__(512, 1) void segwgrad_f32_kernel(const float* __res
     }
 }
 
-template <int CI, int CO, int H, int W, int WO, int PADW, int SEGS, int MSPLIT, int NSPLIT, int KSPLIT, int PH = 0, int PW = 0>
-static void segwgrad_f32_launch(hipStream_t st, const float* x, const float* dz, float* dw, int n_segments, segw_bn bn = segw_bn{}) {
+template <int CI, int CO, int H, int W, int WO, int PADW, int SEGS, int MSPLIT, int NSPLIT, int KSPLIT, int PH, int PW>
+static int segwgrad_f32_launch(hipStream_t st, const float* x, const float* dz, float* dw, int n_segments, segw_bn bn) {
     typedef segwf_cfg<CI, CO, H, W, WO, PADW, SEGS, MSPLIT, NSPLIT, KSPLIT> C;
-    static std::atomic<bool> attr[SC_MAX_DEV];
-    const int dev = sc_device();
-    if (!attr[dev].load(std::memory_order_relaxed)) {
-        (void)hipFuncSetAttribute((const void*)segwgrad_f32_kernel<CI, CO, H, W, WO, PADW, SEGS, MSPLIT, NSPLIT, KSPLIT, PH, PW>,
-                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)C::LDS);
-        attr[dev].store(true, std::memory_order_relaxed);
-    }
+    const auto kernel = segwgrad_f32_kernel<CI, CO, H, W, WO, PADW, SEGS, MSPLIT, NSPLIT, KSPLIT, PH, PW>;
+    static std::atomic<bool> lds_ok[64];
+    if (nq_lds_opt_in((const void*)kernel, (int)C::LDS, lds_ok)) return 2;
     const int n_groups = (n_segments + SEGS - 1) / SEGS;
-    const int grid = n_groups < sc_cu_count() ? n_groups : sc_cu_count();
-    hipLaunchKernelGGL((segwgrad_f32_kernel<CI, CO, H, W, WO, PADW, SEGS, MSPLIT, NSPLIT, KSPLIT, PH, PW>), dim3(grid), dim3(512), C::LDS, st,
-                       x, dz, dw, n_segments, bn);
+    hipLaunchKernelGGL(kernel, dim3(n_groups < sc_cu_count() ? n_groups : sc_cu_count()), dim3(512), C::LDS, st, x, dz, dw, n_segments, bn);
+    return 0;
 }
 
-// exact fp32, same five shapes and the same contract as nisqa_segconv_wgrad_bf16 / nisqa_segconv_wgrad_bn_bf16 (z == NULL: dz_out
-// holds dz on entry and nothing is folded; otherwise the BatchNorm backward runs inside and dz_out, dgamma, dbeta are written)
+// segments per group and the split of the eight waves over (M tiles) x (N tiles) x (K steps), per shape
+struct segwf_tile { int segs, msplit, nsplit, ksplit; };
+static constexpr segwf_tile SEGWF_TILE[sc_shapes::N] = {
+    //  24x7 16>32    12x5 32>64    12x5 64>64    6x3 64>64     6x3 64>64 pad 0
+    {1, 1, 1, 8}, {1, 2, 2, 2}, {1, 2, 4, 1}, {4, 2, 4, 1}, {8, 2, 4, 1},
+};
+// exact fp32, the same contract as nisqa_segconv_wgrad_bf16 / nisqa_segconv_wgrad_bn_bf16 (z == NULL: dz_out holds dz on entry and
+// nothing is folded; otherwise the BatchNorm backward runs inside and dz_out, dgamma, dbeta are written)
 extern "C" int nisqa_segconv_wgrad_f32(const float* x, const float* z, const float* dy, const int32_t* arg, const float* drop,
                                        const float* mean_rstd, const float* gamma, const float* beta, const double* sums2,
                                        float* dz_out, float* dgamma, float* dbeta, float* dw, int32_t n_segments, int32_t h, int32_t w,
                                        int32_t ci, int32_t co, int32_t pad_w, int32_t ho, int32_t wo, void* stream) {
-    if (!x || !dz_out || !dw || n_segments <= 0 || !nisqa_segconv_supported(h, w, ci, co, pad_w)) return NISQA_ERR_ARG;
-    const bool fold = z != nullptr;
-    if (fold && (!dy || !arg || !mean_rstd || !gamma || !beta || !sums2 || !dgamma || !dbeta)) return NISQA_ERR_ARG;
-    hipStream_t st = (hipStream_t)stream;
     const segw_bn bn = {z, dy, arg, drop, mean_rstd, gamma, beta, sums2, dz_out, dgamma, dbeta};
-    const int key = SC_KEY(h, w, ci, co);
-    NQ_LAUNCH_BEGIN();
-    if (!fold) {
-        if (key == SC_KEY(24, 7, 16, 32)) segwgrad_f32_launch<16, 32, 24, 7, 7, 1, 1, 1, 1, 8>(st, x, dz_out, dw, n_segments);
-        else if (key == SC_KEY(12, 5, 32, 64)) segwgrad_f32_launch<32, 64, 12, 5, 5, 1, 1, 2, 2, 2>(st, x, dz_out, dw, n_segments);
-        else if (key == SC_KEY(12, 5, 64, 64)) segwgrad_f32_launch<64, 64, 12, 5, 5, 1, 1, 2, 4, 1>(st, x, dz_out, dw, n_segments);
-        else if (pad_w == 1) segwgrad_f32_launch<64, 64, 6, 3, 3, 1, 4, 2, 4, 1>(st, x, dz_out, dw, n_segments);
-        else segwgrad_f32_launch<64, 64, 6, 3, 1, 0, 8, 2, 4, 1>(st, x, dz_out, dw, n_segments);
-        return NQ_LAUNCH_STATUS();
-    }
-    if (key == SC_KEY(24, 7, 16, 32) && ho == 12 && wo == 5) segwgrad_f32_launch<16, 32, 24, 7, 7, 1, 1, 1, 1, 8, 12, 5>(st, x, nullptr, dw, n_segments, bn);
-    else if (key == SC_KEY(12, 5, 32, 64) && ho == 12 && wo == 5) segwgrad_f32_launch<32, 64, 12, 5, 5, 1, 1, 2, 2, 2, 12, 5>(st, x, nullptr, dw, n_segments, bn);
-    else if (key == SC_KEY(12, 5, 64, 64) && ho == 6 && wo == 3) segwgrad_f32_launch<64, 64, 12, 5, 5, 1, 1, 2, 4, 1, 6, 3>(st, x, nullptr, dw, n_segments, bn);
-    else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 1 && ho == 6 && wo == 3) segwgrad_f32_launch<64, 64, 6, 3, 3, 1, 4, 2, 4, 1, 6, 3>(st, x, nullptr, dw, n_segments, bn);
-    else if (key == SC_KEY(6, 3, 64, 64) && pad_w == 0 && ho == 6 && wo == 1) segwgrad_f32_launch<64, 64, 6, 3, 1, 0, 8, 2, 4, 1, 6, 1>(st, x, nullptr, dw, n_segments, bn);
-    else return NISQA_ERR_ARG;
-    return NQ_LAUNCH_STATUS();
+    const bool fold = z != nullptr;
+    if (!segw_args_ok(x, dz_out, dw, n_segments, fold ? &bn : nullptr)) return NISQA_ERR_ARG;
+    return sc_shapes::for_shape(h, w, ci, co, pad_w, [&](auto shape) -> int {
+        typedef decltype(shape) S;
+        constexpr segwf_tile T = SEGWF_TILE[S::I];
+        if (fold && (ho != S::PH || wo != S::PW)) return NISQA_ERR_ARG;
+        hipStream_t st = (hipStream_t)stream;
+        NQ_LAUNCH_BEGIN();
+        const int rc = fold ? segwgrad_f32_launch<S::CI, S::CO, S::H, S::W, S::WO, S::PADW, T.segs, T.msplit, T.nsplit, T.ksplit, S::PH, S::PW>(st, x, nullptr, dw, n_segments, bn)
+                            : segwgrad_f32_launch<S::CI, S::CO, S::H, S::W, S::WO, S::PADW, T.segs, T.msplit, T.nsplit, T.ksplit, 0, 0>(st, x, dz_out, dw, n_segments, segw_bn{});
+        return rc ? rc : NQ_LAUNCH_STATUS();
+    });
 }

@@ -569,6 +569,122 @@ def test_abi_argument_validation_without_gpu():
     assert L.nisqa_pool_att(None, None, None, 1, 32, 9, None, None, None, None) == lib.NISQA_ERR_ARG
 
 
+def test_segconv_entry_points_validate_without_gpu():
+    """The segment-resident convolutions of the training step: the shape predicate, the fragment sizes and every argument check
+    of the forward / input-gradient / weight-gradient / pack entries.  Every call here is one the library rejects before it
+    launches (no GPU is needed); pointers that only have to be non-NULL are the integer P, which a rejected call never reads."""
+    import ctypes
+    from nisqa_amd import lib
+    L, ERR, P = lib.load(), lib.NISQA_ERR_ARG, 0x1000
+    # (h, w, ci, co, pad_w) -> the pooled size (ho, wo) the folded weight gradients take
+    shapes = {(24, 7, 16, 32, 1): (12, 5), (12, 5, 32, 64, 1): (12, 5), (12, 5, 64, 64, 1): (6, 3), (6, 3, 64, 64, 1): (6, 3),
+              (6, 3, 64, 64, 0): (6, 1)}
+    tried = set()
+    for s in shapes:
+        assert L.nisqa_segconv_supported(*s) == 1, s
+        for field, steps in enumerate([(-1, 1, s[0], -(s[0] // 2)), (-2, -1, 1, 2), (-16, 16, s[2]), (-16, 16, s[3]), (-1, 1, 2)]):
+            for d in steps:
+                n = list(s)
+                n[field] += d
+                tried.add(tuple(n))
+    assert len(tried) > 60 and (24, 7, 16, 32, 0) in tried and (24, 8, 16, 32, 1) in tried and (6, 3, 64, 64, 2) in tried
+    for n in sorted(tried):
+        assert L.nisqa_segconv_supported(*n) == (1 if n in shapes else 0), n
+
+    # fragment bytes of every supported (mode, ci, co): plain (bf16 hi + lo), three-term, f16 (+ 16: the scale exponent), fp32
+    sizes = {(0, 16, 32): (18432, 27648, 18448, 18432), (1, 16, 32): (36864, 55296, 36880, 36864),
+             (0, 32, 64): (73728, 110592, 73744, 73728), (1, 32, 64): (73728, 110592, 73744, 73728),
+             (0, 64, 64): (147456, 221184, 147472, 147456), (1, 64, 64): (147456, 221184, 147472, 147456)}
+    frag_bytes = [L.nisqa_segconv_frag_bytes, L.nisqa_segconv_frag_bytes_x6, L.nisqa_segconv_frag_bytes_f16, L.nisqa_segconv_frag_bytes_f32]
+    for key, want in sizes.items():
+        assert tuple(f(*key) for f in frag_bytes) == want, key
+    for bad in [(2, 16, 32), (-1, 16, 32), (0, 8, 32), (0, 24, 32), (0, 16, 0), (1, 16, 40), (0, 0, 0)]:
+        assert [f(*bad) for f in frag_bytes] == [-1] * 4, bad
+
+    # ---- forward / input gradient: (mode, src, frags, out, n_segments, h, w, ci, co, pad_w, bias, stats2c, stream)
+    for f in (L.nisqa_segconv_bf16, L.nisqa_segconv_f16, L.nisqa_segconv_f32, L.nisqa_segconv_bf16x6):
+        for s in shapes:
+            for mode in (-1, 2):
+                assert f(mode, P, P, P, 4, *s, None, None, None) == ERR
+            for n_seg in (0, -1):
+                assert f(0, P, P, P, n_seg, *s, None, None, None) == ERR
+                assert f(1, P, P, P, n_seg, *s, None, None, None) == ERR
+            for mode in (0, 1):
+                for k in range(3):
+                    ptrs = [P, P, P]
+                    ptrs[k] = None
+                    assert f(mode, *ptrs, 4, *s, None, None, None) == ERR
+            assert f(1, P, P, P, 4, *s, P, None, None) == ERR             # an input gradient has no bias ...
+            assert f(1, P, P, P, 4, *s, None, P, None) == ERR             # ... and no statistics
+        for n in sorted(tried - set(shapes)):
+            assert f(0, P, P, P, 4, *n, None, None, None) == ERR, n
+            assert f(1, P, P, P, 4, *n, None, None, None) == ERR, n
+
+    # ---- weight gradient, plain: (x, dz, dw, n_segments, h, w, ci, co, pad_w, stream)
+    for s in shapes:
+        for k in range(3):
+            ptrs = [P, P, P]
+            ptrs[k] = None
+            assert L.nisqa_segconv_wgrad_bf16(*ptrs, 4, *s, None) == ERR
+        assert L.nisqa_segconv_wgrad_bf16(P, P, P, 0, *s, None) == ERR
+    for n in sorted(tried - set(shapes)):
+        assert L.nisqa_segconv_wgrad_bf16(P, P, P, 4, *n, None) == ERR, n
+
+    # ---- weight gradient with the BatchNorm backward folded in:
+    #      (x, z, dy, arg, drop, mean_rstd, gamma, beta, sums2, dz_out, dgamma, dbeta, dw, n_segments, h, w, ci, co, pad_w, ho, wo, stream)
+    # nisqa_segconv_wgrad_bn_bf16 folds always; the other two fold when z != NULL and read dz from dz_out otherwise
+    DROP, Z = 4, 1
+    for f in (L.nisqa_segconv_wgrad_bn_bf16, L.nisqa_segconv_wgrad_bf16x6, L.nisqa_segconv_wgrad_f32):
+        always = f is L.nisqa_segconv_wgrad_bn_bf16
+        for s, own in shapes.items():
+            for k in range(13):
+                if k == DROP or (k == Z and not always):            # drop may be NULL; z == NULL selects the plain form
+                    continue
+                ptrs = [P] * 13
+                ptrs[k] = None
+                assert f(*ptrs, 4, *s, *own, None) == ERR, (s, k)
+            for n_seg in (0, -1):
+                assert f(*[P] * 13, n_seg, *s, *own, None) == ERR
+            for pooled in set(shapes.values()) | {(0, 0), (own[1], own[0]), (own[0] + 1, own[1]), (own[0], own[1] + 1)}:
+                if pooled != own:
+                    assert f(*[P] * 13, 4, *s, *pooled, None) == ERR, (s, pooled)
+            if not always:                                          # the plain form: x, dz_out, dw are needed
+                for k in (0, 9, 12):
+                    ptrs = [P] + [None] * 8 + [P, None, None, P]
+                    ptrs[k] = None
+                    assert f(*ptrs, 4, *s, *own, None) == ERR, (s, k)
+                assert f(*[P] + [None] * 8 + [P, None, None, P], 0, *s, *own, None) == ERR
+            else:
+                assert f(*[P, None] + [P] * 11, 4, *s, *own, None) == ERR
+        for n in sorted(tried - set(shapes)):
+            for pooled in set(shapes.values()):
+                assert f(*[P] * 13, 4, *n, *pooled, None) == ERR, n
+            if not always:
+                assert f(*[P] + [None] * 8 + [P, None, None, P], 4, *n, 0, 0, None) == ERR, n
+    assert L.nisqa_segconv_wgrad_bn_bf16(*[P] * 13, 4, 24, 7, 16, 32, 1, 6, 3, None) == ERR
+
+    # ---- packing: (n_jobs, modes, w, ci, co, frags, stream), HOST arrays of n_jobs entries
+    def jobs(n, mode=0, w=P, ci=16, co=32, frag=P):
+        return [(ctypes.c_int32 * n)(*[mode] * n), (ctypes.c_void_p * n)(*[w] * n), (ctypes.c_int32 * n)(*[ci] * n),
+                (ctypes.c_int32 * n)(*[co] * n), (ctypes.c_void_p * n)(*[frag] * n)]
+    for f in (L.nisqa_segconv_pack_many, L.nisqa_segconv_pack_x6_many, L.nisqa_segconv_pack_f16_many, L.nisqa_segconv_pack_f32_many):
+        for n_jobs in (0, -1, 11):
+            assert f(n_jobs, *jobs(11), None) == ERR
+        for k in range(5):
+            arrays = jobs(2)
+            arrays[k] = None
+            assert f(2, *arrays, None) == ERR
+        for bad in (dict(mode=2), dict(mode=-1), dict(w=None), dict(frag=None), dict(ci=8), dict(ci=24), dict(co=0), dict(co=40)):
+            assert f(3, *jobs(3, **bad), None) == ERR, bad
+            arrays = jobs(3, **bad)                                  # ... also when only the LAST job is bad
+            good = jobs(3)
+            for k in range(5):
+                good[k][2] = arrays[k][2]
+            assert f(3, *good, None) == ERR, bad
+    for bad in [(2, P, 16, 32, P), (0, None, 16, 32, P), (0, P, 16, 32, None), (0, P, 8, 32, P), (1, P, 16, 40, P)]:
+        assert L.nisqa_segconv_pack(*bad, None) == ERR
+
+
 def test_engine_fails_loudly_without_gpu():
     if torch.cuda.is_available():
         pytest.skip('GPU present')
