@@ -1,8 +1,19 @@
-// The whole AdaptCNN (conv1..conv6, BatchNorm folded, adaptive max-pools) on split-bf16 MFMA ("bf16x3") --
-// same role, inputs and outputs as cnn_front_kernel + cnn_back_kernel in cnn.hip (reference
-// nisqa/NISQA_lib.py:2239-2282, 487-502, 688-710).
+// The whole AdaptCNN (conv1..conv6, BatchNorm folded, adaptive max-pools) on the 16-bit matrix pipe -- same role, inputs and
+// outputs as cnn_front_kernel + cnn_back_kernel in cnn.hip (reference nisqa/NISQA_lib.py:2239-2282, 487-502, 688-710).
+// ONE source for the four 16-bit operand formats (conv_bf16.hpp): the two-term bf16x3 / f16x3 / f16x4 and the three-term
+// bf16x6, the default.  The geometry (window staging, row -> pixel maps, tap masks, pooling windows, shared S4 / S5 planes,
+// feature store) is written once over T planes per tensor; what belongs to a format's arithmetic or to its measured schedule
+// sits behind `if constexpr`: the product order, the K loop (fb_conv_k), the f16 scales and the three-term form's preloads
+// and scheduling fences.
 //
-// Every fp32 operand x is carried as x = hi + lo with hi = bf16(x), lo = bf16(x - hi) (16 mantissa
+// "bf16x6": every fp32 operand x is carried as THREE bf16 terms x = hi + mid + lo (8 + 8 + 8 significant bits, each rounded to
+// nearest: the split is EXACT, no bit of the fp32 value is lost) and a product is formed as the six MFMA products hh + hm + mh +
+// hl + lh + mm on v_mfma_f32_32x32x16_bf16 with fp32 accumulation.  The three dropped products (ml, lm, ll) are at most
+// 2 x 2^-24 of the product and typically 0.5 x 2^-24 rms -- the size of the rounding an fp32 multiply-add applies to the same
+// product.  Against float64 the results are as close as the exact-fp32 MFMA kernels' (tests/test_gpu_parity.py:
+// test_rounding_error_of_the_precision_modes_against_float64; DESIGN.md 4.5 "bf16x6"), at 16 / 6 = 2.7 x their matrix-pipe rate.
+//
+// "bf16x3": every fp32 operand x is carried as x = hi + lo with hi = bf16(x), lo = bf16(x - hi) (16 mantissa
 // bits) and each product is formed as hi*hi + hi*lo + lo*hi on v_mfma_f32_32x32x16_bf16 with fp32
 // accumulation: 3 MFMAs at 16x the fp32-MFMA rate = 5.3x the exact-fp32 throughput.  Dropped term:
 // lo*lo ~ 2^-18.  conv1 sees dB values up to |80|: two terms resolve them to 6e-4 dB, the size of the mel
@@ -12,12 +23,16 @@
 // Structure:
 //   * a workgroup is FOUR waves = four consecutive segments of one clip; conv1..conv4 are wave-private and barrier-free:
 //     each wave streams its weight fragments from L2 into a 3-deep register ring (conv_k_bf16) and keeps its
-//     activations in its own LDS region as two bf16 planes (hi, lo), pixel-major with pixel rows padded by 16 bytes, with
-//     row -> pixel maps chosen so that every adaptive-max-pool window is in-lane;
-//   * conv1 runs on the matrix pipe too, two mel-adjacent output pixels per MFMA row (operands are dword reads from two
-//     zero-bordered bf16 planes of the input patch, no packing);
+//     activations in its own LDS region as T 16-bit planes (hi, lo / hi, mid, lo), pixel-major with pixel rows padded by 16
+//     bytes, with row -> pixel maps chosen so that every adaptive-max-pool window is in-lane;
+//   * conv1 runs on the matrix pipe too, two mel-adjacent output pixels per MFMA row (operands are dword reads from the
+//     zero-bordered planes of the input patch, no packing);
 //   * conv5/conv6 (18 / 6 output pixels per segment) are batched over the workgroup's four segments with the output
-//     channels split over the waves (16x16x32 MFMA tiles), so no tile is mostly padding.
+//     channels split over the waves (16x16x32 MFMA tiles), so no tile is mostly padding;
+//   * T = 2: 79 KB of LDS per workgroup, two workgroups (two waves per SIMD) per CU.  T = 3: 117 KB, ONE workgroup per CU, one
+//     wave per SIMD on the 512-register budget -- the K loops keep the A rows of the next step and two steps of weight fragments
+//     in flight themselves and are opened a phase ahead (conv_k_terms_ring; tools/micro/klx6.hip: 96 % matrix-pipe duty at
+//     1.79 GHz in the conv3 + conv4 loops, the chip's power envelope).
 // What bounds it (tools/micro/issue2.hip): a wave hides <= 5 other instructions behind a 32x32x16 MFMA
 // (<= 2 behind a 16x16x32) and a VALU-only stream issues one instruction per ~5 cycles, so every instruction outside the
 // MFMA shadows counts.  Hence: LDS by 32-bit addresses (no 64-bit pointer arithmetic), lane-static tap masks instead of
@@ -46,23 +61,27 @@
 #define FB_RS3 144                         /* A3: 60 px x 64 ch; S4 / S5: 72 rows x 64 ch */
 #define FB_P3 (60 * FB_RS3)
 #define FB_PS (72 * FB_RS3)
-#define FB_PATCH (2 * FB_P1)               /* conv1 input: two zero-bordered bf16 planes [17][50] behind the A1 planes */
-#define FB_PPLANE 1700                     /* bytes per patch plane (850 bf16) */
+#define FB_PATCH(T) ((T) * FB_P1)          /* conv1 input: T zero-bordered 16-bit planes [17][50] behind the T A1 planes */
+#define FB_PPLANE 1700                     /* bytes per patch plane (850 x 16 bit) */
 #define FB_ZADDR 2048u                     /* the shared zero block */
 #define FB_BASE 2176u                      /* first wave region */
-#define FB_WAVE 19584u
-#define FB_WGS 2
-#define FB_LDS (FB_BASE + 4 * FB_WAVE)     /* 80512 B -> two workgroups (8 waves) per CU */
-static_assert(FB_PATCH + 2 * FB_PPLANE <= FB_WAVE && 2 * FB_P3 <= FB_WAVE && 2 * FB_PS <= 2 * FB_WAVE, "LDS plan");
-static_assert(FB_WGS * FB_LDS <= 160 * 1024, "workgroups per CU");
+#define FB_WAVE(T) (((T) * (FB_P1 + FB_PPLANE) + 63u) / 64u * 64u)   /* A1 + patch, the widest tenant */
+#define FB_WGS(T) ((T) == 2 ? 2 : 1)       /* workgroups per CU, the kernels' __launch_bounds__ */
+#define FB_LDS(T) (FB_BASE + 4 * FB_WAVE(T))
+static_assert(FB_WAVE(2) == 19584 && FB_LDS(2) == 80512 && 2 * FB_LDS(2) <= 160 * 1024, "two terms: two workgroups (8 waves) per CU");
+static_assert(FB_WAVE(3) == 29312 && FB_LDS(3) == 119424 && FB_LDS(3) <= 160 * 1024 && 2 * FB_LDS(3) > 160 * 1024, "three terms: one workgroup per CU");
+#define FB_PLAN_OK(T) (FB_PATCH(T) + (T) * FB_PPLANE <= FB_WAVE(T) && (T) * FB_P3 <= FB_WAVE(T) && (T) * FB_PS <= 2 * FB_WAVE(T))
+static_assert(FB_PLAN_OK(2) && FB_PLAN_OK(3), "LDS plan");
 
 __device__ constexpr int bwin75_lo(int b) { return b == 0 ? 0 : b == 1 ? 1 : b == 2 ? 2 : b == 3 ? 4 : 5; }
 __device__ constexpr int bwin75_hi(int b) { return b == 0 ? 2 : b == 1 ? 3 : b == 2 ? 5 : b == 3 ? 6 : 7; }
 __device__ constexpr int bwin53_lo(int b) { return b == 0 ? 0 : b == 1 ? 1 : 3; }
 __device__ constexpr int bwin53_hi(int b) { return b == 0 ? 2 : b == 1 ? 4 : 5; }
 
-// layer-boundary stamps of the phase clock (tools/phase_clock.py; empty macros unless the unit is built with -DNQ_EXPERIMENTAL)
+// layer-boundary stamps of the phase clock (tools/phase_clock.py; empty macros unless the unit is built with -DNQ_EXPERIMENTAL):
+// one slot array for the two-term kernels, one for the three-term kernel (NQ_PRECISION=bf16x6)
 NQ_CLK_EXPORT(g_phase_clk, nisqa_debug_phase_clock)
+NQ_CLK_EXPORT(g_phase_clk6, nisqa_debug_phase_clock6)
 
 // the per-row scale tables of the f16 formats' conv5 / conv6 epilogues (the LDS below the zero block is otherwise unused)
 #define FB_TAB5 0u                         /* [72 rows] {2^(e5 - e4 - kw5), 2^e5} of the row's segment */
@@ -71,10 +90,24 @@ NQ_DEV f32x2_t lds_ld64(unsigned a) { return *(NQ_AS3 const f32x2_t*)(a); }
 // bias + ReLU of an epilogue value; the f16 formats fold the power-of-two scales in: relu(v * c + t) with c = 2^(e_out - e_in - kw),
 // t = shift * 2^e_out -- exact scalings, so the result is 2^e_out times what the unscaled arithmetic rounds to
 template <int FMT>
-NQ_DEV float epi_fmt(float v, float c, float t) { return FMT == NQ_FMT_BF16X3 ? fmaxf(v + t, 0.f) : fmaxf(fmaf(v, c, t), 0.f); }
+NQ_DEV float epi_fmt(float v, float c, float t) {
+    return FMT == NQ_FMT_BF16X3 || FMT == NQ_FMT_BF16X6 ? fmaxf(v + t, 0.f) : fmaxf(fmaf(v, c, t), 0.f);
+}
 
-// FMT: operand format (conv_bf16.hpp): bf16 hi + lo / three products, or f16 hi + lo of the power-of-two-scaled tensors with three or
-//      all four products.  For the f16 formats wb is the CNNH_ blob (fragments of W * 2^kw + per-layer constants) and every activation
+// The K loop of one 3 x 3 layer in the format's own form (conv_bf16.hpp).  Three terms: conv_k_terms_ring, A rows one step ahead,
+// a fence behind every step's requests, and the first two steps of fragments already in `ring` (requested by the caller a phase
+// ahead).  Two terms: conv_k_bf16 with the layer's APF and ring depth, no fences (two waves per SIMD fill each other's stalls; the
+// same fence measured slower there) -- `ring` is unused.
+template <int FMT, int CIN, int MT, int NT, int W, int RS, int PLANE, bool APF, int RING>
+NQ_DEV void fb_conv_k(f32x16 (&acc)[MT][NT], __amdgpu_buffer_rsrc_t wrs, int wbyte, unsigned lane16, const unsigned (&base)[MT],
+                      const unsigned (&m9)[MT], conv_k_ring<FMT == NQ_FMT_BF16X6 ? 3 : 2, NT, 3>& ring) {
+    if constexpr (FMT == NQ_FMT_BF16X6) conv_k_terms_ring<3, CIN, MT, NT, W, RS, PLANE, FB_ZADDR, 3, true, true>(acc, wrs, wbyte, lane16, base, m9, ring);
+    else conv_k_bf16<CIN, MT, NT, W, RS, PLANE, FB_ZADDR, APF, RING, FMT>(acc, wrs, wbyte, lane16, base, m9);
+}
+
+// FMT: operand format (conv_bf16.hpp): bf16 hi + lo / three products, bf16 hi + mid + lo / six products (wb: the CNNX_ blob), or f16
+//      hi + lo of the power-of-two-scaled tensors with three or all four products.
+//      For the f16 formats wb is the CNNH_ blob (fragments of W * 2^kw + per-layer constants) and every activation
 //      tensor is stored as y * 2^e with e = 15 - ceil(log2(m_in * G + T)): m_in the MEASURED maximum of the layer's input for this
 //      segment, G = max_c sum |W_c| and T = max |shift| of the layer -- |y| <= m_in * G + T, so the scaled tensor stays below 2^15 for
 //      any finite input and any weights (no calibration, no clamping), 3-5 bits below it for the shipped weights.
@@ -89,8 +122,12 @@ NQ_DEV void cnn_front_split_body(
     float* __restrict__ feat, const float* __restrict__ seg_x, int seg_L,
     const uint32_t* __restrict__ clip_max_enc, float top_db) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
-    constexpr bool F16 = FMT != NQ_FMT_BF16X3;
-    static_assert(!(F16 && P3), "the fp32 copy of the pooled conv4 tensor is a bf16x3 debug output");
+    constexpr bool X6 = FMT == NQ_FMT_BF16X6, F16 = FMT == NQ_FMT_F16X3 || FMT == NQ_FMT_F16X4;
+    constexpr int T = X6 ? 3 : 2;                         // terms per operand = planes per tensor
+    static_assert(!P3 || FMT == NQ_FMT_BF16X3, "the fp32 copy of the pooled conv4 tensor is a bf16x3 debug output");
+    // fragment blob of the term count: CNNB_ (two terms, also the CNNH_ blob of the f16 formats) or CNNX_ (three)
+    constexpr int W1_ = X6 ? CNNX_W1 : CNNB_W1, W2_ = X6 ? CNNX_W2 : CNNB_W2, W3_ = X6 ? CNNX_W3 : CNNB_W3, W4_ = X6 ? CNNX_W4 : CNNB_W4,
+                  W5_ = X6 ? CNNX_W5 : CNNB_W5, W6_ = X6 ? CNNX_W6 : CNNB_W6, WU16_ = X6 ? CNNX_U16S : CNNB_U16S;
     // F16: per-layer constants behind the fragments (layout.hpp CNNH_META): kw[l], G[l], T[l] for l = 1..6 at index l - 1
     const int* __restrict__ meta_i = (const int*)(wb + CNNH_META);
     const float* __restrict__ meta_f = (const float*)(wb + CNNH_META);
@@ -105,12 +142,12 @@ NQ_DEV void cnn_front_split_body(
     if (nvalid <= 0) return;                             // whole workgroup is padding
     const bool valid = wave < nvalid;                    // padding waves still walk the barriers (on zeros)
     const int p = p0 + wave, k = k0 + wave;
-    const unsigned R = FB_BASE + wave * FB_WAVE;         // this wave's LDS region
+    const unsigned R = FB_BASE + wave * FB_WAVE(T);      // this wave's LDS region
     const unsigned lane16 = lane * 16;
-    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)wb, 0, CNNB_U16S * 2, 0x00020000);
+    const __amdgpu_buffer_rsrc_t wrs = __builtin_amdgcn_make_buffer_rsrc((void*)wb, 0, WU16_ * 2, 0x00020000);
     NQ_STAMP(0);
 
-    // ---- stage the 15-frame window as two zero-bordered bf16 planes (hi, lo) [frame j + 1][mel m + 1]:
+    // ---- stage the 15-frame window as T zero-bordered 16-bit planes [frame j + 1][mel m + 1]:
     //      the 3x3 taps of any output pixel are then at constant offsets from it, no bounds checks.
     //      All 12 global loads of the window (and the per-channel shifts of every layer) are requested up front: one
     //      memory latency instead of twelve.
@@ -145,11 +182,12 @@ NQ_DEV void cnn_front_split_body(
         s0 = pow2_f32(e_in);
     }
     {
-        const unsigned pb = R + FB_PATCH;
-        // zero the patch planes (213 x 16 bytes) and the shared zero block (every wave writes the same zeros)
+        const unsigned pb = R + FB_PATCH(T);
+        // zero the patch planes (213 / 319 x 16 bytes) and the shared zero block (every wave writes the same zeros)
+        constexpr int NZ = (T * FB_PPLANE + 15) / 16;
 #pragma unroll
-        for (int it = 0; it < 4; ++it)
-            if (it < 3 || lane < (2 * FB_PPLANE + 15) / 16 - 192) lds_st128(pb + (lane + 64 * it) * 16, f32x4{0.f, 0.f, 0.f, 0.f});
+        for (int it = 0; it < (NZ + 63) / 64; ++it)
+            if (64 * it + 64 <= NZ || lane < NZ - 64 * it) lds_st128(pb + (lane + 64 * it) * 16, f32x4{0.f, 0.f, 0.f, 0.f});
         // (this store goes through the dynamic-LDS symbol on purpose: a kernel that only touches LDS through integer
         // addresses is compiled as one that uses no LDS at all, and then computes garbage)
         if (lane < 32) ((unsigned*)(smem + FB_ZADDR))[lane] = 0u;
@@ -190,10 +228,14 @@ NQ_DEV void cnn_front_split_body(
     //      dmm), dmm = 0..3: the four mels of one kx are CONTIGUOUS in the bordered patch, so the 8 k-slots of a lane are
     //      two pairs of dwords per plane and no packing.  B[k][n] = w[c][dmm - dm][kx] (zero outside the kernel), packed
     //      by weights.py.  Each lane half owns 12 pooled rows gl = mel pairs; the 16 rows of its tile are the frames.
+    // X6 (one wave per SIMD: nobody else covers the L2 round trip a K loop otherwise opens with): the first two K steps of
+    // conv2's fragments travel while conv1 runs; conv3's are requested above conv2's epilogue, conv4's above conv3's
+    conv_k_ring<T, 1, 3> ring2;
+    if constexpr (X6) conv_k_preload(ring2, wrs, W2_ * 2, lane16);
     {
-        f32x4 w1[2];                                      // weights hi and the first residual term (16 mantissa bits)
+        f32x4 w1[1][T];                                   // two terms: weights hi and the first residual term (16 mantissa bits)
 #pragma unroll
-        for (int t = 0; t < 2; ++t) w1[t] = wfrag_load(wrs, lane16, (CNNB_W1 + t * 512) * 2);
+        for (int t = 0; t < T; ++t) w1[0][t] = wfrag_load(wrs, lane16, (W1_ + t * 512) * 2);
         // F16: |y1| <= m0 * G1 + T1 fixes the scale of conv1's output before its first store
         float tn = tn1, c1 = 1.f, ms1 = 0.f;
         int e1 = 0;
@@ -204,41 +246,47 @@ NQ_DEV void cnn_front_split_body(
         }
         // lane half 0: k-slots 0..7 = (kx 0, kx 1); half 1: k-slots 8..11 = kx 2 (12..15 meet zero weights: kx 2 again)
         const int xq = min(qi, 14);                       // row 15 of a tile is padding (result unused)
-        unsigned rd_a = R + FB_PATCH + ((xq + (h ? 2 : 0)) * 50 + 24 * hfi) * 2;
-        unsigned rd_b = R + FB_PATCH + ((xq + (h ? 2 : 1)) * 50 + 24 * hfi) * 2;
+        unsigned rd_a = R + FB_PATCH(T) + ((xq + (h ? 2 : 0)) * 50 + 24 * hfi) * 2;
+        unsigned rd_b = R + FB_PATCH(T) + ((xq + (h ? 2 : 1)) * 50 + 24 * hfi) * 2;
         // The pooled value of a mel pair needs both pair members, which sit 16 lanes apart (columns n and n ^ 16).  Of the
         // 14 pooled values of an iteration (2 mel pairs x 7 frame windows, consecutive pixels v = 7 tt + bb of A1), lane
         // group dm = 0 finalises the even ones and dm = 1 the odd ones: each sends the partner the values it does not own
-        // (ONE ds_swizzle per value pair), takes the maximum, splits it into hi + lo and stores both planes.
+        // (ONE ds_swizzle per value pair), takes the maximum, splits it into its terms and stores the planes.
         const bool is_b = (n & 16) != 0;
         const unsigned mb = is_b ? ~0u : 0u;             // bit select (v_bfi_b32): a ternary on r[] becomes an indexed stack array
         unsigned wr = R + (12 * hf * 7) * FB_RS1 + (n & 15) * 2 + (is_b ? FB_RS1 : 0);
         for (int g2 = 0; g2 < 6; ++g2) {
-            f32x16 acc[2];
-            f32x4 xa[2][2];
+            f32x16 acc[2][1];
+            f32x4 xa[2][T];
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
-                for (int t = 0; t < 2; ++t) {              // dword reads (ds_read2_b32): the pairs are only 4-byte aligned
+                for (int t = 0; t < T; ++t) {              // dword reads (ds_read2_b32): the pairs are only 4-byte aligned
                     const unsigned pa = rd_a + 4 * tt + t * FB_PPLANE, pq = rd_b + 4 * tt + t * FB_PPLANE;
                     xa[tt][t] = f32x4{__uint_as_float(lds_ld32(pa)), __uint_as_float(lds_ld32(pa + 4)),
                                       __uint_as_float(lds_ld32(pq)), __uint_as_float(lds_ld32(pq + 4))};
                 }
-            acc[0] = zero16();
-            acc[1] = zero16();
-            // x = hi + lo carries 16 mantissa bits: 6e-4 dB at |80| dB, the size of the mel stage's own deviation from
-            // the oracle (2.6e-4 dB) and three orders below what moves a MOS by 1e-3; smallest products first
-            if (FMT == NQ_FMT_F16X4) { acc[0] = mfma32_fmt<FMT>(xa[0][1], w1[1], acc[0]); acc[1] = mfma32_fmt<FMT>(xa[1][1], w1[1], acc[1]); }
-            acc[0] = mfma32_fmt<FMT>(xa[0][1], w1[0], acc[0]); acc[1] = mfma32_fmt<FMT>(xa[1][1], w1[0], acc[1]);
-            acc[0] = mfma32_fmt<FMT>(xa[0][0], w1[1], acc[0]); acc[1] = mfma32_fmt<FMT>(xa[1][0], w1[1], acc[1]);
-            acc[0] = mfma32_fmt<FMT>(xa[0][0], w1[0], acc[0]); acc[1] = mfma32_fmt<FMT>(xa[1][0], w1[0], acc[1]);
+            acc[0][0] = zero16();
+            acc[1][0] = zero16();
+            if constexpr (X6) {
+                mma_terms<T, 2, 1>(acc, xa, w1);           // the dB input and the weights are exact in their three terms
+            } else {
+                // x = hi + lo carries 16 mantissa bits: 6e-4 dB at |80| dB, the size of the mel stage's own deviation from
+                // the oracle (2.6e-4 dB) and three orders below what moves a MOS by 1e-3; smallest products first (this
+                // layer's own order: x_lo w_hi before x_hi w_lo, not mma_pair_fmt's)
+                const f32x4 (&w)[T] = w1[0];
+                if (FMT == NQ_FMT_F16X4) { acc[0][0] = mfma32_fmt<FMT>(xa[0][1], w[1], acc[0][0]); acc[1][0] = mfma32_fmt<FMT>(xa[1][1], w[1], acc[1][0]); }
+                acc[0][0] = mfma32_fmt<FMT>(xa[0][1], w[0], acc[0][0]); acc[1][0] = mfma32_fmt<FMT>(xa[1][1], w[0], acc[1][0]);
+                acc[0][0] = mfma32_fmt<FMT>(xa[0][0], w[1], acc[0][0]); acc[1][0] = mfma32_fmt<FMT>(xa[1][0], w[1], acc[1][0]);
+                acc[0][0] = mfma32_fmt<FMT>(xa[0][0], w[0], acc[0][0]); acc[1][0] = mfma32_fmt<FMT>(xa[1][0], w[0], acc[1][0]);
+            }
             // ReLU(. + shift) is monotone, so it is applied before the pair maximum, which is then taken on non-negative
             // floats -- as unsigned integers
             unsigned r[14];
 #pragma unroll
             for (int v = 0; v < 14; ++v) {
                 const int tt = v / 7, bb = v - 7 * tt;
-                const float mx = fmaxf(fmaxf(acc[tt][2 * bb], acc[tt][2 * bb + 1]), acc[tt][2 * bb + 2]);   // frames
+                const float mx = fmaxf(fmaxf(acc[tt][0][2 * bb], acc[tt][0][2 * bb + 1]), acc[tt][0][2 * bb + 2]);   // frames
                 r[v] = __float_as_uint(epi_fmt<FMT>(mx, c1, tn));
             }
             unsigned got[7];
@@ -262,6 +310,7 @@ NQ_DEV void cnn_front_split_body(
 
     NQ_STAMP(2);
     // ---- conv2 16->32 on 24x7, pool -> 12x5 (row maps as in cnn.hip)
+    conv_k_ring<T, 2, 3> ring34;                          // X6: conv3's, then conv4's first fragments
     {
         f32x16 acc[6][1];
         unsigned base[6], m9[6];
@@ -274,8 +323,12 @@ NQ_DEV void cnn_front_split_body(
             m9[t] = tap_mask(u < 84, py, px, 24, 7);
             base[t] = R + ((py - 1) * 7 + (px - 1)) * FB_RS1 + (h << 4);
         }
-        conv_k_bf16<16, 6, 1, 7, FB_RS1, FB_P1, FB_ZADDR, false, NQ_RING2, FMT>(acc, wrs, CNNB_W2 * 2, lane16, base, m9);
+        fb_conv_k<FMT, 16, 6, 1, 7, FB_RS1, FB_P1, false, NQ_RING2>(acc, wrs, W2_ * 2, lane16, base, m9, ring2);
         NQ_STAMP(3);
+        if constexpr (X6) {
+            conv_k_preload(ring34, wrs, W3_ * 2, lane16);
+            __builtin_amdgcn_sched_barrier(0);            // (hipcc would sink the requests below the epilogue, to their use)
+        }
         float tn = tn2, c2 = 1.f, ms2 = 0.f;
         int e2 = 0;
         if (F16) {
@@ -326,8 +379,12 @@ NQ_DEV void cnn_front_split_body(
             for (int nt = 0; nt < 2; ++nt) acc[t][nt] = zero16();
             base[t] = R + base34[t] * FB_RS2 + (h << 4);
         }
-        conv_k_bf16<32, 2, 2, 5, FB_RS2, FB_P2, FB_ZADDR, true, NQ_RING34, FMT>(acc, wrs, CNNB_W3 * 2, lane16, base, m34);
+        fb_conv_k<FMT, 32, 2, 2, 5, FB_RS2, FB_P2, true, NQ_RING34>(acc, wrs, W3_ * 2, lane16, base, m34, ring34);
         NQ_STAMP(5);
+        if constexpr (X6) {
+            conv_k_preload(ring34, wrs, W4_ * 2, lane16);
+            __builtin_amdgcn_sched_barrier(0);
+        }
         float tn[2] = {tn3[0], tn3[1]}, c3 = 1.f, ms3 = 0.f;
         int e3 = 0;
         if (F16) {
@@ -352,16 +409,16 @@ NQ_DEV void cnn_front_split_body(
     }
 
     // ---- conv4 64->64 on 12x5, pool -> 6x3.  The pooled outputs of the workgroup's four segments go to a
-    //      SHARED pair of bf16 planes S4[72 px][64 ch] (row = 18 * wave + pixel) for the N-split conv5/conv6.
+    //      SHARED set of T planes S4[72 px][64 ch] (row = 18 * wave + pixel) for the N-split conv5/conv6.
     NQ_STAMP(6);
-    const unsigned S4 = FB_BASE;                          // 2 planes x FB_PS (wave 0/1 regions; their A3 is dead by then)
-    const unsigned S5 = FB_BASE + 2 * FB_WAVE;            // conv5 output, same shape (wave 2/3 regions)
-    // conv5 / conv6 weight fragments of this wave (its 16 output channels), [step][hi,lo][lane][8]: rings of 4 / 8
-    // K-steps, requested 3 / 7 steps ahead -- a step of conv5 (conv6) is only 15 (6) short MFMAs, an L2 round trip
+    const unsigned S4 = FB_BASE;                          // T planes x FB_PS (wave 0/1 regions; their A3 is dead by then)
+    const unsigned S5 = FB_BASE + 2 * FB_WAVE(T);         // conv5 output, same shape (wave 2/3 regions)
+    // conv5 / conv6 weight fragments of this wave (its 16 output channels), [step][term][lane][8]: rings of 4 / 8
+    // K-steps, requested 3 / 7 steps ahead -- a step of conv5 (conv6) is only 15 (6) short MFMAs (T = 2), an L2 round trip
     // several steps long.  The first requests go out before the previous layer's epilogue.
-    const int w5b = __builtin_amdgcn_readfirstlane((CNNB_W5 + wave * (18 * 2 * 512)) * 2);
-    const int w6b = __builtin_amdgcn_readfirstlane((CNNB_W6 + wave * (18 * 2 * 512)) * 2);
-    f32x4 b5[4][2], b6[8][2];
+    const int w5b = __builtin_amdgcn_readfirstlane((W5_ + wave * (18 * T * 512)) * 2);
+    const int w6b = __builtin_amdgcn_readfirstlane((W6_ + wave * (18 * T * 512)) * 2);
+    f32x4 b5[4][T], b6[8][T];
     {
         f32x16 acc[2][2];
         unsigned base[2];
@@ -371,7 +428,7 @@ NQ_DEV void cnn_front_split_body(
             for (int nt = 0; nt < 2; ++nt) acc[t][nt] = zero16();
             base[t] = R + base34[t] * FB_RS3 + (h << 4);
         }
-        conv_k_bf16<64, 2, 2, 5, FB_RS3, FB_P3, FB_ZADDR, true, NQ_RING34, FMT>(acc, wrs, CNNB_W4 * 2, lane16, base, m34);
+        fb_conv_k<FMT, 64, 2, 2, 5, FB_RS3, FB_P3, true, NQ_RING34>(acc, wrs, W4_ * 2, lane16, base, m34, ring34);
         NQ_STAMP(7);
         float tn[2] = {tn4[0], tn4[1]}, c4 = 1.f, ms4 = 0.f;
         int e4 = 0;
@@ -382,8 +439,10 @@ NQ_DEV void cnn_front_split_body(
             tn[1] *= pow2_f32(e4);
         }
 #pragma unroll
-        for (int g = 0; g < 3; ++g) { b5[g][0] = wfrag_load(wrs, lane16, w5b + g * 2048); b5[g][1] = wfrag_load(wrs, lane16, w5b + g * 2048 + 1024); }
-        __syncthreads();                   // every wave has consumed its A3: the regions may be re-used
+        for (int g = 0; g < 3; ++g)
+#pragma unroll
+            for (int q = 0; q < T; ++q) b5[g][q] = wfrag_load(wrs, lane16, w5b + (g * T + q) * 1024);
+        __syncthreads();                  // every wave has consumed its A3: the regions may be re-used
         const unsigned wr = S4 + (18 * wave + 9 * hf) * FB_RS3 + n * 2;
         float* dst = P3 ? p3 + (size_t)p * (18 * 64) : nullptr;
 #pragma unroll
@@ -438,8 +497,8 @@ NQ_DEV void cnn_front_split_body(
             m5[t] = tap_mask(rho < 72, ry, rx, 6, 3);
             base5[t] = S4 + (slot * 18 + (ry - 1) * 3 + (rx - 1)) * FB_RS3 + (kg << 4);
         }
-        unsigned a5h[5], a5l[5];
-        f32x4 a5[2][5][2];                                  // A rows one step ahead: [buffer][tile][hi, lo]
+        unsigned a5ad[5][T];
+        f32x4 a5[2][5][T];                                  // A rows one step ahead: [buffer][tile][term]
         auto load_a5 = [&](int g) {
             const int tap = g >> 1, s = g & 1;
             const int tapoff = ((tap / 3) * 3 + tap % 3) * FB_RS3;
@@ -447,26 +506,33 @@ NQ_DEV void cnn_front_split_body(
 #pragma unroll
                 for (int t = 0; t < 5; ++t) {
                     const bool ok = (m5[t] >> tap) & 1u;
-                    a5h[t] = ok ? base5[t] : FB_ZADDR - tapoff;
-                    a5l[t] = ok ? base5[t] + FB_PS : FB_ZADDR - tapoff;
+#pragma unroll
+                    for (int q = 0; q < T; ++q) a5ad[t][q] = ok ? base5[t] + q * FB_PS : FB_ZADDR - tapoff;
                 }
             }
 #pragma unroll
-            for (int t = 0; t < 5; ++t) {
-                a5[g & 1][t][0] = lds_ld128(a5h[t] + tapoff + 64 * s);
-                a5[g & 1][t][1] = lds_ld128(a5l[t] + tapoff + 64 * s);
-            }
+            for (int t = 0; t < 5; ++t)
+#pragma unroll
+                for (int q = 0; q < T; ++q) a5[g & 1][t][q] = lds_ld128(a5ad[t][q] + tapoff + 64 * s);
         };
         load_a5(0);
 #pragma unroll
         for (int g = 0; g < 18; ++g) {
-            if (g + 3 < 18) { b5[(g + 3) & 3][0] = wfrag_load(wrs, lane16, w5b + (g + 3) * 2048); b5[(g + 3) & 3][1] = wfrag_load(wrs, lane16, w5b + (g + 3) * 2048 + 1024); }
+            if (g + 3 < 18) {
+#pragma unroll
+                for (int q = 0; q < T; ++q) b5[(g + 3) & 3][q] = wfrag_load(wrs, lane16, w5b + ((g + 3) * T + q) * 1024);
+            }
             if (g + 1 < 18) load_a5(g + 1);
-            mma16_pair_fmt<FMT, 5>(acc5, a5[g & 1], b5[g & 3]);
+            if constexpr (X6) {
+                __builtin_amdgcn_sched_barrier(0);         // requests stay ahead of the step's MFMAs (conv_k_terms: FENCE)
+                mma16_terms<T, 5>(acc5, a5[g & 1], b5[g & 3]);
+            } else mma16_pair_fmt<FMT, 5>(acc5, a5[g & 1], b5[g & 3]);
         }
         NQ_STAMP(9);
 #pragma unroll
-        for (int g = 0; g < 7; ++g) { b6[g][0] = wfrag_load(wrs, lane16, w6b + g * 2048); b6[g][1] = wfrag_load(wrs, lane16, w6b + g * 2048 + 1024); }
+        for (int g = 0; g < 7; ++g)
+#pragma unroll
+            for (int q = 0; q < T; ++q) b6[g][q] = wfrag_load(wrs, lane16, w6b + (g * T + q) * 1024);
         {
             const unsigned wr = S5 + (4 * kg) * FB_RS3 + ch * 2;
 #pragma unroll
@@ -495,8 +561,8 @@ NQ_DEV void cnn_front_split_body(
             m6[t] = tap_mask(rho < 24, y, 1, 6, 3);          // output column x = 1: input columns 0..2 are all inside
             base6[t] = S5 + (slot * 18 + (y - 1) * 3) * FB_RS3 + (kg << 4);
         }
-        unsigned a6h[2], a6l[2];
-        f32x4 a6[2][2][2];
+        unsigned a6ad[2][T];
+        f32x4 a6[2][2][T];
         auto load_a6 = [&](int g) {
             const int tap = g >> 1, s = g & 1;
             const int tapoff = ((tap / 3) * 3 + tap % 3) * FB_RS3;
@@ -504,23 +570,28 @@ NQ_DEV void cnn_front_split_body(
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
                     const bool ok = (m6[t] >> tap) & 1u;
-                    a6h[t] = ok ? base6[t] : FB_ZADDR - tapoff;
-                    a6l[t] = ok ? base6[t] + FB_PS : FB_ZADDR - tapoff;
+#pragma unroll
+                    for (int q = 0; q < T; ++q) a6ad[t][q] = ok ? base6[t] + q * FB_PS : FB_ZADDR - tapoff;
                 }
             }
 #pragma unroll
-            for (int t = 0; t < 2; ++t) {
-                a6[g & 1][t][0] = lds_ld128(a6h[t] + tapoff + 64 * s);
-                a6[g & 1][t][1] = lds_ld128(a6l[t] + tapoff + 64 * s);
-            }
+            for (int t = 0; t < 2; ++t)
+#pragma unroll
+                for (int q = 0; q < T; ++q) a6[g & 1][t][q] = lds_ld128(a6ad[t][q] + tapoff + 64 * s);
         };
         load_a6(0);
 #pragma unroll
         for (int g = 0; g < 18; ++g) {
-            if (g + 7 < 18) { b6[(g + 7) & 7][0] = wfrag_load(wrs, lane16, w6b + (g + 7) * 2048); b6[(g + 7) & 7][1] = wfrag_load(wrs, lane16, w6b + (g + 7) * 2048 + 1024); }
+            if (g + 7 < 18) {
+#pragma unroll
+                for (int q = 0; q < T; ++q) b6[(g + 7) & 7][q] = wfrag_load(wrs, lane16, w6b + ((g + 7) * T + q) * 1024);
+            }
             if (g + 1 < 18) load_a6(g + 1);
-            if (g & 1) mma16_pair_fmt<FMT, 2>(acc6b, a6[1], b6[g & 7]);
-            else mma16_pair_fmt<FMT, 2>(acc6, a6[0], b6[g & 7]);
+            f32x4 (&acc)[2] = (g & 1) ? acc6b : acc6;
+            if constexpr (X6) {
+                __builtin_amdgcn_sched_barrier(0);
+                mma16_terms<T, 2>(acc, a6[g & 1], b6[g & 7]);
+            } else mma16_pair_fmt<FMT, 2>(acc, a6[g & 1], b6[g & 7]);
         }
         NQ_STAMP(11);
         // this wave's 4 x 96 outputs (slot, channel * 6 + y) go through S4 (dead since the barrier above) so that the
@@ -546,49 +617,52 @@ NQ_DEV void cnn_front_split_body(
                 *(f32x4*)(feat + (size_t)(p0 + slot) * 384 + 96 * wave + 4 * (q - 24 * slot)) = lds_ld128(fo + 16 * q);
         }
     }
-    NQ_STAMP_END(g_phase_clk, ((blockIdx.y * gridDim.x + blockIdx.x) << 2) + wave);
+    NQ_STAMP_END((X6 ? g_phase_clk6 : g_phase_clk), ((blockIdx.y * gridDim.x + blockIdx.x) << 2) + wave);
 }
 
-// ---- kernels: one body, three operand formats -------------------------------------------------------------------------------------
+// ---- kernels: one body, four operand formats (thin wrappers: tools and the benchmark look the kernels up by these names) ---------
+#define FB_PARAMS                                                                                                              \
+    const float* __restrict__ mel_tm, const int32_t* __restrict__ frame_off, const int32_t* __restrict__ tok_off,             \
+    const int32_t* __restrict__ n_wins, const float* __restrict__ clip_floor, int n_clips, int seg_hop,                       \
+    const float* __restrict__ cw, const unsigned short* __restrict__ wb, float* __restrict__ p3, float* __restrict__ feat,    \
+    const float* __restrict__ seg_x, int seg_L, const uint32_t* __restrict__ clip_max_enc, float top_db
+#define FB_ARGS mel_tm, frame_off, tok_off, n_wins, clip_floor, n_clips, seg_hop, cw, wb, p3, feat, seg_x, seg_L, clip_max_enc, top_db
 template <bool SEGX, bool P3>
-__global__ __launch_bounds__(256, FB_WGS) void cnn_front_bf16_kernel(
-    const float* __restrict__ mel_tm, const int32_t* __restrict__ frame_off, const int32_t* __restrict__ tok_off,
-    const int32_t* __restrict__ n_wins, const float* __restrict__ clip_floor, int n_clips, int seg_hop,
-    const float* __restrict__ cw, const unsigned short* __restrict__ wb, float* __restrict__ p3, float* __restrict__ feat,
-    const float* __restrict__ seg_x, int seg_L, const uint32_t* __restrict__ clip_max_enc, float top_db) {
-    cnn_front_split_body<NQ_FMT_BF16X3, SEGX, P3>(mel_tm, frame_off, tok_off, n_wins, clip_floor, n_clips, seg_hop, cw, wb, p3, feat, seg_x, seg_L,
-                                                  clip_max_enc, top_db);
+__global__ __launch_bounds__(256, FB_WGS(2)) void cnn_front_bf16_kernel(FB_PARAMS) {
+    cnn_front_split_body<NQ_FMT_BF16X3, SEGX, P3>(FB_ARGS);
 }
 // fp32 operands as two f16 terms of the power-of-two-scaled tensors; P4: all four term products ('f16x4'), else hh + hl + lh ('f16x3')
 template <bool P4, bool SEGX>
-__global__ __launch_bounds__(256, FB_WGS) void cnn_front_f16_kernel(
-    const float* __restrict__ mel_tm, const int32_t* __restrict__ frame_off, const int32_t* __restrict__ tok_off,
-    const int32_t* __restrict__ n_wins, const float* __restrict__ clip_floor, int n_clips, int seg_hop,
-    const float* __restrict__ cw, const unsigned short* __restrict__ wb, float* __restrict__ p3, float* __restrict__ feat,
-    const float* __restrict__ seg_x, int seg_L, const uint32_t* __restrict__ clip_max_enc, float top_db) {
-    cnn_front_split_body<P4 ? NQ_FMT_F16X4 : NQ_FMT_F16X3, SEGX, false>(mel_tm, frame_off, tok_off, n_wins, clip_floor, n_clips, seg_hop, cw, wb, p3,
-                                                                       feat, seg_x, seg_L, clip_max_enc, top_db);
+__global__ __launch_bounds__(256, FB_WGS(2)) void cnn_front_f16_kernel(FB_PARAMS) {
+    cnn_front_split_body<P4 ? NQ_FMT_F16X4 : NQ_FMT_F16X3, SEGX, false>(FB_ARGS);
+}
+// fp32 operands as three bf16 terms, six products ('bf16x6', the default): one workgroup per CU
+template <bool SEGX>
+__global__ __launch_bounds__(256, FB_WGS(3)) void cnn_front_bf16x6_kernel(FB_PARAMS) {
+    cnn_front_split_body<NQ_FMT_BF16X6, SEGX, false>(FB_ARGS);
 }
 
 typedef void (*fb_kernel_t)(const float*, const int32_t*, const int32_t*, const int32_t*, const float*, int, int, const float*,
                             const unsigned short*, float*, float*, const float*, int, const uint32_t*, float);
-// fmt: 0 bf16x3, 1 f16x3, 2 f16x4.  80.5 KB of dynamic LDS is above the 64 KB default: every instantiation is opted in once per
-// device ordinal (a process may drive several GPUs), like the three-term kernel's launcher
+// fmt: the NQ_FMT_ value (0 bf16x3, 1 f16x3, 2 f16x4, 3 bf16x6).  79 KB / 117 KB of dynamic LDS is above the 64 KB default: every
+// instantiation is opted in once per device ordinal (a process may drive several GPUs)
 static int fb_launch(int fmt, bool segx, bool p3, const float* mel_tm, const int32_t* frame_off, const int32_t* tok_off,
                      const int32_t* n_wins, const float* clip_floor, const uint32_t* clip_max_enc, float top_db, int32_t n_clips,
                      int32_t total_tok_padded, int32_t seg_hop, const float* cnn_w, const uint16_t* cnn_wb, float* p3_opt, float* feat,
                      const float* seg_x, int32_t seg_L, void* stream) {
-    if (n_clips <= 0 || total_tok_padded <= 0 || (total_tok_padded & 31) || seg_hop <= 0 || !cnn_wb || !feat || fmt < 0 || fmt > 2 ||
+    if (n_clips <= 0 || total_tok_padded <= 0 || (total_tok_padded & 31) || seg_hop <= 0 || !cnn_wb || !feat || fmt < 0 || fmt > 3 ||
         (p3 && fmt != 0) || (segx && (!seg_x || seg_L <= 0)) || (!segx && !clip_floor && !clip_max_enc))
         return NISQA_ERR_ARG;
-    static const fb_kernel_t kernels[7] = {
+    static const fb_kernel_t kernels[9] = {
         cnn_front_bf16_kernel<false, false>, cnn_front_bf16_kernel<false, true>, cnn_front_bf16_kernel<true, false>,
-        cnn_front_f16_kernel<false, false>, cnn_front_f16_kernel<false, true>, cnn_front_f16_kernel<true, false>, cnn_front_f16_kernel<true, true>};
+        cnn_front_f16_kernel<false, false>, cnn_front_f16_kernel<false, true>, cnn_front_f16_kernel<true, false>, cnn_front_f16_kernel<true, true>,
+        cnn_front_bf16x6_kernel<false>, cnn_front_bf16x6_kernel<true>};
     const int which = fmt == 0 ? (segx ? 2 : p3 ? 1 : 0) : 3 + 2 * (fmt - 1) + (segx ? 1 : 0);
+    const unsigned lds = fmt == NQ_FMT_BF16X6 ? FB_LDS(3) : FB_LDS(2);
     NQ_LAUNCH_BEGIN();
-    static std::atomic<bool> lds_ok[7][64];
-    if (nq_lds_opt_in((const void*)kernels[which], (int)FB_LDS, lds_ok[which])) return 2;
-    hipLaunchKernelGGL(kernels[which], dim3(total_tok_padded / 4), dim3(256), FB_LDS, (hipStream_t)stream, mel_tm, frame_off, tok_off, n_wins,
+    static std::atomic<bool> lds_ok[9][64];
+    if (nq_lds_opt_in((const void*)kernels[which], (int)lds, lds_ok[which])) return 2;
+    hipLaunchKernelGGL(kernels[which], dim3(total_tok_padded / 4), dim3(256), lds, (hipStream_t)stream, mel_tm, frame_off, tok_off, n_wins,
                        clip_floor, n_clips, seg_hop, cnn_w, cnn_wb, p3_opt, feat, seg_x, seg_L, clip_max_enc, top_db);
     return NQ_LAUNCH_STATUS();
 }
@@ -639,5 +713,28 @@ extern "C" int nisqa_cnn_adapt_segments_f16(const float* x, int32_t seg_len_padd
                                             int32_t products, float* feat, void* stream) {
     if (products != 3 && products != 4) return NISQA_ERR_ARG;
     return fb_launch(products - 2, true, false, nullptr, nullptr, tok_off, n_wins, nullptr, nullptr, 0.f, n_clips, total_tok_padded, 1, cnn_w, cnn_wh,
+                     nullptr, feat, x, seg_len_padded, stream);
+}
+
+// ---- the three-term format (cnn_wx: nisqa_amd.weights.pack_adapt_cnn_bf16(terms=3), CNNX_U16S uint16) ----------------------------------
+extern "C" int nisqa_cnn_adapt_bf16x6(const float* mel_tm, const int32_t* frame_off, const int32_t* tok_off,
+                                      const int32_t* n_wins, const float* clip_floor, int32_t n_clips,
+                                      int32_t total_tok_padded, int32_t seg_hop, const float* cnn_w,
+                                      const uint16_t* cnn_wx, float* feat, void* stream) {
+    return fb_launch(NQ_FMT_BF16X6, false, false, mel_tm, frame_off, tok_off, n_wins, clip_floor, nullptr, 0.f, n_clips, total_tok_padded, seg_hop,
+                     cnn_w, cnn_wx, nullptr, feat, nullptr, 0, stream);
+}
+int nq_cnn_adapt_bf16x6_from_max(const float* mel_tm, const int32_t* frame_off, const int32_t* tok_off,
+                                 const int32_t* n_wins, const uint32_t* clip_max_enc, float top_db, int32_t n_clips,
+                                 int32_t total_tok_padded, int32_t seg_hop, const float* cnn_w, const uint16_t* cnn_wx,
+                                 float* feat, void* stream) {
+    if (!clip_max_enc) return NISQA_ERR_ARG;
+    return fb_launch(NQ_FMT_BF16X6, false, false, mel_tm, frame_off, tok_off, n_wins, nullptr, clip_max_enc, top_db, n_clips, total_tok_padded,
+                     seg_hop, cnn_w, cnn_wx, nullptr, feat, nullptr, 0, stream);
+}
+extern "C" int nisqa_cnn_adapt_segments_bf16x6(const float* x, int32_t seg_len_padded, const int32_t* tok_off,
+                                               const int32_t* n_wins, int32_t n_clips, int32_t total_tok_padded,
+                                               const float* cnn_w, const uint16_t* cnn_wx, float* feat, void* stream) {
+    return fb_launch(NQ_FMT_BF16X6, true, false, nullptr, nullptr, tok_off, n_wins, nullptr, nullptr, 0.f, n_clips, total_tok_padded, 1, cnn_w, cnn_wx,
                      nullptr, feat, x, seg_len_padded, stream);
 }

@@ -46,7 +46,7 @@ NQ_DEV float row16_sum_dpp(float v) {
     return v;
 }
 
-// conv2's K loop, second generation (round 4; before: the generic-pointer conv3x3_bf16 with per-tap bounds / swizzle / row
+// conv2's K loop, second generation (round 4; before: a generic-pointer loop with per-tap bounds / swizzle / row
 // arithmetic on every tile).  Its input planes are the chunk-swizzled 16-channel A1 planes conv1 writes (32 bytes per pixel,
 // 16-byte chunk (c >> 3) ^ (image row & 1) at W = 8), so a tap's address is one of TWO lane-static bases -- the centre
 // pixel's chunk for taps in its own image row, the flipped chunk for the rows above and below -- plus a compile-time tap

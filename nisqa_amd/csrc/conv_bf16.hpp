@@ -4,7 +4,7 @@
 #pragma once
 #include "bf16_terms.hpp"
 
-// ---- operand formats of the two-term kernels (cnn_bf16.hip) ---------------------------------------------------------------------
+// ---- operand formats of the 16-bit kernels (cnn_bf16.hip, cnn_std_bf16.hip) ---------------------------------------------------------------------
 //   NQ_FMT_BF16X3: x = hi + lo in bf16 (8 + 8 significand bits), products hh + hl + lh: 16 of an fp32 operand's 24 bits
 //   NQ_FMT_F16X3 / NQ_FMT_F16X4: x * 2^e = hi + lo in f16 (11 + 11 significand bits and lo's sign: the residual x - hi is a
 //     multiple of ulp32(x) of magnitude <= 4096 ulp32, and f16 holds every such integer up to 2048 and every even one up to 4096 --
@@ -17,7 +17,7 @@
 #define NQ_FMT_BF16X3 0
 #define NQ_FMT_F16X3 1
 #define NQ_FMT_F16X4 2
-#define NQ_FMT_BF16X6 3                    /* three bf16 terms, six products (exact operands): the kernels that template over it keep conv_k_terms' loops */
+#define NQ_FMT_BF16X6 3                    /* three bf16 terms, six products (exact operands): the kernels that template over it (cnn_bf16.hip, cnn_std_bf16.hip) keep conv_k_terms' loops */
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x2_t __attribute__((ext_vector_type(2)));
 template <int FMT>
@@ -100,94 +100,8 @@ NQ_DEV void store_split(char* plane_hi, int plane_bytes, int off, float v) {
     *(unsigned short*)(plane_hi + plane_bytes + off) = (unsigned short)lo;
 }
 
-// One conv layer (3x3, padding 1) for this wave's segment, barrier-free.
-//   act_in : this wave's input planes (hi at +0, lo at +PLANE), pixel rows of CIN bf16, swizzled chunks
-//   wb     : layer fragments [TOTAL steps][NT][2][64][8] bf16, streamed from L2: one contiguous 1 KiB
-//            global_load_dwordx4 per fragment, requested TWO K-steps ahead into a 3-deep register ring
-//            (an L2 round trip is ~600 clk, a step of MFMAs 200-800 clk); ~10 TB/s of L2 reads chip-wide
-//   APF    : also double-buffer the A rows from LDS one step ahead (off for conv2: 6 M-tiles of registers)
-//   PAD    : pixel rows are CIN*2 + 16 bytes apart and NOT swizzled (the 16-byte pad spreads consecutive pixels over the
-//            banks like the XOR swizzle does, and every address becomes lane base + compile-time offset)
-template <int CIN, int MT, int NT, int H, int W, bool APF, bool PAD = false>
-NQ_DEV void conv3x3_bf16(f32x16 (&acc)[MT][NT], const char* act_in, const char* zero,
-                         const unsigned short* __restrict__ wb, const int (&py)[MT], const int (&px)[MT],
-                         const bool (&pvalid)[MT], int lane) {
-    constexpr int S16 = CIN / 16;             // K=16 steps per tap
-    constexpr int TOTAL = 9 * S16;
-    constexpr int Cc = CIN / 8;               // 16-byte chunks per pixel row (per plane)
-    constexpr int RS = CIN * 2 + (PAD ? 16 : 0);   // bytes between pixel rows
-    constexpr int PLANE = H * W * RS;         // bytes per plane
-    constexpr int AB = APF ? 2 : 1;
-    const int h = lane >> 5;
-    const f32x4* wl = (const f32x4*)wb + lane;
-    f32x4 bh[3][NT], bl[3][NT], ah[AB][MT], al[AB][MT];
-
-    auto load_b = [&](int g, int slot) {
-#pragma unroll
-        for (int nt = 0; nt < NT; ++nt) {
-            bh[slot][nt] = wl[((g * NT + nt) * 2 + 0) * 64];
-            bl[slot][nt] = wl[((g * NT + nt) * 2 + 1) * 64];
-        }
-    };
-    // A operand of tile t at K-step (tap, s): 16 bytes at  pixel row + (((2s + h) ^ swz) << 4)  of each plane.  With
-    // t = h ^ swz this is  (pixel row | t << 4) ^ (32 s)  (pixel rows are aligned to their size, 32 s stays inside a
-    // row), so the bounds check, the swizzle and the row address are per TAP; a K-step costs one XOR per plane.
-    // Out-of-image taps point both planes at the wave's 128-byte zero block (aligned, so the XOR stays inside it).
-    int a_hi[MT], a_lo[MT];
-    const int zoff = (int)(zero - act_in);
-    auto tap_a = [&](int tap) {
-        const int dy = tap / 3 - 1, dx = tap - 3 * (tap / 3) - 1;
-#pragma unroll
-        for (int t = 0; t < MT; ++t) {
-            const int y = py[t] + dy, x = px[t] + dx;
-            const bool ok = pvalid[t] && (unsigned)y < (unsigned)H && (unsigned)x < (unsigned)W;
-            const int pix = y * W + x;
-            const int swz = PAD ? 0 : ((pix * Cc) >> 4) & (Cc - 1);
-            const int row = pix * RS + ((h ^ swz) << 4);
-            a_hi[t] = ok ? row : zoff;
-            a_lo[t] = ok ? row + PLANE : zoff;
-        }
-    };
-    auto load_a = [&](int g, int slot) {
-        const int tap = g / S16, s = g - tap * S16;
-        if (s == 0) tap_a(tap);
-#pragma unroll
-        for (int t = 0; t < MT; ++t) {
-            // PAD: plain + 32 s (an immediate offset of the LDS read); swizzled: ^ 32 s
-            ah[slot][t] = *(const f32x4*)(act_in + (PAD ? a_hi[t] + 32 * s : a_hi[t] ^ (32 * s)));
-            al[slot][t] = *(const f32x4*)(act_in + (PAD ? a_lo[t] + 32 * s : a_lo[t] ^ (32 * s)));
-        }
-    };
-
-    load_b(0, 0);
-    load_b(1, 1);
-    if (APF) load_a(0, 0);
-#pragma unroll
-    for (int g = 0; g < TOTAL; ++g) {
-        if (g + 2 < TOTAL) load_b(g + 2, (g + 2) % 3);
-        if (APF) { if (g + 1 < TOTAL) load_a(g + 1, (g + 1) & 1); } else load_a(g, 0);
-        const int sa = APF ? (g & 1) : 0, sb = g % 3;
-        // product-major: consecutive MFMAs go to DIFFERENT accumulators (no dependent-accumulate bubbles)
-#pragma unroll
-        for (int t = 0; t < MT; ++t)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[t][nt] = mfma_bf(ah[sa][t], bl[sb][nt], acc[t][nt]);
-#pragma unroll
-        for (int t = 0; t < MT; ++t)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[t][nt] = mfma_bf(al[sa][t], bh[sb][nt], acc[t][nt]);
-#pragma unroll
-        for (int t = 0; t < MT; ++t)
-#pragma unroll
-            for (int nt = 0; nt < NT; ++nt) acc[t][nt] = mfma_bf(ah[sa][t], bh[sb][nt], acc[t][nt]);
-
-    }
-}
-
-
-
 // ======================================================================================================================
-// Second-generation K loop (AdaptCNN kernel): LDS addressed by 32-bit byte addresses in address space 3 (no 64-bit
+// The K loop (AdaptCNN kernel): LDS addressed by 32-bit byte addresses in address space 3 (no 64-bit
 // pointer arithmetic), tap validity as one precomputed 9-bit mask per M tile (lane-static: the row -> pixel maps do not
 // depend on the data), out-of-image taps redirected to a zero block with ONE select per tap and tile, weight fragments
 // through a buffer resource (address = SGPR descriptor + constant lane offset + immediate).  DESIGN.md 4.5.
@@ -330,7 +244,7 @@ NQ_DEV void conv_k_bf16(f32x16 (&acc)[MT][NT], __amdgpu_buffer_rsrc_t rsrc, int 
 
 
 // ======================================================================================================================
-// T terms per operand (cnn_bf16x6.hip: T = 3, bf16 hi + mid + lo = the fp32 operand EXACTLY, 24 mantissa bits): the products
+// T terms per operand (format NQ_FMT_BF16X6 of cnn_bf16.hip / cnn_std_bf16.hip: T = 3, bf16 hi + mid + lo = the fp32 operand EXACTLY, 24 mantissa bits): the products
 // (i, j) with i + j <= T - 1 are formed, smallest first -- for T = 3 the six products hh, hm, mh, hl, lh, mm; what is dropped
 // (ml, lm, ll) is at most 2 x 2^-24 of the product, typically 0.5 x 2^-24 rms: the size of an fp32 multiply-add's own rounding of
 // that product.  T = 2 is the shipped hi/lo form (three products).

@@ -7,7 +7,7 @@
 // every wave's numbers to shared counters: 250 k atomics on one cache line per launch made the kernel 4 x slower):
 //   stamp clock  NQ_STAMP_BEGIN(); NQ_STAMP(i) at layer boundaries i = 0..11; NQ_STAMP_END(ARR, wave_index)
 //                slot = {phase i -> i + 1 for i < 12, [12] = 1, [13] = wall clock, [14] = launch -> stamp 0}; the LAST launch's numbers stay.
-//                (cnn_bf16.hip, cnn_bf16x6.hip; read by tools/phase_clock.py)
+//                (cnn_bf16.hip: one slot array for the two-term kernels, one for the three-term kernel; read by tools/phase_clock.py)
 //   sum clock    NQ_SUM_BEGIN(); NQ_SUM(i) adds the time since the previous mark to phase i (loops: a phase is hit many times);
 //                NQ_SUM_COUNT(i, n) adds n to slot i; NQ_SUM_END(ARR, wave_index, cond) adds the wave's sums to its slot.
 //                (mel.hip, lstm.hip, train_conv.hip; read by tools/mel_clock.py, tools/lstm_clock.py, tools/bench_segconv.py)

@@ -51,7 +51,7 @@
 #define CNNB_W5 (CNNB_W4 + 36 * 2 * 2 * 512)
 #define CNNB_W6 (CNNB_W5 + 36 * 2 * 2 * 512)
 #define CNNB_U16S (CNNB_W6 + 36 * 2 * 2 * 512)
-// three-term fragments of cnn_bf16x6.hip (bf16 hi + mid + lo = the fp32 weight exactly): as above with [3] terms per fragment
+// three-term fragments of cnn_bf16.hip's format BF16X6 (bf16 hi + mid + lo = the fp32 weight exactly): as above with [3] terms per fragment
 #define CNNX_W1 0
 #define CNNX_W2 (CNNX_W1 + 3 * 512)
 #define CNNX_W3 (CNNX_W2 + 9 * 1 * 3 * 512)

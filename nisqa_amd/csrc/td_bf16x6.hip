@@ -1,6 +1,6 @@
 // Attention pooling (5 x PoolAttFF; reference nisqa/NISQA_lib.py:1171-1183) at fp32 OPERAND precision on the bf16 matrix pipe
 // ("bf16x6"): every GEMM operand as THREE bf16 terms (hi + mid + lo: an exact split of the fp32 value) and six
-// v_mfma_f32_32x32x16_bf16 products per term pair (hh, hm, mh, hl, lh, mm; fp32 accumulate) -- cnn_bf16x6.hip, DESIGN.md 4.5.
+// v_mfma_f32_32x32x16_bf16 products per term pair (hh, hm, mh, hl, lh, mm; fp32 accumulate) -- cnn_bf16.hip's format BF16X6, DESIGN.md 4.5.
 // One wave per (32-token tile, head); the self-attention kernels of the same precision are td16_bf16x6.hip.
 #include "bf16_terms.hpp"
 #include "layout.hpp"

@@ -66,7 +66,7 @@ CNNB_W4 = CNNB_W3 + 18 * 2 * 2 * 512
 CNNB_W5 = CNNB_W4 + 36 * 2 * 2 * 512
 CNNB_W6 = CNNB_W5 + 36 * 2 * 2 * 512
 CNNB_U16S = CNNB_W6 + 36 * 2 * 2 * 512
-# three-term fragments (csrc/cnn_bf16x6.hip): [3] terms per fragment
+# three-term fragments (csrc/cnn_bf16.hip, format BF16X6): [3] terms per fragment
 CNNX_W1 = 0
 CNNX_W2 = CNNX_W1 + 3 * 512
 CNNX_W3 = CNNX_W2 + 9 * 1 * 3 * 512

@@ -56,7 +56,7 @@ def test_conv_fragments_roundtrip():
 
 
 def test_three_bf16_terms_hold_an_fp32_value_exactly_and_the_x6_fragments_are_the_weights():
-    """precision 'bf16x6' (csrc/cnn_bf16x6.hip): bf16_split(x, 3) is an EXACT split of any finite fp32 value (8 + 8 + 8 significant
+    """precision 'bf16x6' (csrc/cnn_bf16.hip, format BF16X6): bf16_split(x, 3) is an EXACT split of any finite fp32 value (8 + 8 + 8 significant
     bits, each term rounded to nearest), two terms are not; the three-term fragment blob of pack_adapt_cnn_bf16 holds every
     BatchNorm-folded weight bit for bit at the layout offsets of layout.hpp (CNNX_*)."""
     rng = np.random.default_rng(5)

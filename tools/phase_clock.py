@@ -1,4 +1,5 @@
-"""Per-phase shader-clock profile of cnn_front_bf16_kernel (build: tools/phase_clock.sh -> ab_libs/clock.so).
+"""Per-phase shader-clock profile of the AdaptCNN kernel of NQ_PRECISION (build: tools/phase_clock.sh -> ab_libs/clock.so; the one
+instrumented unit, cnn_bf16.hip, carries the stamps of all four formats).
 
 Run on the GPU box:  NISQA_ALLOW_DEBUG_LIB=1 NISQA_HIP_LIB=$PWD/ab_libs/clock.so python tools/phase_clock.py
 Prints the mean cycles one wave spends between the layer boundaries (under the real 2-waves-per-SIMD contention)."""
@@ -9,7 +10,7 @@ from nisqa_amd import synth, lib
 from nisqa_amd.engine import HipNisqa
 
 dev = torch.device('cuda:0')
-PREC = os.environ.get('NQ_PRECISION', 'bf16x3')          # bf16x6: cnn_front_bf16x6_kernel (its own stamp buffer)
+PREC = os.environ.get('NQ_PRECISION', 'bf16x3')          # bf16x6: cnn_front_bf16x6_kernel (same unit, its own stamp buffer)
 eng = HipNisqa(dict(synth.DIM_ARGS), synth.random_state_dict(7, 'NISQA_DIM'), dev, precision=PREC)
 L = ctypes.CDLL(lib.LIB_PATH)
 DBG = getattr(L, 'nisqa_debug_phase_clock6' if PREC == 'bf16x6' else 'nisqa_debug_phase_clock')

@@ -1,6 +1,6 @@
 #!/bin/bash
 # Builds ab_libs/NAME.so (default clock): the library with cnn_bf16.hip compiled -DNQ_EXPERIMENTAL (csrc/experimental.hpp: clock64
-# stamps inside cnn_front_bf16_kernel).  Load it with NISQA_ALLOW_DEBUG_LIB=1 (lib.load() refuses instrumented builds otherwise).
+# stamps inside cnn_front_bf16_kernel / cnn_front_f16_kernel / cnn_front_bf16x6_kernel: one unit, both clocks).  Load it with NISQA_ALLOW_DEBUG_LIB=1 (lib.load() refuses instrumented builds otherwise).
 # The knock-out flags of rounds 2-5 (-DNQ_KO=..) left the sources in round 6: git show c223882:nisqa_amd/csrc/conv_bf16.hpp
 set -e
 NAME=${1:-clock}; FLAGS=$2
