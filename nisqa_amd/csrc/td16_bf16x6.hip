@@ -16,8 +16,8 @@
 // wave's registers.
 //
 // Operands: every fp32 operand as THREE bf16 terms (hi + mid + lo, an exact split) and the six products hh hm mh hl lh mm, fp32
-// accumulate, smallest products first -- the arithmetic of td_bf16x6.hip's round-5 kernels (softmax, LayerNorm, biases, residuals
-// fp32 in registers).
+// accumulate, smallest products first -- the arithmetic of the round-5 kernels, td_bf16.hip's chain helpers with T = 3 (softmax,
+// LayerNorm, biases, residuals fp32 in registers).
 //
 // Fragment maps (wave64, lane l: c = l & 15, g = l >> 4):
 //   A (16 x 32): A[row c][k-slot 8 g + e]    B (32 x 16): B[k-slot 8 g + e][col c]    D (16 x 16): D[row 4 g + r][col c], r = 0..3

@@ -1,6 +1,9 @@
 // Self-attention and attention-pooling on split-bf16 MFMA -- same kernels, layouts and maths as td.hip
 // (reference nisqa/NISQA_lib.py:988-996, 1025-1040, 1171-1183) with every GEMM as three
 // v_mfma_f32_32x32x16_bf16 products of bf16 hi/lo operands (fp32 accumulate; |dMOS| ~ 1e-5).
+// The chain helpers and the pooling kernel are written over the number of terms T per operand: T = 2 is that form ('bf16x3'), T = 3
+// (hi + mid + lo, an EXACT split, the six products of bf16_terms.hpp's mma_terms) is the two-call pooling of 'bf16x6', whose
+// self-attention kernels are td16_bf16x6.hip.
 //
 // What changes against the fp32 version:
 //   * a K-step is 16 wide; lane half h supplies 8 k-slots.  For operands that come from MEMORY the slots are
@@ -14,14 +17,16 @@
 #include "layout.hpp"
 #include "../../include/nisqa_hip.h"
 
-// 8 consecutive registers of a D fragment -> B-operand (hi, lo) of one K=16 step
-NQ_DEV void split8(const f32x16& a, int base, f32x4& hi, f32x4& lo) {
+// 8 consecutive registers of a D fragment -> the T B-operand terms of one K=16 step (T = 2: hi, lo)
+template <int T>
+NQ_DEV void split8(const f32x16& a, int base, f32x4 (&b)[T]) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        unsigned h_, l_;
-        split2(a[base + 2 * q], a[base + 2 * q + 1], h_, l_);
-        hi[q] = __uint_as_float(h_);
-        lo[q] = __uint_as_float(l_);
+        unsigned t[T];
+        if constexpr (T == 2) split2(a[base + 2 * q], a[base + 2 * q + 1], t[0], t[1]);
+        else split2t(a[base + 2 * q], a[base + 2 * q + 1], t);
+#pragma unroll
+        for (int k = 0; k < T; ++k) b[k][q] = __uint_as_float(t[k]);
     }
 }
 
@@ -39,45 +44,49 @@ NQ_DEV void store_dtok_split(u16* __restrict__ hi_row, u16* __restrict__ lo_row,
         }
 }
 
-// out[mt] += W * in  (W: chain-order bf16 fragments [4 steps][MTT][hl][64][8], in: D layout of a 64 x 32 tile).
+// out[mt] += W * in  (W: chain-order bf16 fragments [4 steps][MTT][T terms][64][8] in memory, in: D layout of a 64 x 32 tile).
 // One wave runs per SIMD, so every global load is an exposed round trip unless it is requested a phase ahead: the
 // fragments of a whole GEMM (tiles mt0 .. mt0+MT-1 of MTT) are loaded by chain_load -- which the caller issues before
 // the VALU work that precedes the GEMM -- and consumed by chain_mma.
-template <int MT>
-struct chain_frags { f32x4 h[4][MT], l[4][MT]; };
+// The terms are the outermost index (and the attention tile below names its two split terms): hipcc's schedule of
+// td_layer_bf16_kernel moves with the order the aggregates are declared in, and in this form all four kernels of the file compile to
+// the instruction streams they had as two sources (profiles/r09_pool_score_one_source.txt).
+template <int T, int MT>
+struct chain_frags { f32x4 t[T][4][MT]; };
 
-template <int MT, int MTT>
-NQ_DEV void chain_load(const u16* __restrict__ wb, int mt0, chain_frags<MT>& f, int lane) {
+template <int MTT, int T, int MT>
+NQ_DEV void chain_load(const u16* __restrict__ wb, int mt0, chain_frags<T, MT>& f, int lane) {
     const f32x4* af = (const f32x4*)wb + lane;
 #pragma unroll
     for (int s = 0; s < 4; ++s)
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) {
-            f.h[s][mt] = af[((s * MTT + mt0 + mt) * 2 + 0) * 64];
-            f.l[s][mt] = af[((s * MTT + mt0 + mt) * 2 + 1) * 64];
-        }
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int k = 0; k < T; ++k) f.t[k][s][mt] = af[((s * MTT + mt0 + mt) * T + k) * 64];
 }
 
-template <int MT>
-NQ_DEV void chain_mma(const chain_frags<MT>& f, const f32x16 (&in)[2], f32x16 (&out)[MT]) {
+template <int T, int MT>
+NQ_DEV void chain_mma(const chain_frags<T, MT>& f, const f32x16 (&in)[2], f32x16 (&out)[MT]) {
 #pragma unroll
     for (int s = 0; s < 4; ++s) {
-        f32x4 bh, bl;
-        split8(in[s >> 1], 8 * (s & 1), bh, bl);
+        f32x4 b[T];
+        split8(in[s >> 1], 8 * (s & 1), b);
+        if constexpr (T == 2) {                           // h.l, l.h, h.h -- this form's own order (bf16_terms.hpp issues l.h first)
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) out[mt] = mfma_bf(f.h[s][mt], bl, out[mt]);   // product-major: consecutive
+            for (int mt = 0; mt < MT; ++mt) out[mt] = mfma_bf(f.t[0][s][mt], b[1], out[mt]);   // product-major: consecutive
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) out[mt] = mfma_bf(f.l[s][mt], bh, out[mt]);   // MFMAs on different
+            for (int mt = 0; mt < MT; ++mt) out[mt] = mfma_bf(f.t[1][s][mt], b[0], out[mt]);   // MFMAs on different
 #pragma unroll
-        for (int mt = 0; mt < MT; ++mt) out[mt] = mfma_bf(f.h[s][mt], bh, out[mt]);   // accumulators
+            for (int mt = 0; mt < MT; ++mt) out[mt] = mfma_bf(f.t[0][s][mt], b[0], out[mt]);   // accumulators
+        } else {
+            f32x4 a[MT][T];
+#pragma unroll
+            for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+                for (int k = 0; k < T; ++k) a[mt][k] = f.t[k][s][mt];
+            mma_terms<T, MT>(out, a, b);                  // the six products: weight term i, activation term j, i + j <= 2
+        }
     }
-}
-
-template <int MT>
-NQ_DEV void chain_gemm_bf(const u16* __restrict__ wb, const f32x16 (&in)[2], f32x16 (&out)[MT], int lane) {
-    chain_frags<MT> f;
-    chain_load<MT, MT>(wb, 0, f, lane);
-    chain_mma<MT>(f, in, out);
 }
 
 struct qkv_planes { u16 *qh, *ql, *kh, *kl, *vh, *vl; };   // q,k: [NP][64]; v: [64][NP]
@@ -90,25 +99,25 @@ NQ_DEV qkv_planes planes_of(float* base, size_t np64) {
 
 // Q, K, V of a layer as three 64-wide chain GEMMs: the fragments and biases of the next one are in flight while the
 // previous one's results are split and stored.  qkv_prefetch (the q fragments) is issued by the caller a phase ahead.
-struct qkv_pre { chain_frags<2> f; f32x16 bias[2]; };
+struct qkv_pre { chain_frags<2, 2> f; f32x16 bias[2]; };
 NQ_DEV void qkv_prefetch(const float* __restrict__ lw, const u16* __restrict__ lwb, qkv_pre& p, int lane) {
-    chain_load<2, 6>(lwb + TDBL_QKV, 0, p.f, lane);
+    chain_load<6>(lwb + TDBL_QKV, 0, p.f, lane);
     load_dvec<2>(lw + TDL_QKV_B, p.bias, lane >> 5);
 }
 NQ_DEV void qkv_store_bf(const float* __restrict__ lw, const u16* __restrict__ lwb, const f32x16 (&x)[2],
                          const qkv_planes& P, int tok, int np, int lane, qkv_pre& q) {
     const int hf = lane >> 5;
     qkv_pre k;
-    chain_load<2, 6>(lwb + TDBL_QKV, 2, k.f, lane);
+    chain_load<6>(lwb + TDBL_QKV, 2, k.f, lane);
     load_dvec<2>(lw + TDL_QKV_B + 64, k.bias, hf);
-    chain_mma<2>(q.f, x, q.bias);
+    chain_mma(q.f, x, q.bias);
     qkv_pre v;
-    chain_load<2, 6>(lwb + TDBL_QKV, 4, v.f, lane);
+    chain_load<6>(lwb + TDBL_QKV, 4, v.f, lane);
     load_dvec<2>(lw + TDL_QKV_B + 128, v.bias, hf);
     store_dtok_split(P.qh + (size_t)tok * 64, P.ql + (size_t)tok * 64, q.bias, hf, 0.125f);
-    chain_mma<2>(k.f, x, k.bias);
+    chain_mma(k.f, x, k.bias);
     store_dtok_split(P.kh + (size_t)tok * 64, P.kl + (size_t)tok * 64, k.bias, hf, 1.0f);
-    chain_mma<2>(v.f, x, v.bias);
+    chain_mma(v.f, x, v.bias);
 #pragma unroll
     for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
@@ -262,8 +271,9 @@ __global__ __launch_bounds__(64) void td_layer_bf16_kernel(const int32_t* __rest
         for (int r = 0; r < 16; ++r) { o[0][r] *= alpha; o[1][r] *= alpha; }
 #pragma unroll
         for (int s = 0; s < 2; ++s) {
-            f32x4 ph, pl;
-            split8(sacc, 8 * s, ph, pl);
+            f32x4 p[2];
+            split8(sacc, 8 * s, p);
+            const f32x4 ph = p[0], pl = p[1];          // (by name: see chain_frags)
             o[0] = mfma_bf(vh_[0][s], pl, o[0]); o[1] = mfma_bf(vh_[1][s], pl, o[1]);
             o[0] = mfma_bf(vl_[0][s], ph, o[0]); o[1] = mfma_bf(vl_[1][s], ph, o[1]);
             o[0] = mfma_bf(vh_[0][s], ph, o[0]); o[1] = mfma_bf(vh_[1][s], ph, o[1]);
@@ -275,30 +285,30 @@ __global__ __launch_bounds__(64) void td_layer_bf16_kernel(const int32_t* __rest
     }
     // ---- out-projection, residual + LN1, feed-forward, residual + LN2, next layer's QKV: every parameter block is
     //      requested one phase before its use
-    chain_frags<2> fa, fb;
+    chain_frags<2, 2> fa, fb;
     f32x16 y[2], xr[2], g[2], bt[2], h1[2], h2[2];
-    chain_load<2, 2>(lwb + TDBL_OUT, 0, fa, lane);
+    chain_load<2>(lwb + TDBL_OUT, 0, fa, lane);
     load_dvec<2>(lw + TDL_OUT_B, y, h);
     load_dvec<2>(x_in + (size_t)tok * 64, xr, h);
     const float inv_l = 1.0f / l;
 #pragma unroll
     for (int r = 0; r < 16; ++r) { o[0][r] *= inv_l; o[1][r] *= inv_l; }
-    chain_mma<2>(fa, o, y);
-    chain_load<2, 2>(lwb + TDBL_FF1, 0, fb, lane);
+    chain_mma(fa, o, y);
+    chain_load<2>(lwb + TDBL_FF1, 0, fb, lane);
     load_dvec<2>(lw + TDL_LN1_G, g, h);
     load_dvec<2>(lw + TDL_LN1_B, bt, h);
     load_dvec<2>(lw + TDL_FF1_B, h1, h);
 #pragma unroll
     for (int r = 0; r < 16; ++r) { y[0][r] += xr[0][r]; y[1][r] += xr[1][r]; }
     layernorm64(y, g, bt);
-    chain_mma<2>(fb, y, h1);
-    chain_load<2, 2>(lwb + TDBL_FF2, 0, fa, lane);
+    chain_mma(fb, y, h1);
+    chain_load<2>(lwb + TDBL_FF2, 0, fa, lane);
     load_dvec<2>(lw + TDL_FF2_B, h2, h);
     load_dvec<2>(lw + TDL_LN2_G, g, h);
     load_dvec<2>(lw + TDL_LN2_B, bt, h);
 #pragma unroll
     for (int r = 0; r < 16; ++r) { h1[0][r] = fmaxf(h1[0][r], 0.f); h1[1][r] = fmaxf(h1[1][r], 0.f); }
-    chain_mma<2>(fa, h1, h2);
+    chain_mma(fa, h1, h2);
     qkv_pre qp;
     if (lw_next) qkv_prefetch(lw_next, lwb_next, qp, lane);
 #pragma unroll
@@ -308,10 +318,11 @@ __global__ __launch_bounds__(64) void td_layer_bf16_kernel(const int32_t* __rest
     if (lw_next) qkv_store_bf(lw_next, lwb_next, y, planes_of(qkv_next, (size_t)np * 64), tok, np, lane, qp);
 }
 
-__global__ __launch_bounds__(64) void pool_score_bf16_kernel(const float* __restrict__ x, const int32_t* __restrict__ tok_off,
-                                                             const int32_t* __restrict__ n_wins, int n_clips, int n_heads,
-                                                             const float* __restrict__ pw, const u16* __restrict__ pwb,
-                                                             float* __restrict__ sc, float* __restrict__ yv) {
+// PoolAttFF scores and values of one head for a 32-token tile: one wave per (tile, head), the heads are independent
+template <int T>
+NQ_DEV void pool_score(const float* __restrict__ x, const int32_t* __restrict__ tok_off, const int32_t* __restrict__ n_wins,
+                       int n_clips, const float* __restrict__ pw, const u16* __restrict__ pwb, float* __restrict__ sc,
+                       float* __restrict__ yv) {
     const int lane = threadIdx.x, j = lane & 31, h = lane >> 5;
     const int tile0 = xcd_tile(blockIdx.x, gridDim.x) * 32;
     const int b = find_segment_wave(tok_off, n_clips, tile0, lane);
@@ -319,32 +330,41 @@ __global__ __launch_bounds__(64) void pool_score_bf16_kernel(const float* __rest
     const int tok = tile0 + j;
     f32x16 xr[2];
     load_dvec<2>(x + (size_t)tok * 64, xr, h);
-    {
-        const int hd = blockIdx.y;                           // one wave per (tile, head): the heads are independent
-        const float* w = pw + (size_t)hd * PL_FLOATS;
-        f32x16 hid[4], w2[4], w3[2];
-        chain_frags<4> f;
-        chain_load<4, 4>(pwb + (size_t)hd * PLB_U16S, 0, f, lane);
-        load_dvec<4>(w + PL_B1, hid, h);
-        load_dvec<4>(w + PL_W2, w2, h);
-        load_dvec<2>(w + PL_W3, w3, h);
-        chain_mma<4>(f, xr, hid);
-        float s = 0.f, v = 0.f;
+    const int hd = blockIdx.y;
+    const float* w = pw + (size_t)hd * PL_FLOATS;
+    f32x16 hid[4], w2[4], w3[2];
+    chain_frags<T, 4> f;
+    chain_load<4>(pwb + (size_t)hd * (T == 2 ? PLB_U16S : PLX_U16S), 0, f, lane);
+    load_dvec<4>(w + PL_B1, hid, h);
+    load_dvec<4>(w + PL_W2, w2, h);
+    load_dvec<2>(w + PL_W3, w3, h);
+    chain_mma(f, xr, hid);
+    float s = 0.f, v = 0.f;
 #pragma unroll
-        for (int mt = 0; mt < 4; ++mt)
+    for (int mt = 0; mt < 4; ++mt)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) s = fmaf(w2[mt][r], fmaxf(hid[mt][r], 0.f), s);
+        for (int r = 0; r < 16; ++r) s = fmaf(w2[mt][r], fmaxf(hid[mt][r], 0.f), s);
 #pragma unroll
-        for (int mt = 0; mt < 2; ++mt)
+    for (int mt = 0; mt < 2; ++mt)
 #pragma unroll
-            for (int r = 0; r < 16; ++r) v = fmaf(w3[mt][r], xr[mt][r], v);
-        s += __shfl_xor(s, 32);
-        v += __shfl_xor(v, 32);
-        if (h == 0) {
-            sc[(size_t)tok * 8 + hd] = s + w[PL_B2];
-            yv[(size_t)tok * 8 + hd] = v + w[PL_B2 + 1];
-        }
+        for (int r = 0; r < 16; ++r) v = fmaf(w3[mt][r], xr[mt][r], v);
+    s += __shfl_xor(s, 32);
+    v += __shfl_xor(v, 32);
+    if (h == 0) {
+        sc[(size_t)tok * 8 + hd] = s + w[PL_B2];
+        yv[(size_t)tok * 8 + hd] = v + w[PL_B2 + 1];
     }
+}
+
+// the two kernel symbols (profiles and tools name them)
+#define NQ_POOL_SCORE_ARGS                                                                                                  \
+    const float* __restrict__ x, const int32_t* __restrict__ tok_off, const int32_t* __restrict__ n_wins, int n_clips,     \
+        int n_heads, const float* __restrict__ pw, const u16* __restrict__ pwb, float* __restrict__ sc, float* __restrict__ yv
+__global__ __launch_bounds__(64) void pool_score_bf16_kernel(NQ_POOL_SCORE_ARGS) {
+    pool_score<2>(x, tok_off, n_wins, n_clips, pw, pwb, sc, yv);
+}
+__global__ __launch_bounds__(64) void pool_score_bf16x6_kernel(NQ_POOL_SCORE_ARGS) {
+    pool_score<3>(x, tok_off, n_wins, n_clips, pw, pwb, sc, yv);
 }
 
 extern "C" int nisqa_td_selfatt_bf16(const float* feat, const int32_t* tok_off, const int32_t* n_wins, int32_t n_clips,
@@ -370,21 +390,44 @@ extern "C" int nisqa_td_selfatt_bf16(const float* feat, const int32_t* tok_off, 
     return NQ_LAUNCH_STATUS();
 }
 
-extern "C" int nisqa_pool_score_bf16(const float* x, const int32_t* tok_off, const int32_t* n_wins, int32_t n_clips,
-                                     int32_t total_tok_padded, int32_t n_heads, const float* pool_w, const uint16_t* pool_wb,
-                                     float* ws, void* stream) {
+// the four pooling entries: scores and values into ws ([NP][8] x 2), then -- with `out` -- nisqa_pool_final's softmax over each clip
+static int pool_launch(void (*kernel)(NQ_POOL_SCORE_ARGS), const float* x, const int32_t* tok_off, const int32_t* n_wins,
+                       int32_t n_clips, int32_t total_tok_padded, int32_t n_heads, const float* pool_w, const uint16_t* pool_wb,
+                       float* ws, bool final, float* out, void* stream) {
     if (n_clips <= 0 || total_tok_padded <= 0 || (total_tok_padded & 31) || n_heads < 1 || n_heads > 8 || !pool_wb)
         return NISQA_ERR_ARG;
     NQ_LAUNCH_BEGIN();
-    hipLaunchKernelGGL(pool_score_bf16_kernel, dim3(total_tok_padded / 32, n_heads), dim3(64), 0, (hipStream_t)stream, x, tok_off,
-                       n_wins, n_clips, n_heads, pool_w, pool_wb, ws, ws + (size_t)total_tok_padded * 8);
-    return NQ_LAUNCH_STATUS();
+    hipLaunchKernelGGL(kernel, dim3(total_tok_padded / 32, n_heads), dim3(64), 0, (hipStream_t)stream, x, tok_off, n_wins, n_clips,
+                       n_heads, pool_w, pool_wb, ws, ws + (size_t)total_tok_padded * 8);
+    const int rc = NQ_LAUNCH_STATUS();
+    if (rc || !final) return rc;
+    return nisqa_pool_final(tok_off, n_wins, n_clips, total_tok_padded, n_heads, ws, out, stream);
+}
+
+extern "C" int nisqa_pool_score_bf16(const float* x, const int32_t* tok_off, const int32_t* n_wins, int32_t n_clips,
+                                     int32_t total_tok_padded, int32_t n_heads, const float* pool_w, const uint16_t* pool_wb,
+                                     float* ws, void* stream) {
+    return pool_launch(pool_score_bf16_kernel, x, tok_off, n_wins, n_clips, total_tok_padded, n_heads, pool_w, pool_wb, ws, false,
+                       nullptr, stream);
 }
 
 extern "C" int nisqa_pool_att_bf16(const float* x, const int32_t* tok_off, const int32_t* n_wins, int32_t n_clips,
                                    int32_t total_tok_padded, int32_t n_heads, const float* pool_w, const uint16_t* pool_wb,
                                    float* ws, float* out, void* stream) {
-    const int rc = nisqa_pool_score_bf16(x, tok_off, n_wins, n_clips, total_tok_padded, n_heads, pool_w, pool_wb, ws, stream);
-    if (rc) return rc;
-    return nisqa_pool_final(tok_off, n_wins, n_clips, total_tok_padded, n_heads, ws, out, stream);
+    return pool_launch(pool_score_bf16_kernel, x, tok_off, n_wins, n_clips, total_tok_padded, n_heads, pool_w, pool_wb, ws, true, out,
+                       stream);
+}
+
+extern "C" int nisqa_pool_score_bf16x6(const float* x, const int32_t* tok_off, const int32_t* n_wins, int32_t n_clips,
+                                       int32_t total_tok_padded, int32_t n_heads, const float* pool_w, const uint16_t* pool_wx,
+                                       float* ws, void* stream) {
+    return pool_launch(pool_score_bf16x6_kernel, x, tok_off, n_wins, n_clips, total_tok_padded, n_heads, pool_w, pool_wx, ws, false,
+                       nullptr, stream);
+}
+
+extern "C" int nisqa_pool_att_bf16x6(const float* x, const int32_t* tok_off, const int32_t* n_wins, int32_t n_clips,
+                                     int32_t total_tok_padded, int32_t n_heads, const float* pool_w, const uint16_t* pool_wx,
+                                     float* ws, float* out, void* stream) {
+    return pool_launch(pool_score_bf16x6_kernel, x, tok_off, n_wins, n_clips, total_tok_padded, n_heads, pool_w, pool_wx, ws, true, out,
+                       stream);
 }

@@ -5,6 +5,7 @@ path (mel front end, AdaptCNN, self-attention, attention pooling) runs in the HI
 the C ABI (include/nisqa_hip.h).  No fallback: constructing the engine without a GPU or without
 the built library raises.
 """
+import collections
 import ctypes
 import os
 
@@ -28,8 +29,58 @@ TOK_PAD = 64          # tokens of a clip are padded to whole 64-token workgroups
 # three term products; self-attention and pooling run as in 'bf16x6'.  Measured against float64 they are as close as 'f32' and 'bf16x6'
 # (the same test), at 4 / 3 instead of 6 MFMA products -- but an operand may lose its last bit, so they are opt-in, not the default.
 DEFAULT_PRECISION = 'bf16x6'
-PRECISIONS = ('f32', 'bf16x3', 'bf16x6', 'f16x3', 'f16x4')
-CNN_MODE = {'f32': 0, 'bf16x3': 1, 'bf16x6': 2, 'f16x3': 3, 'f16x4': 4}
+
+
+def _pack_bf16(terms):
+    return lambda sd: _w.pack_adapt_cnn_bf16(sd, conv1_pairs=True, terms=terms)
+
+
+# What a precision IS, stated once: nisqa_model_dev.cnn_mode; the operand format of self-attention and pooling (a key of TD: the f16 CNN
+# modes pair with the three-term kernels); how cnn_wb is packed (None: no 16-bit blob); and per CNN stage -- frame-fed AdaptCNN,
+# segment-fed AdaptCNN, StandardCNN -- the entry point and what it takes between cnn_w and the stream (`terms`: the digit the precision's
+# name ends in; the f16 entries serve both counts).
+Precision = collections.namedtuple('Precision', 'cnn_mode td pack_cnn adapt segments standard')
+_WB, _F16 = 'cnn_wb feat', 'cnn_wb terms feat'
+PRECISION = {
+    'f32': Precision(0, 'f32', None, ('nisqa_cnn_adapt', 'p3 feat'), ('nisqa_cnn_adapt_segments', 'p3 feat'), ('nisqa_cnn_standard', 'p3 feat')),
+    'bf16x3': Precision(1, 'bf16x3', _pack_bf16(2), ('nisqa_cnn_adapt_bf16', 'cnn_wb p3 feat'), ('nisqa_cnn_adapt_segments_bf16', _WB),
+                        ('nisqa_cnn_standard_bf16', _WB)),
+    'bf16x6': Precision(2, 'bf16x6', _pack_bf16(3), ('nisqa_cnn_adapt_bf16x6', _WB), ('nisqa_cnn_adapt_segments_bf16x6', _WB),
+                        ('nisqa_cnn_standard_bf16x6', _WB)),
+    'f16x3': Precision(3, 'bf16x6', _w.pack_adapt_cnn_f16, ('nisqa_cnn_adapt_f16', _F16), ('nisqa_cnn_adapt_segments_f16', _F16),
+                       ('nisqa_cnn_standard_f16', _F16)),
+    'f16x4': Precision(4, 'bf16x6', _w.pack_adapt_cnn_f16, ('nisqa_cnn_adapt_f16', _F16), ('nisqa_cnn_adapt_segments_f16', _F16),
+                       ('nisqa_cnn_standard_f16', _F16)),
+}
+PRECISIONS = tuple(PRECISION)
+CNN_MODE = {p: row.cnn_mode for p, row in PRECISION.items()}
+# Self-attention and pooling per operand format: the two entries (they take the 16-bit blob behind the fp32 one where `terms` is set), the
+# fused self-attention + pooling entry where one exists, and the terms per fragment of td_wb / pool_wb (None: no blob).
+TdFormat = collections.namedtuple('TdFormat', 'selfatt pool fused terms')
+TD = {
+    'f32': TdFormat('nisqa_td_selfatt', 'nisqa_pool_att', None, None),
+    'bf16x3': TdFormat('nisqa_td_selfatt_bf16', 'nisqa_pool_att_bf16', None, 2),
+    'bf16x6': TdFormat('nisqa_td_selfatt_bf16x6', 'nisqa_pool_att_bf16x6', 'nisqa_td_pool_bf16x6', 3),
+}
+# the name a failing entry is reported under, where that is not its own
+WHAT = {'nisqa_cnn_adapt_segments_bf16': 'nisqa_cnn_adapt_segments_bf16x3', 'nisqa_cnn_standard_bf16': 'nisqa_cnn_standard_bf16x3',
+        'nisqa_td_selfatt_bf16': 'nisqa_td_selfatt_bf16x3', 'nisqa_pool_att_bf16': 'nisqa_pool_att_bf16x3'}
+
+
+def cnn_call(precision, stage, head, cnn_wb, p3, feat, stream):
+    """stage: 'adapt' | 'segments' | 'standard'; head: the entry's arguments up to and including cnn_w
+    -> (entry name, the name _lib.check reports, the entry's whole argument list)"""
+    name, tail = getattr(PRECISION[precision], stage)
+    vals = {'cnn_wb': cnn_wb, 'p3': p3, 'feat': feat, 'terms': int(precision[-1])}
+    return name, WHAT.get(name, name), list(head) + [vals[k] for k in tail.split()] + [stream]
+
+
+def td_call(td_precision, stage, head, wb, tail):
+    """stage: 'selfatt' | 'pool'; head: the arguments up to and including the fp32 blob, wb: the 16-bit blob, tail: those behind it
+    -> (entry name, the name _lib.check reports, the entry's whole argument list)"""
+    fmt = TD[td_precision]
+    name = getattr(fmt, stage)
+    return name, WHAT.get(name, name), list(head) + ([wb] if fmt.terms else []) + list(tail)
 
 
 class BatchPlan(object):
@@ -110,6 +161,10 @@ def _ptr(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
+def _or(value, default):
+    return default if value is None else value
+
+
 # pool option of a StandardCNN + BiLSTM model -> nisqa_model_dev.arch / nisqa_lstm_pool's pool_mode
 LSTM_ARCH = {'last_step_bi': 1, 'avg': 2, 'max': 3}
 LSTM_POOL_MODE = {1: _lib.LSTM_POOL_LAST_STEP_BI, 2: _lib.LSTM_POOL_AVG, 3: _lib.LSTM_POOL_MAX}
@@ -186,42 +241,28 @@ class HipNisqa(object):
         self.precision = precision or os.environ.get('NISQA_HIP_PRECISION') or DEFAULT_PRECISION
         if self.precision not in PRECISIONS:
             raise ValueError('precision must be one of {}, got {}'.format(', '.join(PRECISIONS), self.precision))
-        # the operand format of self-attention / pooling: the f16 CNN modes pair with the three-term kernels
-        self.td_precision = 'bf16x6' if self.precision in ('f16x3', 'f16x4') else self.precision
+        row = PRECISION[self.precision]
+        self.td_precision = row.td              # the operand format of self-attention / pooling
+        self.cnn_wb = up(row.pack_cnn(state_dict).view(np.int16)) if row.pack_cnn else None
+        self._mel = {}
+        self._ws = {}                      # one workspace per stream (batches may be in flight on several)
         if self.arch >= 1:
-            # StandardCNN (split-bf16 or exact-fp32 MFMA) + BiLSTM + last-step / average / max pooling (fp32 VALU)
+            # StandardCNN (split 16-bit or exact-fp32 MFMA) + BiLSTM + last-step / average / max pooling (fp32 VALU in every mode)
             self.n_layers, self.n_heads = 0, 1
             self.cnn_w = up(_w.pack_standard_cnn(state_dict))
             self.td_w = up(_w.pack_lstm_laststep(state_dict))
             self.pool_w = torch.zeros(4, dtype=torch.float32, device=self.device)
-            self.cnn_wb = up(_w.pack_adapt_cnn_bf16(state_dict, conv1_pairs=True).view(np.int16)) if self.precision == 'bf16x3' else None
-            if self.precision == 'bf16x6':               # three-term fragments (the BiLSTM and the pooling are fp32 in every mode)
-                self.cnn_wb = up(_w.pack_adapt_cnn_bf16(state_dict, conv1_pairs=True, terms=3).view(np.int16))
-            if self.precision in ('f16x3', 'f16x4'):     # two-term f16 fragments of the scaled weights + per-layer constants
-                self.cnn_wb = up(_w.pack_adapt_cnn_f16(state_dict).view(np.int16))
             self.td_wb = self.pool_wb = None
-            self._mel = {}
-            self._ws = {}
             return
         self.n_layers = int(a['td_sa_num_layers'])
         heads = ['pool_layers.%d.model.' % h for h in range(5)] if self.dim else ['pool.model.']
         self.n_heads = len(heads)
         self.cnn_w = up(_w.pack_adapt_cnn(state_dict))
-        bf = self.precision == 'bf16x3'
-        self.cnn_wb = up(_w.pack_adapt_cnn_bf16(state_dict, conv1_pairs=True).view(np.int16)) if bf else None
-        if self.precision == 'bf16x6':
-            self.cnn_wb = up(_w.pack_adapt_cnn_bf16(state_dict, conv1_pairs=True, terms=3).view(np.int16))
-        if self.precision in ('f16x3', 'f16x4'):
-            self.cnn_wb = up(_w.pack_adapt_cnn_f16(state_dict).view(np.int16))
         self.td_w = up(_w.pack_self_att(state_dict, self.n_layers))
         self.pool_w = up(_w.pack_pool_att(state_dict, heads))
-        self.td_wb = up(_w.pack_self_att_bf16(state_dict, self.n_layers).view(np.int16)) if bf else None
-        self.pool_wb = up(_w.pack_pool_att_bf16(state_dict, heads).view(np.int16)) if bf else None
-        if self.td_precision == 'bf16x6':                    # three-term fragments for self-attention and pooling as well
-            self.td_wb = up(_w.pack_self_att_bf16(state_dict, self.n_layers, terms=3).view(np.int16))
-            self.pool_wb = up(_w.pack_pool_att_bf16(state_dict, heads, terms=3).view(np.int16))
-        self._mel = {}
-        self._ws = {}                      # one workspace per stream (batches may be in flight on several)
+        terms = TD[self.td_precision].terms
+        self.td_wb = up(_w.pack_self_att_bf16(state_dict, self.n_layers, terms=terms).view(np.int16)) if terms else None
+        self.pool_wb = up(_w.pack_pool_att_bf16(state_dict, heads, terms=terms).view(np.int16)) if terms else None
 
     # -- tables -----------------------------------------------------------------------------
     def mel_tables(self, sr):
@@ -349,32 +390,25 @@ class HipNisqa(object):
                    'nisqa_mel_finalize')
         return mel, floor
 
-    def cnn(self, mel_tm, clip_floor, plan):
+    def _cnn_stage(self, stage, head, plan, feat, p3_rows):
+        """run the stage's entry of this precision (head: its arguments up to cnn_w) -> the pooled-conv scratch [NP][p3_rows][64] where
+        the entry writes one, else None"""
+        needs_p3 = 'p3' in getattr(PRECISION[self.precision], stage)[1].split()
+        p3 = torch.empty((plan.total_tok, p3_rows, 64), dtype=torch.float32, device=self.device) if needs_p3 else None
+        name, what, args = cnn_call(self.precision, stage, head + (_ptr(self.cnn_w),), _ptr(self.cnn_wb) if self.cnn_wb is not None else None,
+                                    _ptr(p3) if needs_p3 else None, _ptr(feat), self._stream())
+        _lib.check(getattr(self.lib, name)(*args), what)
+        return p3
+
+    def _mel_head(self, mel_tm, clip_floor, plan):
         d = plan.to(self.device)
-        p3 = torch.empty((plan.total_tok, 18, 64), dtype=torch.float32, device=self.device)
+        return (_ptr(mel_tm), _ptr(d['frame_off']), _ptr(d['tok_off']), _ptr(d['n_wins']), _ptr(clip_floor), plan.n_clips, plan.total_tok,
+                self.seg_hop)
+
+    def cnn(self, mel_tm, clip_floor, plan):
+        """AdaptCNN -> (feat [NP, 384], the pooled conv4 tensor [NP, 18, 64] or None: the one-launch kernels keep it out of memory)"""
         feat = torch.zeros((plan.total_tok, 384), dtype=torch.float32, device=self.device)
-        if self.precision == 'bf16x3':
-            _lib.check(self.lib.nisqa_cnn_adapt_bf16(_ptr(mel_tm), _ptr(d['frame_off']), _ptr(d['tok_off']),
-                                                     _ptr(d['n_wins']), _ptr(clip_floor), plan.n_clips, plan.total_tok,
-                                                     self.seg_hop, _ptr(self.cnn_w), _ptr(self.cnn_wb), _ptr(p3),
-                                                     _ptr(feat), self._stream()), 'nisqa_cnn_adapt_bf16')
-        elif self.precision == 'bf16x6':
-            _lib.check(self.lib.nisqa_cnn_adapt_bf16x6(_ptr(mel_tm), _ptr(d['frame_off']), _ptr(d['tok_off']),
-                                                       _ptr(d['n_wins']), _ptr(clip_floor), plan.n_clips, plan.total_tok,
-                                                       self.seg_hop, _ptr(self.cnn_w), _ptr(self.cnn_wb), _ptr(feat),
-                                                       self._stream()), 'nisqa_cnn_adapt_bf16x6')
-            p3 = None                      # (the one-launch kernel has no pooled conv4 tensor in memory)
-        elif self.precision in ('f16x3', 'f16x4'):
-            _lib.check(self.lib.nisqa_cnn_adapt_f16(_ptr(mel_tm), _ptr(d['frame_off']), _ptr(d['tok_off']), _ptr(d['n_wins']),
-                                                    _ptr(clip_floor), plan.n_clips, plan.total_tok, self.seg_hop, _ptr(self.cnn_w),
-                                                    _ptr(self.cnn_wb), int(self.precision[-1]), _ptr(feat), self._stream()),
-                       'nisqa_cnn_adapt_f16')
-            p3 = None
-        else:
-            _lib.check(self.lib.nisqa_cnn_adapt(_ptr(mel_tm), _ptr(d['frame_off']), _ptr(d['tok_off']), _ptr(d['n_wins']),
-                                                _ptr(clip_floor), plan.n_clips, plan.total_tok, self.seg_hop,
-                                                _ptr(self.cnn_w), _ptr(p3), _ptr(feat), self._stream()), 'nisqa_cnn_adapt')
-        return feat, p3
+        return feat, self._cnn_stage('adapt', self._mel_head(mel_tm, clip_floor, plan), plan, feat, 18)
 
     def forward_segments(self, x, n_wins):
         """Reference inner operator model(x[B,L,1,48,15], n_wins[B]) -> [B, heads] (NL:137-142, NL:260-268)."""
@@ -389,43 +423,15 @@ class HipNisqa(object):
             raise ValueError('n_wins must hold one count in [1, L] per clip')
         plan = BatchPlan.from_n_wins(n)
         d = plan.to(self.device)
-        p3 = torch.empty((plan.total_tok, 18, 64), dtype=torch.float32, device=self.device)
         feat = torch.empty((plan.total_tok, 384), dtype=torch.float32, device=self.device)
-        if self.precision in ('bf16x3', 'bf16x6'):
-            fn = self.lib.nisqa_cnn_adapt_segments_bf16 if self.precision == 'bf16x3' else self.lib.nisqa_cnn_adapt_segments_bf16x6
-            _lib.check(fn(_ptr(x), L, _ptr(d['tok_off']), _ptr(d['n_wins']), B, plan.total_tok, _ptr(self.cnn_w), _ptr(self.cnn_wb),
-                          _ptr(feat), self._stream()), 'nisqa_cnn_adapt_segments_' + self.precision)
-        elif self.precision in ('f16x3', 'f16x4'):
-            _lib.check(self.lib.nisqa_cnn_adapt_segments_f16(_ptr(x), L, _ptr(d['tok_off']), _ptr(d['n_wins']), B, plan.total_tok,
-                                                             _ptr(self.cnn_w), _ptr(self.cnn_wb), int(self.precision[-1]), _ptr(feat),
-                                                             self._stream()), 'nisqa_cnn_adapt_segments_f16')
-        else:
-            _lib.check(self.lib.nisqa_cnn_adapt_segments(_ptr(x), L, _ptr(d['tok_off']), _ptr(d['n_wins']), B,
-                                                         plan.total_tok, _ptr(self.cnn_w), _ptr(p3), _ptr(feat),
-                                                         self._stream()), 'nisqa_cnn_adapt_segments')
+        self._cnn_stage('segments', (_ptr(x), L, _ptr(d['tok_off']), _ptr(d['n_wins']), B, plan.total_tok), plan, feat, 18)
         return self.td_pool(feat, plan)
 
     # -- nisqa_tts.tar stages ------------------------------------------------------------------------
     def cnn_std(self, mel_tm, clip_floor, plan):
         """StandardCNN + fc_out -> feat20 [NP, 20]"""
-        d = plan.to(self.device)
         feat = torch.zeros((plan.total_tok, 20), dtype=torch.float32, device=self.device)
-        if self.precision in ('f16x3', 'f16x4'):
-            _lib.check(self.lib.nisqa_cnn_standard_f16(_ptr(mel_tm), _ptr(d['frame_off']), _ptr(d['tok_off']), _ptr(d['n_wins']),
-                                                       _ptr(clip_floor), plan.n_clips, plan.total_tok, self.seg_hop, _ptr(self.cnn_w),
-                                                       _ptr(self.cnn_wb), int(self.precision[-1]), _ptr(feat), self._stream()),
-                       'nisqa_cnn_standard_f16')
-            return feat
-        if self.precision in ('bf16x3', 'bf16x6'):
-            fn = self.lib.nisqa_cnn_standard_bf16 if self.precision == 'bf16x3' else self.lib.nisqa_cnn_standard_bf16x6
-            _lib.check(fn(_ptr(mel_tm), _ptr(d['frame_off']), _ptr(d['tok_off']), _ptr(d['n_wins']), _ptr(clip_floor), plan.n_clips,
-                          plan.total_tok, self.seg_hop, _ptr(self.cnn_w), _ptr(self.cnn_wb), _ptr(feat), self._stream()),
-                       'nisqa_cnn_standard_' + self.precision)
-            return feat
-        p3 = torch.empty((plan.total_tok, 12, 64), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.nisqa_cnn_standard(_ptr(mel_tm), _ptr(d['frame_off']), _ptr(d['tok_off']), _ptr(d['n_wins']),
-                                               _ptr(clip_floor), plan.n_clips, plan.total_tok, self.seg_hop,
-                                               _ptr(self.cnn_w), _ptr(p3), _ptr(feat), self._stream()), 'nisqa_cnn_standard')
+        self._cnn_stage('standard', self._mel_head(mel_tm, clip_floor, plan), plan, feat, 12)
         return feat
 
     def lstm(self, feat20, plan, want_seq=False, arch=None, want_pooled=False):
@@ -448,47 +454,46 @@ class HipNisqa(object):
                                                 self._stream()), 'nisqa_lstm_pool')
         return (out, seq, hfin) if want_pooled else (out, seq)
 
-    def td(self, feat, plan):
+    def td(self, feat, plan, td_w=None, td_wb=None, n_layers=None):
+        """self-attention -> x [NP, 64]; the weights default to the engine's own"""
+        td_w, td_wb, n_layers = _or(td_w, self.td_w), _or(td_wb, self.td_wb), _or(n_layers, self.n_layers)
         d = plan.to(self.device)
         ws = torch.empty(plan.total_tok * 64 * 9, dtype=torch.float32, device=self.device)
         x = torch.zeros((plan.total_tok, 64), dtype=torch.float32, device=self.device)
-        if self.td_precision in ('bf16x3', 'bf16x6'):
-            fn = self.lib.nisqa_td_selfatt_bf16 if self.td_precision == 'bf16x3' else self.lib.nisqa_td_selfatt_bf16x6
-            _lib.check(fn(_ptr(feat), _ptr(d['tok_off']), _ptr(d['n_wins']), plan.n_clips, plan.total_tok, self.n_layers,
-                          _ptr(self.td_w), _ptr(self.td_wb), _ptr(ws), _ptr(x), self._stream()), 'nisqa_td_selfatt_' + self.td_precision)
-        else:
-            _lib.check(self.lib.nisqa_td_selfatt(_ptr(feat), _ptr(d['tok_off']), _ptr(d['n_wins']), plan.n_clips,
-                                                 plan.total_tok, self.n_layers, _ptr(self.td_w), _ptr(ws), _ptr(x),
-                                                 self._stream()), 'nisqa_td_selfatt')
+        name, what, args = td_call(self.td_precision, 'selfatt',
+                                   (_ptr(feat), _ptr(d['tok_off']), _ptr(d['n_wins']), plan.n_clips, plan.total_tok, n_layers, _ptr(td_w)),
+                                   _ptr(td_wb) if td_wb is not None else None, (_ptr(ws), _ptr(x), self._stream()))
+        _lib.check(getattr(self.lib, name)(*args), what)
         return x
 
-    def td_pool(self, feat, plan):
+    def td_pool(self, feat, plan, td_w=None, td_wb=None, n_layers=None, pool_w=None, pool_wb=None, n_heads=None):
         """self-attention + attention pooling as the whole-batch forward runs them: in the three-term modes ONE chain of
         n_layers + 1 launches (nisqa_td_pool_bf16x6), otherwise td() then pool()"""
-        if self.td_precision != 'bf16x6':
-            return self.pool(self.td(feat, plan), plan)
+        fused = TD[self.td_precision].fused
+        if not fused:
+            return self.pool(self.td(feat, plan, td_w, td_wb, n_layers), plan, pool_w, pool_wb, n_heads)
+        td_w, td_wb, n_layers = _or(td_w, self.td_w), _or(td_wb, self.td_wb), _or(n_layers, self.n_layers)
+        pool_wb, n_heads = _or(pool_wb, self.pool_wb), _or(n_heads, self.n_heads)
         d = plan.to(self.device)
         ws = torch.empty(plan.total_tok * 64 * 9, dtype=torch.float32, device=self.device)
         wsp = torch.empty(plan.total_tok * 16 + plan.n_clips, dtype=torch.float32, device=self.device)
         x = torch.zeros((plan.total_tok, 64), dtype=torch.float32, device=self.device)
-        out = torch.empty((plan.n_clips, self.n_heads), dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.nisqa_td_pool_bf16x6(_ptr(feat), _ptr(d['tok_off']), _ptr(d['n_wins']), plan.n_clips, plan.total_tok,
-                                                 self.n_layers, _ptr(self.td_w), _ptr(self.td_wb), self.n_heads, _ptr(self.pool_wb),
-                                                 _ptr(ws), _ptr(x), _ptr(wsp), _ptr(out), self._stream()), 'nisqa_td_pool_bf16x6')
+        out = torch.empty((plan.n_clips, n_heads), dtype=torch.float32, device=self.device)
+        _lib.check(getattr(self.lib, fused)(_ptr(feat), _ptr(d['tok_off']), _ptr(d['n_wins']), plan.n_clips, plan.total_tok, n_layers,
+                                            _ptr(td_w), _ptr(td_wb), n_heads, _ptr(pool_wb), _ptr(ws), _ptr(x), _ptr(wsp), _ptr(out),
+                                            self._stream()), fused)
         return out
 
-    def pool(self, x, plan):
+    def pool(self, x, plan, pool_w=None, pool_wb=None, n_heads=None):
+        """attention pooling -> [B, n_heads]; the weights default to the engine's own"""
+        pool_w, pool_wb, n_heads = _or(pool_w, self.pool_w), _or(pool_wb, self.pool_wb), _or(n_heads, self.n_heads)
         d = plan.to(self.device)
         ws = torch.empty(plan.total_tok * 16, dtype=torch.float32, device=self.device)
-        out = torch.empty((plan.n_clips, self.n_heads), dtype=torch.float32, device=self.device)
-        if self.td_precision in ('bf16x3', 'bf16x6'):
-            fn = self.lib.nisqa_pool_att_bf16 if self.td_precision == 'bf16x3' else self.lib.nisqa_pool_att_bf16x6
-            _lib.check(fn(_ptr(x), _ptr(d['tok_off']), _ptr(d['n_wins']), plan.n_clips, plan.total_tok, self.n_heads,
-                          _ptr(self.pool_w), _ptr(self.pool_wb), _ptr(ws), _ptr(out), self._stream()), 'nisqa_pool_att_' + self.td_precision)
-        else:
-            _lib.check(self.lib.nisqa_pool_att(_ptr(x), _ptr(d['tok_off']), _ptr(d['n_wins']), plan.n_clips, plan.total_tok,
-                                               self.n_heads, _ptr(self.pool_w), _ptr(ws), _ptr(out), self._stream()),
-                       'nisqa_pool_att')
+        out = torch.empty((plan.n_clips, n_heads), dtype=torch.float32, device=self.device)
+        name, what, args = td_call(self.td_precision, 'pool',
+                                   (_ptr(x), _ptr(d['tok_off']), _ptr(d['n_wins']), plan.n_clips, plan.total_tok, n_heads, _ptr(pool_w)),
+                                   _ptr(pool_wb) if pool_wb is not None else None, (_ptr(ws), _ptr(out), self._stream()))
+        _lib.check(getattr(self.lib, name)(*args), what)
         return out
 
 
@@ -555,8 +560,9 @@ class HipNisqaDE(object):
         up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
         pfx = 'time_dependency_2.model.'
         self.td2_w = up(_w.pack_self_att(state_dict, self.n_layers2, pfx, in_features=self.fuse_width))
-        self.td2_wb = up(_w.pack_self_att_bf16(state_dict, self.n_layers2, pfx, terms=3, in_features=self.fuse_width).view(np.int16)) \
-            if self.base.td_precision == 'bf16x6' else None
+        terms = TD[self.base.td_precision].terms
+        self.td2_wb = up(_w.pack_self_att_bf16(state_dict, self.n_layers2, pfx, terms=terms, in_features=self.fuse_width).view(np.int16)) \
+            if terms else None
 
     def _stream(self):
         return self.base._stream()
@@ -584,24 +590,9 @@ class HipNisqaDE(object):
 
     def td2_pool(self, fused, dplan):
         """time_dependency_2 + pool on the fused features of the degraded clips (dplan: their plan) -> [B, 1]"""
-        d = dplan.to(self.device)
-        np_ = dplan.total_tok
-        ws = torch.empty(np_ * 64 * 9, dtype=torch.float32, device=self.device)
-        x = torch.zeros((np_, 64), dtype=torch.float32, device=self.device)
-        out = torch.empty((dplan.n_clips, 1), dtype=torch.float32, device=self.device)
         b = self.base
-        if b.td_precision == 'bf16x6':
-            wsp = torch.empty(np_ * 16 + dplan.n_clips, dtype=torch.float32, device=self.device)
-            _lib.check(self.lib.nisqa_td_pool_bf16x6(_ptr(fused), _ptr(d['tok_off']), _ptr(d['n_wins']), dplan.n_clips, np_, self.n_layers2,
-                                                     _ptr(self.td2_w), _ptr(self.td2_wb), 1, _ptr(b.pool_wb), _ptr(ws), _ptr(x), _ptr(wsp),
-                                                     _ptr(out), self._stream()), 'nisqa_td_pool_bf16x6')
-            return out
-        _lib.check(self.lib.nisqa_td_selfatt(_ptr(fused), _ptr(d['tok_off']), _ptr(d['n_wins']), dplan.n_clips, np_, self.n_layers2,
-                                             _ptr(self.td2_w), _ptr(ws), _ptr(x), self._stream()), 'nisqa_td_selfatt')
-        wsp = torch.empty(np_ * 16, dtype=torch.float32, device=self.device)
-        _lib.check(self.lib.nisqa_pool_att(_ptr(x), _ptr(d['tok_off']), _ptr(d['n_wins']), dplan.n_clips, np_, 1, _ptr(b.pool_w),
-                                           _ptr(wsp), _ptr(out), self._stream()), 'nisqa_pool_att')
-        return out
+        return b.td_pool(fused, dplan, td_w=self.td2_w, td_wb=self.td2_wb, n_layers=self.n_layers2, pool_w=b.pool_w, pool_wb=b.pool_wb,
+                         n_heads=1)
 
     def forward_features(self, feat, plan, want_idx=False):
         """feat [NP, 384]: AdaptCNN output of the plan's 2B clips -> ([B, 1], hard-mode indices or None)"""

@@ -86,7 +86,7 @@ TDBL_FF1 = TDBL_OUT + 4 * 2 * 2 * 512
 TDBL_FF2 = TDBL_FF1 + 4 * 2 * 2 * 512
 TDBL_U16S = TDBL_FF2 + 4 * 2 * 2 * 512
 PLB_U16S = 4 * 4 * 2 * 512
-# three-term fragments (csrc/td_bf16x6.hip)
+# three-term fragments (csrc/td16_bf16x6.hip, and the pooling of csrc/td_bf16.hip with T = 3)
 TDX_PROJ = 0
 TDX_LAYER0 = TDX_PROJ + 24 * 2 * 3 * 512
 TDXL_QKV = 0

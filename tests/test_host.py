@@ -127,7 +127,7 @@ def test_two_f16_terms_hold_an_fp32_value_to_its_last_bit_or_one_ulp_and_the_f16
 
 
 def test_three_term_linear_fragments_hold_the_weights_exactly():
-    """td_bf16x6.hip: the chain-order fragments [K/16][rows/32][3][64][8] of a linear layer sum to the fp32 weight bit for bit at the
+    """td_bf16.hip with three terms: the chain-order fragments [K/16][rows/32][3][64][8] of a linear layer sum to the fp32 weight bit for bit at the
     k-slot map of the two-term form; blob sizes follow layout.hpp (TDX_*, PLX_*)."""
     rng = np.random.default_rng(3)
     w = (rng.standard_normal((192, 64)) * 10.0 ** rng.uniform(-3, 1, (192, 64))).astype(np.float32)
@@ -1869,3 +1869,42 @@ def test_batch_floor_grows_with_the_job():
         assert NL.batch_policy(Eng(), Ds(), range(10 ** 6), 1).min_tokens == 777
     finally:
         del os.environ['NISQA_MIN_TOKENS']
+
+
+# ---- the engine's precision tables (nisqa_amd/engine.py) against the C ABI's symbol table ----------------------------------
+CNN_STAGE_HEAD = {'adapt': 9, 'segments': 7, 'standard': 9}      # arguments of a CNN entry up to and including cnn_w
+
+
+def test_precision_table_names_declared_entries_with_argument_lists_of_the_declared_length():
+    from nisqa_amd import engine as E, lib as L
+    assert E.PRECISIONS == ('f32', 'bf16x3', 'bf16x6', 'f16x3', 'f16x4')
+    assert E.CNN_MODE == {'f32': 0, 'bf16x3': 1, 'bf16x6': 2, 'f16x3': 3, 'f16x4': 4}          # nisqa_model_dev.cnn_mode (api.hip)
+    for p in E.PRECISIONS:
+        assert E.PRECISION[p].td == ('bf16x6' if p in ('f16x3', 'f16x4') else p)          # the td_precision rule
+        assert (E.PRECISION[p].pack_cnn is None) == (p == 'f32')
+        for stage, n_head in CNN_STAGE_HEAD.items():
+            head = ['head%d' % i for i in range(n_head)]
+            name, what, args = E.cnn_call(p, stage, head, 'cnn_wb', 'p3', 'feat', 'stream')
+            assert name in L.SYMBOLS and what.startswith('nisqa_cnn_'), (p, stage, name)
+            assert len(args) == len(L.SYMBOLS[name][1]), (p, stage, name, args)
+            assert args[:n_head] == head and args[-2:] == ['feat', 'stream'] and len(set(map(str, args))) == len(args)
+            if p in ('f16x3', 'f16x4'):                      # the term count sits where the ABI declares its int32
+                k = args.index(int(p[-1]))
+                assert L.SYMBOLS[name][1][k] is L.c_i32 and args[k - 1] == 'cnn_wb'
+            assert ('cnn_wb' in args) == (p != 'f32')
+    assert E.cnn_call('bf16x3', 'adapt', [0] * 9, 'cnn_wb', 'p3', 'feat', 's')[2][9:] == ['cnn_wb', 'p3', 'feat', 's']
+    assert E.cnn_call('f32', 'standard', [0] * 9, None, 'p3', 'feat', 's')[2][9:] == ['p3', 'feat', 's']
+
+
+def test_self_attention_and_pooling_table_names_declared_entries():
+    from nisqa_amd import engine as E, lib as L
+    assert set(E.TD) == {E.PRECISION[p].td for p in E.PRECISIONS} == {'f32', 'bf16x3', 'bf16x6'}
+    for t, fmt in E.TD.items():
+        assert fmt.terms == {'f32': None, 'bf16x3': 2, 'bf16x6': 3}[t]
+        assert (fmt.fused is not None) == (t == 'bf16x6') and (fmt.fused is None or fmt.fused in L.SYMBOLS)
+        for stage in ('selfatt', 'pool'):
+            head, tail = ['head%d' % i for i in range(7)], ['ws', 'out', 'stream']
+            name, what, args = E.td_call(t, stage, head, 'wb', tail)
+            assert name in L.SYMBOLS and len(args) == len(L.SYMBOLS[name][1]), (t, stage, name)
+            assert args == head + (['wb'] if fmt.terms else []) + tail
+            assert what == (name if t != 'bf16x3' else name + 'x3')          # the labels error messages have always carried
