@@ -248,11 +248,16 @@ int nisqa_softmax_rows_bwd(const float* p, const float* dp, const int64_t* off, 
 int nisqa_elementwise(int32_t op, const float* x, const float* aux, const float* bias, int64_t rows, int32_t cols,
                       float* y, void* stream);
 
-/* biasLoss.get_loss (NISQA_lib.py:1880-1892, 1946-1950): loss = sum_h mean_{b: y not NaN} (map_b(y_hat) - y)^2,
- * map_b = cubic with coefficients bias[b][4] (NULL: identity).  Writes loss[1 + heads] (total, then one term per head) and
- * dy_hat[B][heads]. */
+/* biasLoss.get_loss (NISQA_lib.py:1880-1892, 1946-1950): loss = sum_h mean_{b: y not NaN} (map_bh(y_hat[b][h]) - y[b][h])^2,
+ * map_bh(v) = q0 + q1 v + q2 v^2 + q3 v^3 (NULL: identity), d y_hat[b][h] = 2 e / count_h * (q1 + 2 q2 v + 3 q3 v^2).  Writes
+ * loss[1 + heads] (total, then one term per head) and dy_hat[B][heads].
+ *   nisqa_mse_loss        q = bias[b][4]: one mapping per clip, shared by the heads (the one-headed models);
+ *   nisqa_mse_loss_heads  q = bias[b][h][4]: one mapping per clip AND head (NISQA_DIM keeps five biasLoss objects,
+ *                         NISQA_model.py:256-371).  With n_heads == 1 the two are the same. */
 int nisqa_mse_loss(const float* y_hat, const float* y, const float* bias, int32_t n_clips, int32_t n_heads,
                    float* loss, float* dy_hat, void* stream);
+int nisqa_mse_loss_heads(const float* y_hat, const float* y, const float* bias, int32_t n_clips, int32_t n_heads,
+                         float* loss, float* dy_hat, void* stream);
 
 /* Dropout multipliers (nn.Dropout / Dropout2d in train mode): out[i] = u_i >= p ? 1/(1-p) : 0 with u_i the i-th value of the
  * Philox-4x32-10 stream (seed, offset counts groups of four values); the reference draws its masks from torch's global
@@ -310,9 +315,11 @@ int nisqa_adam_step(float* param, const float* grad, float* m, float* v, int64_t
  *   uploads and passes back as wgrad_desc / colsum_jobs.  cap = capacity of out in int64s.
  * nisqa_tdtrain_step: forward, loss, backward.  Adds every parameter gradient of the block into `grads` (zeroed by the
  *   caller), writes y_hat, loss and the feature gradient.  labels [n_clips][n_heads] (NaN = unlabelled), bias_map [n_clips][4]
- *   cubic coefficients or NULL, inv_count [n_heads] = 1 / (labelled clips of the whole batch, all ranks) or 0.  mask_* are the
+ *   cubic coefficients (one mapping per clip, applied to every head) or NULL, inv_count [n_heads] = 1 / (labelled clips of the whole batch, all ranks) or 0.  mask_* are the
  *   dropout multipliers of each layer in the CALLER's token order (mask_p: [sum L^2] attention probabilities, row-major per
- *   clip at sq_off; mask_1 / mask_f / mask_2: [n_tokens][64]) or NULL. */
+ *   clip at sq_off; mask_1 / mask_f / mask_2: [n_tokens][64]) or NULL.
+ * nisqa_tdtrain_step_heads: the same step with bias_map read as [n_clips][n_heads][4], one mapping per clip and head (see
+ *   nisqa_mse_loss_heads); everything else, the layout of the arguments included, is nisqa_tdtrain_step's. */
 typedef struct nisqa_tdtrain_args {
     int32_t n_clips, n_tokens, n_tokens_padded, n_layers, n_heads, n_wgrad_groups, n_wgrad_tiles, n_colsum_jobs;
     const int32_t* seg_off;      /* device [n_clips + 1] */
@@ -325,7 +332,7 @@ typedef struct nisqa_tdtrain_args {
     float* ws;                   /* device, out[0] floats */
     float* frags;                /* device, out[1] floats */
     const float* labels;         /* device */
-    const float* bias_map;       /* device or NULL */
+    const float* bias_map;       /* device or NULL: [n_clips][4], or [n_clips][n_heads][4] for nisqa_tdtrain_step_heads */
     const float* inv_count;      /* device [n_heads] */
     const float* mask_p[4];
     const float* mask_1[4];
@@ -337,6 +344,7 @@ typedef struct nisqa_tdtrain_args {
 int nisqa_tdtrain_plan(int32_t n_clips, int32_t n_tokens, int32_t n_tokens_padded, int32_t n_layers, int32_t n_heads,
                        const int32_t* poff, int64_t* out, int64_t cap);
 int nisqa_tdtrain_step(const nisqa_tdtrain_args* args, void* stream);
+int nisqa_tdtrain_step_heads(const nisqa_tdtrain_args* args, void* stream);
 
 #ifdef __cplusplus
 }

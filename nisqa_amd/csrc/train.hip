@@ -1891,8 +1891,9 @@ extern "C" int nisqa_elementwise(int32_t op, const float* x, const float* aux, c
 }
 
 __global__ __launch_bounds__(64) void mse_loss_kernel(const float* __restrict__ y_hat, const float* __restrict__ y,
-                                                      const float* __restrict__ bias, int n_clips, int n_heads,
-                                                      float* __restrict__ loss, float* __restrict__ dy_hat) {
+                                                      const float* __restrict__ bias, int clip_stride, int head_stride,
+                                                      int n_clips, int n_heads, float* __restrict__ loss,
+                                                      float* __restrict__ dy_hat) {
     __shared__ float part[64];
     const int hd = threadIdx.x;
     float l = 0.f;
@@ -1904,7 +1905,7 @@ __global__ __launch_bounds__(64) void mse_loss_kernel(const float* __restrict__ 
             const float t = y[b * n_heads + hd], v = y_hat[b * n_heads + hd];
             float mapped = v, slope = 1.f;
             if (bias) {
-                const float* q = bias + b * 4;
+                const float* q = bias + b * clip_stride + hd * head_stride;
                 mapped = q[0] + v * (q[1] + v * (q[2] + v * q[3]));
                 slope = q[1] + v * (2.f * q[2] + 3.f * v * q[3]);
             }
@@ -1927,13 +1928,24 @@ __global__ __launch_bounds__(64) void mse_loss_kernel(const float* __restrict__ 
     }
 }
 
-extern "C" int nisqa_mse_loss(const float* y_hat, const float* y, const float* bias, int32_t n_clips, int32_t n_heads,
-                              float* loss, float* dy_hat, void* stream) {
+// bias rows [n_clips][4] shared by the heads (head stride 0) or [n_clips][n_heads][4] (one mapping per head): one kernel body
+static int mse_loss(const float* y_hat, const float* y, const float* bias, bool per_head, int32_t n_clips, int32_t n_heads,
+                    float* loss, float* dy_hat, void* stream) {
     if (!y_hat || !y || !loss || !dy_hat || n_clips <= 0 || n_heads <= 0 || n_heads > 64) return NISQA_ERR_ARG;
     NQ_LAUNCH_BEGIN();
-    hipLaunchKernelGGL(mse_loss_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, y_hat, y, bias, n_clips, n_heads, loss,
-                       dy_hat);
+    hipLaunchKernelGGL(mse_loss_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, y_hat, y, bias, per_head ? 4 * n_heads : 4,
+                       per_head ? 4 : 0, n_clips, n_heads, loss, dy_hat);
     return NQ_LAUNCH_STATUS();
+}
+
+extern "C" int nisqa_mse_loss(const float* y_hat, const float* y, const float* bias, int32_t n_clips, int32_t n_heads,
+                              float* loss, float* dy_hat, void* stream) {
+    return mse_loss(y_hat, y, bias, false, n_clips, n_heads, loss, dy_hat, stream);
+}
+
+extern "C" int nisqa_mse_loss_heads(const float* y_hat, const float* y, const float* bias, int32_t n_clips, int32_t n_heads,
+                                    float* loss, float* dy_hat, void* stream) {
+    return mse_loss(y_hat, y, bias, true, n_clips, n_heads, loss, dy_hat, stream);
 }
 
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,

@@ -420,6 +420,7 @@ __global__ __launch_bounds__(64) void tdt_layer_fwd_kernel(tdt_common c, tdt_lay
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void tdt_pool_clip_kernel(tdt_common c, tdt_heads hs, const float* __restrict__ x,
                                                             const float* __restrict__ labels, const float* __restrict__ bias_map,
+                                                            int map_clip_stride, int map_head_stride,
                                                             const float* __restrict__ inv_cnt, float* __restrict__ y_hat,
                                                             float* __restrict__ loss) {
     __shared__ float red[256];
@@ -467,7 +468,7 @@ __global__ __launch_bounds__(256) void tdt_pool_clip_kernel(tdt_common c, tdt_he
             if (!isnan(tgt)) {
                 float mapped = yv, slope = 1.f;
                 if (bias_map) {
-                    const float* q = bias_map + b * 4;
+                    const float* q = bias_map + b * map_clip_stride + hd * map_head_stride;
                     mapped = q[0] + yv * (q[1] + yv * (q[2] + yv * q[3]));
                     slope = q[1] + yv * (2.f * q[2] + 3.f * yv * q[3]);
                 }
@@ -998,7 +999,8 @@ extern "C" int nisqa_tdtrain_plan(int32_t n_clips, int32_t n_tokens, int32_t n_t
     return NISQA_OK;
 }
 
-extern "C" int nisqa_tdtrain_step(const nisqa_tdtrain_args* a, void* stream) {
+// bias_map rows [n_clips][4] shared by the heads, or (per_head) [n_clips][n_heads][4]
+static int tdt_step(const nisqa_tdtrain_args* a, bool per_head, void* stream) {
     if (!a || !tdt_dims_ok(a->n_clips, a->n_tokens, a->n_tokens_padded, a->n_layers, a->n_heads) || !a->seg_off || !a->ptok_off ||
         !a->tile_clip || !a->sq_off || !a->params || !a->grads || !a->poff || !a->ws || !a->frags || !a->labels || !a->inv_count ||
         !a->wgrad_desc || !a->colsum_jobs)
@@ -1081,7 +1083,7 @@ extern "C" int nisqa_tdtrain_step(const nisqa_tdtrain_args* a, void* stream) {
                            (const float*)(ws + y.x[l]), ws + y.x[l + 1], hs);
     }
     hipLaunchKernelGGL(tdt_pool_clip_kernel, dim3(B, nh), dim3(256), 0, st, c, hs, (const float*)(ws + y.x[nl]), a->labels, a->bias_map,
-                       a->inv_count, ws + y.yhat, ws + y.loss);
+                       per_head ? 4 * nh : 4, per_head ? 4 : 0, a->inv_count, ws + y.yhat, ws + y.loss);
     // backward
     hipLaunchKernelGGL(tdt_bwd_tail_kernel, dim3(tiles), dim3(64), 0, st, c, Lp[nl - 1], hs, (const float*)(ws + y.x[nl]));
     for (int l = nl - 1; l >= 0; --l) {
@@ -1102,3 +1104,7 @@ extern "C" int nisqa_tdtrain_step(const nisqa_tdtrain_args* a, void* stream) {
                        (const float*)ws, G);
     return NQ_LAUNCH_STATUS();
 }
+
+extern "C" int nisqa_tdtrain_step(const nisqa_tdtrain_args* a, void* stream) { return tdt_step(a, false, stream); }
+
+extern "C" int nisqa_tdtrain_step_heads(const nisqa_tdtrain_args* a, void* stream) { return tdt_step(a, true, stream); }

@@ -95,6 +95,7 @@ c_f = ctypes.c_float
 TRAIN_SYMBOLS = {
     'nisqa_tdtrain_plan': (ctypes.c_int, [c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_i64]),
     'nisqa_tdtrain_step': (ctypes.c_int, [ctypes.POINTER(TdTrainArgs), c_p]),
+    'nisqa_tdtrain_step_heads': (ctypes.c_int, [ctypes.POINTER(TdTrainArgs), c_p]),
     'nisqa_gemm_f32': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_f, c_p]),
     'nisqa_gemm_f32_one': (ctypes.c_int, [c_p, c_p, c_p, c_i64, c_i64, c_i64, c_i64, c_i64, c_i64, c_i32, c_i32, c_i32,
                                           c_f, c_p, c_i32, c_p]),
@@ -145,6 +146,7 @@ TRAIN_SYMBOLS = {
     'nisqa_softmax_rows_bwd': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_f, c_p, c_p]),
     'nisqa_elementwise': (ctypes.c_int, [c_i32, c_p, c_p, c_p, c_i64, c_i32, c_p, c_p]),
     'nisqa_mse_loss': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, c_p, c_p, c_p]),
+    'nisqa_mse_loss_heads': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, c_p, c_p, c_p]),
     'nisqa_dropout_mask': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, c_f, c_i64, c_p, c_p]),
     'nisqa_cast_scatter': (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_p]),
     'nisqa_adam_step': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_f, c_i32, c_p]),

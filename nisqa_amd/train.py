@@ -89,6 +89,36 @@ def feat_from_kernel(w):
     return w.reshape(w.shape[0], -1, 64).permute(0, 2, 1).reshape(w.shape[0], -1)
 
 
+def bias_rows(bias, n_clips, n_heads):
+    """The bias-aware loss's cubic coefficients as the loss kernels read them: ``bias`` [B, 4] (one mapping per clip, shared
+    by the heads) or [B, H, 4] (one per clip and head: NISQA_DIM's five biasLoss objects) -> (float32 [B, 4] or [B, H * 4],
+    per_head).  With one head the two forms are the same thing and the shared form is what comes back."""
+    a = np.asarray(bias, np.float32)
+    if a.shape == (n_clips, 4):
+        return np.ascontiguousarray(a), False
+    if a.shape == (n_clips, n_heads, 4):
+        return np.ascontiguousarray(a.reshape(n_clips, n_heads * 4)), n_heads > 1
+    raise ValueError('bias coefficients of shape {}: [{}, 4] or [{}, {}, 4] expected'.format(a.shape, n_clips, n_clips, n_heads))
+
+
+def concat_groups(frame_offs, n_wins):
+    """One batch staged as several groups of clips (one per sample rate, each with its own spectrogram [frames_g][48]): the
+    frame offsets and segment counts of the batch with the groups' spectrograms back to back -- every group's offsets shifted
+    by the frames before it -- and the clip order, [B][2] = (group, clip in the group).  Host arithmetic only.  One group
+    comes back as it went in (the same objects)."""
+    order = np.array([(g, i) for g, n in enumerate(n_wins) for i in range(len(n))], dtype=np.int64).reshape(-1, 2)
+    if len(frame_offs) == 1:
+        return frame_offs[0], n_wins[0], order
+    for f, n in zip(frame_offs, n_wins):
+        if len(f) != len(n) + 1 or int(f[0]) != 0:
+            raise ValueError('a group needs frame offsets [n_clips + 1] starting at 0 and n_wins [n_clips]')
+    base = np.concatenate(([0], np.cumsum([int(f[-1]) for f in frame_offs], dtype=np.int64)))
+    off = np.concatenate([np.asarray(f[:-1], np.int64) + b for f, b in zip(frame_offs, base)] + [base[-1:]])
+    if int(off[-1]) >= 2 ** 31:
+        raise ValueError('{} spectrogram frames in one batch'.format(int(off[-1])))
+    return off.astype(np.int32), np.concatenate([np.asarray(n, np.int32) for n in n_wins]), order
+
+
 class _FlatTrainer(object):
     """What the HIP training steps share: every parameter in ONE flat device buffer in kernel layout (``_to_kernel`` /
     ``_from_kernel`` convert to and from the reference's shapes), its gradient buffer, the BatchNorm buffers of
@@ -244,6 +274,20 @@ class _FlatTrainer(object):
         mel, floor = self.eng.mel(pcm, plan, sr, clamp=False)
         d = plan.to(self.device)
         return self._step(mel, d['frame_off'], plan.n_wins, floor, y, masks, bias)
+
+    def step_groups(self, groups, y, masks=None, bias=None):
+        """One step on a batch staged as several groups, [(pcm, plan, sr), ...] (the ingest stages one group per sample rate;
+        train-mode BatchNorm spans the batch, so it is not split): the mel front end runs per group at that group's rate, the
+        spectrograms go back to back into one buffer and everything behind them is one ``_step``.  ``y``, ``bias`` and the
+        returned ``y_hat`` are in the concatenated clip order (concat_groups).  One group is exactly ``step_pcm``."""
+        if len(groups) == 1:
+            return self.step_pcm(groups[0][0], groups[0][1], groups[0][2], y, masks, bias)
+        mels, floors = zip(*[self.eng.mel(pcm, plan, sr, clamp=False) for pcm, plan, sr in groups])
+        frame_off, n_wins, _ = concat_groups([plan.frame_off for _, plan, _ in groups], [plan.n_wins for _, plan, _ in groups])
+        pin = self.device.type == 'cuda'
+        host = torch.empty(frame_off.shape, dtype=torch.int32, pin_memory=pin)
+        host.numpy()[...] = frame_off
+        return self._step(torch.cat(mels), host.to(self.device, non_blocking=pin), n_wins, torch.cat(floors), y, masks, bias)
 
     def step_spec(self, specs, y, masks=None, bias=None):
         """specs: list of [48, T] dB spectrograms (the input of segment_specs) -- used by the parity tests."""
@@ -660,7 +704,8 @@ class HipTrainer(_FlatTrainer):
         return pl
 
     def _td_fused(self, y, bias, masks):
-        """nisqa_tdtrain_step on the features the CNN left in the workspace -> (y_hat, loss, d loss / d feat)."""
+        """nisqa_tdtrain_step (nisqa_tdtrain_step_heads when ``bias`` holds one mapping per head) on the features the CNN left
+        in the workspace -> (y_hat, loss, d loss / d feat)."""
         pl, tv = self._td_plan_cur, self._tv
         B, S, H = self.B, self.S, len(self.heads)
         yv = np.asarray(y, np.float32).reshape(B, H)
@@ -669,7 +714,10 @@ class HipTrainer(_FlatTrainer):
             cnt = _dist.all_reduce_sum_(torch.from_numpy(cnt.copy())).numpy()
         inv = np.where(cnt > 0, 1.0 / np.maximum(cnt, 1), 0.0).astype(np.float32)
         # labels, 1 / count per head and the bias-mapping coefficients in ONE page-locked upload
-        n_host = B * H + 8 + (B * 4 if bias is not None else 0)
+        per_head = False
+        if bias is not None:
+            bias, per_head = bias_rows(bias, B, H)
+        n_host = B * H + 8 + (bias.size if bias is not None else 0)
         pin = self.device.type == 'cuda'
         host = torch.empty(n_host, dtype=torch.float32, pin_memory=pin)
         hv = host.numpy()
@@ -677,7 +725,7 @@ class HipTrainer(_FlatTrainer):
         hv[B * H:B * H + 8] = 0
         hv[B * H:B * H + H] = inv
         if bias is not None:
-            hv[B * H + 8:] = np.asarray(bias, np.float32).reshape(-1)
+            hv[B * H + 8:] = bias.reshape(-1)
         dev = host.to(self.device, non_blocking=pin)
         a = _lib.TdTrainArgs()
         a.n_clips, a.n_tokens, a.n_tokens_padded, a.n_layers, a.n_heads = B, S, pl['NP'], self.n_layers, H
@@ -697,7 +745,8 @@ class HipTrainer(_FlatTrainer):
                 keep.append(m)
                 field[l] = m.data_ptr() if m is not None else None
         a.wgrad_desc, a.colsum_jobs = tv['td_desc'].data_ptr(), tv['td_jobs'].data_ptr()
-        self._ck(self.lib.nisqa_tdtrain_step(ctypes.byref(a), self._st()), 'nisqa_tdtrain_step')
+        entry = 'nisqa_tdtrain_step_heads' if per_head else 'nisqa_tdtrain_step'
+        self._ck(getattr(self.lib, entry)(ctypes.byref(a), self._st()), entry)
         self._td_keep = keep                            # explicit masks / the label buffer stay alive until the step has run
         ws = self._td_ws
         # y_hat and the loss leave the persistent workspace as fresh tensors: the next step overwrites the workspace, and a
@@ -709,7 +758,7 @@ class HipTrainer(_FlatTrainer):
         da = ws[pl['dfeat']:pl['dfeat'] + S * 384].view(S, 6, 64)
         return y_hat, loss, da
 
-    def _td_unfused(self, feat, y, y_dev, bias_dev, masks):
+    def _td_unfused(self, feat, y, y_dev, bias_dev, per_head, masks):
         """The self-attention block, the pooling heads and the loss operator by operator (round-3 path, ~116 launches; kept
         behind NISQA_HIP_TRAIN_FUSED_TD=0 as the cross-check of csrc/train_td.hip) -> (y_hat, loss, d loss / d feat)."""
         L_ = self.lib
@@ -770,8 +819,9 @@ class HipTrainer(_FlatTrainer):
         self._ew(0, y_hat, bias=b3, rows=B, cols=H)
         loss_v = self._new(1 + H)
         dyh = self._new(B, H)
-        self._ck(L_.nisqa_mse_loss(_ptr(y_hat), _ptr(y_dev), _ptr(bias_dev) if bias_dev is not None else None, B, H,
-                                   _ptr(loss_v), _ptr(dyh), st), 'nisqa_mse_loss')
+        entry = 'nisqa_mse_loss_heads' if per_head else 'nisqa_mse_loss'
+        self._ck(getattr(L_, entry)(_ptr(y_hat), _ptr(y_dev), _ptr(bias_dev) if bias_dev is not None else None, B, H,
+                                    _ptr(loss_v), _ptr(dyh), st), entry)
         loss = loss_v[:1]
         if _dist.world()[1] > 1:
             # the loss is a mean over the labelled clips of the WHOLE batch: rescale this rank's share per head
@@ -838,9 +888,12 @@ class HipTrainer(_FlatTrainer):
         self._prepare(n_wins)
         self.gflat.zero_()
         y_dev = bias_dev = feat_out = None
+        per_head = False
         if not self.fused_td:
             y_dev = self._upload(y, len(self.heads))
-            bias_dev = None if bias is None else self._upload(bias, 4)
+            if bias is not None:
+                rows, per_head = bias_rows(bias, self.B, len(self.heads))
+                bias_dev = self._upload(rows, rows.shape[1])
         else:                                               # the CNN writes its features straight into the fused block's workspace
             pl = self._td_buffers()
             feat_out = self._td_ws[pl['feat']:pl['feat'] + self.S * 384]
@@ -849,7 +902,7 @@ class HipTrainer(_FlatTrainer):
         if self.fused_td:
             y_hat, loss, da = self._td_fused(y, bias, masks)
         else:
-            y_hat, loss, da = self._td_unfused(feat, y, y_dev, bias_dev, masks)
+            y_hat, loss, da = self._td_unfused(feat, y, y_dev, bias_dev, per_head, masks)
         da = [da]
         self._cnn_bwd(cnn, da)
         return self._finish_step(y_hat, loss)

@@ -29,7 +29,7 @@ import torch
 
 from . import dist as _dist
 from .engine import HipNisqa, check_lstm_args, LSTM_POOL_MODE
-from .train import _FlatTrainer, _BN_BUFFERS, _ptr, feat_to_kernel, feat_from_kernel
+from .train import _FlatTrainer, _BN_BUFFERS, _ptr, bias_rows, feat_to_kernel, feat_from_kernel
 
 # conv output (H, W) and the pool after it: pool_first 48 x 15 -> 24 x 8, pool after conv2 and conv4, identity elsewhere
 GEO = [(48, 15, (24, 8)), (24, 8, (12, 4)), (12, 4, (12, 4)), (12, 4, (6, 2)), (6, 2, (6, 2)), (6, 2, (6, 2))]
@@ -115,7 +115,7 @@ class HipTrainerLSTM(_FlatTrainer):
         P, G = self.P, self.G
         self.gflat.zero_()
         y_dev = self._upload(y, 1)
-        bias_dev = None if bias is None else self._upload(bias, 4)
+        bias_dev = None if bias is None else self._upload(bias_rows(bias, B, 1)[0], 4)      # [B,4] or [B,1,4]: one head
         cnn, act = self._cnn_fwd(mel, frame_off, floor, masks)
         feat = act.view(S, 768)                                               # [S][12 pixels][64] in (pixel, c) order
         x20 = self._linear_fwd(feat, FC_W, 'cnn.model.fc_out.bias', S, 768, 20)

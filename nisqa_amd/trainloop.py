@@ -5,6 +5,15 @@ ReduceLROnPlateau, early stopping, results CSV and checkpoints -- around the per
 train mode, backward, Adam).  WAV files reach the GPU through the same
 native ingest as prediction (``nisqa_amd.ingest``); the validation pass is the inference engine on the current weights.
 
+Bias-aware loss (``tr_bias_mapping: first_order``): one ``biasLoss`` per head, as the reference keeps them (NISQA_model.py:
+256-371) -- each estimates its own per-database line from that head's predictions after every epoch, and a batch's step gets
+the rows of all of them as ``[B, heads, 4]`` (``[B, 1, 4]`` for the one-headed models, which is the shared ``[B, 4]`` form).
+
+Sample rates: the ingest stages a batch as one group of clips per rate.  A batch that mixes rates stays ONE step (train-mode
+BatchNorm spans the batch): every group is copied, resampled (``ms_sr``) and converted on its own, the trainer computes each
+group's spectrogram at that group's rate and runs the rest once (``step_groups``).  Labels, bias rows and predictions follow
+the step's clip order, group after group.
+
 One loop serves both model types: ``targets`` is ['mos'] (well: csv_mos_train) for NISQA and
 ['mos', 'noi', 'dis', 'col', 'loud'] for NISQA_DIM, with the reference's key suffixes ('', '_noi', ...) in the result
 dicts, its printed lines and its checkpoint dictionary (so ``run_predict.py`` loads what this writes, here and in the
@@ -31,7 +40,7 @@ from .train_lstm import HipTrainerLSTM
 class biasLoss(object):
     """Per-database first-order bias of the predictions (reference NISQA_lib.py:1855-1950): once the epoch's Pearson
     correlation exceeds ``min_r`` every database gets the line mapping its predictions onto its labels, and the loss
-    is taken after that mapping (``b`` rows of the samples in the batch go to the loss kernel)."""
+    is taken after that mapping (``b`` rows of the samples in the batch go to the loss kernel).  One object per head."""
 
     def __init__(self, db, anchor_db=None, mapping='first_order', min_r=0.7, loss_weight=0.0, do_print=True):
         self.db, self.mapping, self.min_r, self.anchor_db = db, mapping, min_r, anchor_db
@@ -190,31 +199,31 @@ def train(nm):
         pending = None                                                   # (idx, device y_hat, device loss) of the last step
         try:
             for staged in ing:
-                if len(staged.groups) != 1:
-                    ing.ring.release_after(staged.slot, None)
-                    raise NotImplementedError('a training batch mixes sample rates {}: BatchNorm statistics span the batch, '
-                                              'so it cannot be split'.format([g.sr for g in staged.groups]))
-                g = staged.groups[0]
-                plan = tr.eng.audio_plan(g.lengths, g.sr, names=g.names)     # (at ms_sr when the run sets it: lb.load resamples)
+                # one group per sample rate in the batch (the reference loads every file at its own rate, NISQA_lib.py:2299-2310):
+                # train-mode BatchNorm spans the batch, so the groups stay ONE step -- only the spectrogram is per group
                 raw = ing.ring.buf[staged.slot]
-                host = raw[g.offset:g.offset + g.nbytes].view(torch.int16 if g.is_i16 else torch.float32)
-                pcm = host.to(tr.device, non_blocking=True)
+                pcms = []
+                for g in staged.groups:
+                    host = raw[g.offset:g.offset + g.nbytes].view(torch.int16 if g.is_i16 else torch.float32)
+                    pcms.append(host.to(tr.device, non_blocking=True))
                 ev = torch.cuda.Event()
-                ev.record()
+                ev.record()                                              # behind the last group's copy
                 ing.ring.release_after(staged.slot, ev)
-                pcm = tr.eng.resample(pcm, g.lengths, g.sr)              # a no-op unless ms_sr is set and differs from the files' rate
-                if pcm.dtype == torch.int16:
-                    pcm = tr.eng.pcm16_to_f32(pcm)
-                ids = np.asarray(g.ids)
+                groups = []
+                for g, pcm in zip(staged.groups, pcms):
+                    plan = tr.eng.audio_plan(g.lengths, g.sr, names=g.names)     # (at ms_sr when the run sets it: lb.load resamples)
+                    pcm = tr.eng.resample(pcm, g.lengths, g.sr)          # a no-op unless ms_sr is set and differs from the files' rate
+                    if pcm.dtype == torch.int16:
+                        pcm = tr.eng.pcm16_to_f32(pcm)
+                    groups.append((pcm, plan, tr.eng.rate(g.sr)))
+                ids = np.concatenate([np.asarray(g.ids) for g in staged.groups])     # the clip order of the step: group after group
                 bias = None
-                if losses[0].apply_bias_loss:
-                    if len(names) > 1:
-                        raise NotImplementedError('bias loss for NISQA_DIM needs one mapping per head (not built)')
-                    bias = losses[0].rows(ids)
+                if losses[0].apply_bias_loss:                            # [B, heads, 4]: every head's own line per database
+                    bias = np.stack([bl.rows(ids) for bl in losses], 1)
                 if pending is not None:                                  # fetch the previous step's numbers while this one runs
                     y_hat_train[pending[0]] = pending[1].cpu().numpy()
                     loss_sum += float(pending[2])
-                loss = tr.step_pcm(pcm, plan, tr.eng.rate(g.sr), y_train[ids].astype(np.float32), bias=bias)
+                loss = tr.step_groups(groups, y_train[ids].astype(np.float32), bias=bias)
                 pending = (ids, tr.last['y_hat'], loss)
             if pending is not None:
                 y_hat_train[pending[0]] = pending[1].cpu().numpy()
