@@ -258,6 +258,26 @@ int nisqa_cnn_standard_f16(const float* mel_tm, const int32_t* frame_off, const 
                            const int32_t* n_wins, const float* clip_floor, int32_t n_clips,
                            int32_t total_tok_padded, int32_t seg_hop, const float* cnn_std_w,
                            const uint16_t* cnn_wh, int32_t products, float* feat20, void* stream);
+/* Segment-tensor input mode of the four entries above: the reference's inner operator model.forward(x, n_wins)
+ * (NISQA.forward, NISQA_lib.py:137-142: Framewise.forward over x, NISQA_lib.py:487-502, then StandardCNN.forward incl. fc_out,
+ * NISQA_lib.py:811-836) hands over x[B][seg_len_padded][1][48][15] (zero-padded to seg_len_padded segments per clip; segments
+ * k >= n_wins[b] are never read).  Same feat20 output as the frame-fed entry of the same precision -- bit for bit where x holds
+ * the windows the frame-fed entry cuts from the floored spectrogram -- and the same blobs; no dB floor is applied (x is already
+ * clamped).  A NULL x, seg_len_padded <= 0, n_clips <= 0, total_tok_padded not a positive multiple of 32 or products outside
+ * {3, 4} return NISQA_ERR_ARG before any launch. */
+int nisqa_cnn_standard_segments(const float* x, int32_t seg_len_padded, const int32_t* tok_off,
+                                const int32_t* n_wins, int32_t n_clips, int32_t total_tok_padded,
+                                const float* cnn_std_w, float* p3_ws, float* feat20, void* stream);
+int nisqa_cnn_standard_segments_bf16(const float* x, int32_t seg_len_padded, const int32_t* tok_off,
+                                     const int32_t* n_wins, int32_t n_clips, int32_t total_tok_padded,
+                                     const float* cnn_std_w, const uint16_t* cnn_wb, float* feat20, void* stream);
+int nisqa_cnn_standard_segments_bf16x6(const float* x, int32_t seg_len_padded, const int32_t* tok_off,
+                                       const int32_t* n_wins, int32_t n_clips, int32_t total_tok_padded,
+                                       const float* cnn_std_w, const uint16_t* cnn_wx, float* feat20, void* stream);
+int nisqa_cnn_standard_segments_f16(const float* x, int32_t seg_len_padded, const int32_t* tok_off,
+                                    const int32_t* n_wins, int32_t n_clips, int32_t total_tok_padded,
+                                    const float* cnn_std_w, const uint16_t* cnn_wh, int32_t products, float* feat20,
+                                    void* stream);
 int nisqa_lstm_laststep(const float* feat20, const int32_t* tok_off, const int32_t* n_wins,
                         int32_t n_clips, const float* lstm_w, float* hfin_ws, float* seq_opt,
                         float* out, void* stream);

@@ -185,6 +185,8 @@ class _NisqaBase(nn.Module):
 
     def forward(self, x, n_wins):
         """Reference inner operator model(x[B,L,1,48,15], n_wins[B]) -> [B, heads] (NL:137-142, NL:260-268)."""
+        from .engine import check_segments
+        check_segments(x, n_wins, 1)                               # malformed arguments raise before the engine is built
         dev = x.device if x.is_cuda else None
         return self.engine(dev).forward_segments(x, n_wins)
 
@@ -272,8 +274,12 @@ class NISQA_DE(nn.Module):
         return self._engine
 
     def forward(self, x, n_wins):
-        raise NotImplementedError('NISQA_DE: the segment-tensor forward is not implemented on the HIP engine; use predict() '
-                                  '(predict_csv with csv_ref)')
+        """Reference inner operator model(x[B,L,2,48,15], n_wins[B,2]) -> [B, 1] (NL:399-424): channel 0 of x holds the degraded
+        clip's segments, channel 1 the reference clip's.  Malformed arguments raise ValueError before any GPU work."""
+        from .engine import check_segments
+        check_segments(x, n_wins, 2)
+        dev = x.device if x.is_cuda else None
+        return self.engine(dev).forward_segments(x, n_wins)
 
 
 # ---------------------------------------------------------------------------------------------
@@ -332,14 +338,25 @@ class SpeechQualityDataset(object):
     def __getitem__(self, index):
         """(x_spec_seg [max_length,1,n_mels,seg_length], y, (index, n_wins)) like NL:2162-2233.  The spectrogram is
         computed by the HIP front end; the overlapping-window gather (NL:2266-2280) is a host-side view for callers
-        that want the reference's item format -- the predict loop never materialises it."""
+        that want the reference's item format -- the predict loop never materialises it.
+        A double-ended dataset gives (x [max_length,2,n_mels,seg_length], y, (index, [n_wins_deg, n_wins_ref])) like NL:2170-2214:
+        channel 0 the degraded file's segments, channel 1 the reference file's, both from the HIP front end."""
         assert isinstance(index, int), 'index must be integer (no slice)'
-        if self.double_ended:
-            raise NotImplementedError('item access of a double-ended dataset is not implemented on the HIP path; predict_mos reads the '
-                                      '(degraded, reference) pairs itself')
         if getattr(self, '_engine_factory', None) is None:
             raise RuntimeError('SpeechQualityDataset item access needs bind_engine(...) (spectrograms are computed on the GPU)')
+        if self.double_ended:
+            (xd, y, (_, nd)), (xr, _, (_, nr)) = self._item(index), self.ref_view()._item(index)
+            if self.max_length is None and int(nd) != int(nr):     # (the reference's torch.cat of unpadded halves fails there too)
+                raise ValueError('a double-ended item without max_length needs equal segment counts, got {} and {}'.format(
+                    int(nd), int(nr)))
+            return torch.cat([xd, xr], 1), y, (index, np.array([int(nd), int(nr)]))
+        return self._item(index)
+
+    def _item(self, index):
+        """the single-ended item of this dataset's file column"""
         eng = self._engine_factory()
+        if hasattr(eng, 'base'):                                   # HipNisqaDE: mel, resampling and plans are its single-ended engine's
+            eng = eng.base
         y, sr = self.load_audio(index)
         plan = eng.audio_plan([len(y)], sr, names=[self.file_path(index)])
         pcm = eng.resample(torch.from_numpy(y).to(eng.device), [len(y)], sr)          # (ms_sr: lb.load resamples first, NL:2300-2304)

@@ -21,6 +21,11 @@
 #define SB_ZERO SB_ACT
 #define SB_LDS (SB_ACT + 256)
 
+// SEGX: the input is the reference's segment tensor x[B][L][1][48][15] (inner-operator mode, model.forward(x, n_wins),
+// NISQA_lib.py:137-142) instead of the spectrogram: mel_tm is then x and seg_hop its padded segment count L; frame_off and
+// clip_floor are not read and no floor is applied (x is already clamped).  The loads stay linear over the 720 contiguous
+// floats; only the LDS address changes (mel-major -> the frame-major patch conv1 reads).
+template <bool SEGX>
 __global__ __launch_bounds__(64, 2) void cnn_std_front_kernel(
     const float* __restrict__ mel_tm, const int32_t* __restrict__ frame_off,
     const int32_t* __restrict__ tok_off, const int32_t* __restrict__ n_wins,
@@ -33,7 +38,15 @@ __global__ __launch_bounds__(64, 2) void cnn_std_front_kernel(
     const int k = p - tok_off[b];
     if (k >= n_wins[b]) return;
 
-    {
+    if (SEGX) {
+        float* in_lds = (float*)(smem + SF_IN);
+        const float* src = mel_tm + ((size_t)b * seg_hop + k) * 720;
+        for (int i = lane; i < 720; i += 64) {
+            const int m = i / 15;
+            in_lds[(i - 15 * m) * 48 + m] = src[i];
+        }
+        ((float*)(smem + SF_ZERO))[lane] = 0.f;
+    } else {
         float* in_lds = (float*)(smem + SF_IN);
         const float* src = mel_tm + (size_t)(frame_off[b] + k * seg_hop) * 48;
         const float fl = clip_floor[b];
@@ -285,8 +298,21 @@ extern "C" int nisqa_cnn_standard(const float* mel_tm, const int32_t* frame_off,
                                   float* p3_ws, float* feat20, void* stream) {
     if (n_clips <= 0 || total_tok_padded <= 0 || (total_tok_padded & 31) || seg_hop <= 0) return NISQA_ERR_ARG;
     NQ_LAUNCH_BEGIN();
-    hipLaunchKernelGGL(cnn_std_front_kernel, dim3(total_tok_padded), dim3(64), SF_LDS, (hipStream_t)stream, mel_tm,
+    hipLaunchKernelGGL(cnn_std_front_kernel<false>, dim3(total_tok_padded), dim3(64), SF_LDS, (hipStream_t)stream, mel_tm,
                        frame_off, tok_off, n_wins, clip_floor, n_clips, seg_hop, cnn_std_w, p3_ws);
+    hipLaunchKernelGGL(cnn_std_back_kernel, dim3(total_tok_padded / 4), dim3(64), SB_LDS, (hipStream_t)stream,
+                       (const float*)p3_ws, tok_off, n_wins, n_clips, cnn_std_w, feat20);
+    return NQ_LAUNCH_STATUS();
+}
+
+// Segment-tensor input (nisqa_hip.h): the front kernel's SEGX form, then the same back kernel
+extern "C" int nisqa_cnn_standard_segments(const float* x, int32_t seg_len_padded, const int32_t* tok_off,
+                                           const int32_t* n_wins, int32_t n_clips, int32_t total_tok_padded,
+                                           const float* cnn_std_w, float* p3_ws, float* feat20, void* stream) {
+    if (!x || seg_len_padded <= 0 || n_clips <= 0 || total_tok_padded <= 0 || (total_tok_padded & 31)) return NISQA_ERR_ARG;
+    NQ_LAUNCH_BEGIN();
+    hipLaunchKernelGGL(cnn_std_front_kernel<true>, dim3(total_tok_padded), dim3(64), SF_LDS, (hipStream_t)stream, x,
+                       (const int32_t*)nullptr, tok_off, n_wins, (const float*)nullptr, n_clips, seg_len_padded, cnn_std_w, p3_ws);
     hipLaunchKernelGGL(cnn_std_back_kernel, dim3(total_tok_padded / 4), dim3(64), SB_LDS, (hipStream_t)stream,
                        (const float*)p3_ws, tok_off, n_wins, n_clips, cnn_std_w, feat20);
     return NQ_LAUNCH_STATUS();

@@ -126,7 +126,11 @@ NQ_DEV float ss_epi(float v, float c, float t) { return (FMT == NQ_FMT_BF16X3 ||
 // FMT (conv_bf16.hpp): NQ_FMT_BF16X3 -- bf16 hi + lo, three products (the input keeps a third term) -- or the f16 formats: every
 // tensor as f16 hi + lo of y * 2^e, e from the measured maximum of the layer's input and the layer's weight norm (cnn_bf16.hip's
 // scheme: |y| <= m_in * G + T), three or four products; wb is then the CNNH_ blob (weights.pack_adapt_cnn_f16)
-template <int FMT>
+// SEGX: the input is the reference's segment tensor x[B][L][1][48][15] (inner-operator mode, model.forward(x, n_wins),
+// NISQA_lib.py:137-142) instead of the spectrogram: mel_tm is then x and seg_hop its padded segment count L; frame_off and
+// clip_floor are not read and no floor is applied (x is already clamped).  Only the staging differs -- the same 12 linear loads,
+// other plane addresses -- so the same window gives the same bits in either form.
+template <int FMT, bool SEGX = false>
 NQ_DEV void cnn_std_split_body(
     const float* __restrict__ mel_tm, const int32_t* __restrict__ frame_off,
     const int32_t* __restrict__ tok_off, const int32_t* __restrict__ n_wins,
@@ -162,8 +166,8 @@ NQ_DEV void cnn_std_split_body(
     //      immediates (element i0 = lane + 64 q = (frame, mel) = divmod(i0, 48); q = 3 t + u: frame q + t + (lane + 16 u) / 48)
     const unsigned R = SS_BASE + (unsigned)wave * SS_WAVE; // this wave's region (the kernel has no static LDS: addresses start at 0)
     {
-        const float fl = clip_floor[b];
-        const float* src = mel_tm + (size_t)(frame_off[b] + k * seg_hop) * 48;
+        const float fl = SEGX ? -3.0e38f : clip_floor[b];
+        const float* src = SEGX ? mel_tm + ((size_t)b * seg_hop + k) * 720 : mel_tm + (size_t)(frame_off[b] + k * seg_hop) * 48;
         float vraw[12];
 #pragma unroll
         for (int q = 0; q < 12; ++q) vraw[q] = (valid && (q < 11 || lane < 16)) ? src[lane + 64 * q] : 0.f;
@@ -183,15 +187,17 @@ NQ_DEV void cnn_std_split_body(
         if (F16) {                                          // the window's own largest magnitude fixes its scale
             float mr = 0.f;
 #pragma unroll
-            for (int q = 0; q < 12; ++q) mr = fmaxf(mr, valid ? __builtin_fabsf(fmaxf(vraw[q], fl)) : 0.f);
+            for (int q = 0; q < 12; ++q) mr = fmaxf(mr, valid ? __builtin_fabsf(SEGX ? vraw[q] : fmaxf(vraw[q], fl)) : 0.f);
             m_in = wave_max_nonneg(mr);
             e_in = f16_scale_exp(m_in);
             s0 = pow2_f32(e_in);
         }
 #pragma unroll
         for (int q = 0; q < 12; ++q) {
-            const float v = valid ? fmaxf(vraw[q], fl) : 0.f;
-            const unsigned a = ob[q % 3] + (q + q / 3) * 100;
+            const float v = valid ? (SEGX ? vraw[q] : fmaxf(vraw[q], fl)) : 0.f;
+            // SEGX: element i0 = lane + 64 q of the [48][15] image is (mel, frame) = divmod(i0, 15)
+            const int i0 = lane + 64 * q, sm = i0 / 15, sj = i0 - 15 * sm;
+            const unsigned a = SEGX ? pb + ((sj + 1) * 50 + sm + 1) * 2 : ob[q % 3] + (q + q / 3) * 100;
             if (F16) {
                 if (q < 11 || lane < 16) lds_store_one_fmt<FMT>(a, SS_PPLANE, v * s0, dummy_mx);
             } else {                                        // lds_store_terms<3> with the stores behind the split
@@ -612,20 +618,38 @@ __global__ __launch_bounds__(256, 2) void cnn_std_f16_kernel(
     cnn_std_split_body<P4 ? NQ_FMT_F16X4 : NQ_FMT_F16X3>(mel_tm, frame_off, tok_off, n_wins, clip_floor, n_clips, seg_hop, cw, wb, feat20);
 }
 
+// the segment-fed forms (SEGX) of the four kernels above
+#define SS_PARAMS                                                                                                      \
+    const float* __restrict__ mel_tm, const int32_t* __restrict__ frame_off, const int32_t* __restrict__ tok_off,     \
+    const int32_t* __restrict__ n_wins, const float* __restrict__ clip_floor, int n_clips, int seg_hop,               \
+    const float* __restrict__ cw, const unsigned short* __restrict__ wb, float* __restrict__ feat20
+#define SS_ARGS mel_tm, frame_off, tok_off, n_wins, clip_floor, n_clips, seg_hop, cw, wb, feat20
+__global__ __launch_bounds__(256, 2) void cnn_std_seg_bf16_kernel(SS_PARAMS) { cnn_std_split_body<NQ_FMT_BF16X3, true>(SS_ARGS); }
+__global__ __launch_bounds__(256, 1) void cnn_std_seg_bf16x6_kernel(SS_PARAMS) { cnn_std_split_body<NQ_FMT_BF16X6, true>(SS_ARGS); }
+template <bool P4>
+__global__ __launch_bounds__(256, 2) void cnn_std_seg_f16_kernel(SS_PARAMS) {
+    cnn_std_split_body<P4 ? NQ_FMT_F16X4 : NQ_FMT_F16X3, true>(SS_ARGS);
+}
+
 typedef void (*ss_kernel_t)(const float*, const int32_t*, const int32_t*, const int32_t*, const float*, int, int, const float*,
                             const unsigned short*, float*);
 // fmt: 0 bf16x3, 1 f16x3, 2 f16x4, 3 bf16x6; 70.6 / 94.6 KB of dynamic LDS: above the 64 KB default, opted in once per kernel and device
-static int ss_launch(int fmt, const float* mel_tm, const int32_t* frame_off, const int32_t* tok_off, const int32_t* n_wins,
+// segx: mel_tm is the segment tensor x and seg_hop its padded segment count (frame_off, clip_floor unused)
+static int ss_launch(int fmt, bool segx, const float* mel_tm, const int32_t* frame_off, const int32_t* tok_off, const int32_t* n_wins,
                      const float* clip_floor, int32_t n_clips, int32_t total_tok_padded, int32_t seg_hop, const float* cnn_std_w,
                      const uint16_t* cnn_wb, float* feat20, void* stream) {
-    if (n_clips <= 0 || total_tok_padded <= 0 || (total_tok_padded & 31) || seg_hop <= 0 || !cnn_wb || !feat20 || fmt < 0 || fmt > 3)
+    if (n_clips <= 0 || total_tok_padded <= 0 || (total_tok_padded & 31) || seg_hop <= 0 || !cnn_wb || !feat20 || fmt < 0 || fmt > 3 ||
+        (segx && !mel_tm))
         return NISQA_ERR_ARG;
-    static const ss_kernel_t kernels[4] = {cnn_std_bf16_kernel, cnn_std_f16_kernel<false>, cnn_std_f16_kernel<true>, cnn_std_bf16x6_kernel};
+    static const ss_kernel_t kernels[8] = {cnn_std_bf16_kernel, cnn_std_f16_kernel<false>, cnn_std_f16_kernel<true>, cnn_std_bf16x6_kernel,
+                                           cnn_std_seg_bf16_kernel, cnn_std_seg_f16_kernel<false>, cnn_std_seg_f16_kernel<true>,
+                                           cnn_std_seg_bf16x6_kernel};
+    const int which = fmt + (segx ? 4 : 0);
     const int lds = fmt == 3 ? SS_LDS_T(3) : SS_LDS_T(2);
     NQ_LAUNCH_BEGIN();
-    static std::atomic<bool> lds_ok[4][64];
-    if (nq_lds_opt_in((const void*)kernels[fmt], lds, lds_ok[fmt])) return 2;
-    hipLaunchKernelGGL(kernels[fmt], dim3(total_tok_padded / 4), dim3(256), lds, (hipStream_t)stream, mel_tm, frame_off, tok_off, n_wins,
+    static std::atomic<bool> lds_ok[8][64];
+    if (nq_lds_opt_in((const void*)kernels[which], lds, lds_ok[which])) return 2;
+    hipLaunchKernelGGL(kernels[which], dim3(total_tok_padded / 4), dim3(256), lds, (hipStream_t)stream, mel_tm, frame_off, tok_off, n_wins,
                        clip_floor, n_clips, seg_hop, cnn_std_w, cnn_wb, feat20);
     return NQ_LAUNCH_STATUS();
 }
@@ -634,7 +658,7 @@ extern "C" int nisqa_cnn_standard_bf16(const float* mel_tm, const int32_t* frame
                                        const int32_t* n_wins, const float* clip_floor, int32_t n_clips,
                                        int32_t total_tok_padded, int32_t seg_hop, const float* cnn_std_w,
                                        const uint16_t* cnn_wb, float* feat20, void* stream) {
-    return ss_launch(0, mel_tm, frame_off, tok_off, n_wins, clip_floor, n_clips, total_tok_padded, seg_hop, cnn_std_w, cnn_wb, feat20, stream);
+    return ss_launch(0, false, mel_tm, frame_off, tok_off, n_wins, clip_floor, n_clips, total_tok_padded, seg_hop, cnn_std_w, cnn_wb, feat20, stream);
 }
 
 // the f16 formats (cnn_wh: nisqa_amd.weights.pack_adapt_cnn_f16 of the StandardCNN's convolutions; products = 3 or 4)
@@ -643,7 +667,7 @@ extern "C" int nisqa_cnn_standard_f16(const float* mel_tm, const int32_t* frame_
                                       int32_t total_tok_padded, int32_t seg_hop, const float* cnn_std_w,
                                       const uint16_t* cnn_wh, int32_t products, float* feat20, void* stream) {
     if (products != 3 && products != 4) return NISQA_ERR_ARG;
-    return ss_launch(products - 2, mel_tm, frame_off, tok_off, n_wins, clip_floor, n_clips, total_tok_padded, seg_hop, cnn_std_w, cnn_wh, feat20,
+    return ss_launch(products - 2, false, mel_tm, frame_off, tok_off, n_wins, clip_floor, n_clips, total_tok_padded, seg_hop, cnn_std_w, cnn_wh, feat20,
                      stream);
 }
 
@@ -652,5 +676,25 @@ extern "C" int nisqa_cnn_standard_bf16x6(const float* mel_tm, const int32_t* fra
                                          const int32_t* n_wins, const float* clip_floor, int32_t n_clips,
                                          int32_t total_tok_padded, int32_t seg_hop, const float* cnn_std_w,
                                          const uint16_t* cnn_wx, float* feat20, void* stream) {
-    return ss_launch(3, mel_tm, frame_off, tok_off, n_wins, clip_floor, n_clips, total_tok_padded, seg_hop, cnn_std_w, cnn_wx, feat20, stream);
+    return ss_launch(3, false, mel_tm, frame_off, tok_off, n_wins, clip_floor, n_clips, total_tok_padded, seg_hop, cnn_std_w, cnn_wx, feat20, stream);
+}
+
+// ---- segment-tensor input (nisqa_hip.h): x[B][seg_len_padded][1][48][15] in place of the spectrogram ----------------------------------
+extern "C" int nisqa_cnn_standard_segments_bf16(const float* x, int32_t seg_len_padded, const int32_t* tok_off,
+                                                const int32_t* n_wins, int32_t n_clips, int32_t total_tok_padded,
+                                                const float* cnn_std_w, const uint16_t* cnn_wb, float* feat20, void* stream) {
+    return ss_launch(0, true, x, nullptr, tok_off, n_wins, nullptr, n_clips, total_tok_padded, seg_len_padded, cnn_std_w, cnn_wb, feat20, stream);
+}
+extern "C" int nisqa_cnn_standard_segments_f16(const float* x, int32_t seg_len_padded, const int32_t* tok_off,
+                                               const int32_t* n_wins, int32_t n_clips, int32_t total_tok_padded,
+                                               const float* cnn_std_w, const uint16_t* cnn_wh, int32_t products, float* feat20,
+                                               void* stream) {
+    if (products != 3 && products != 4) return NISQA_ERR_ARG;
+    return ss_launch(products - 2, true, x, nullptr, tok_off, n_wins, nullptr, n_clips, total_tok_padded, seg_len_padded, cnn_std_w, cnn_wh,
+                     feat20, stream);
+}
+extern "C" int nisqa_cnn_standard_segments_bf16x6(const float* x, int32_t seg_len_padded, const int32_t* tok_off,
+                                                  const int32_t* n_wins, int32_t n_clips, int32_t total_tok_padded,
+                                                  const float* cnn_std_w, const uint16_t* cnn_wx, float* feat20, void* stream) {
+    return ss_launch(3, true, x, nullptr, tok_off, n_wins, nullptr, n_clips, total_tok_padded, seg_len_padded, cnn_std_w, cnn_wx, feat20, stream);
 }

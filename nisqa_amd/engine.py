@@ -37,20 +37,21 @@ def _pack_bf16(terms):
 
 # What a precision IS, stated once: nisqa_model_dev.cnn_mode; the operand format of self-attention and pooling (a key of TD: the f16 CNN
 # modes pair with the three-term kernels); how cnn_wb is packed (None: no 16-bit blob); and per CNN stage -- frame-fed AdaptCNN,
-# segment-fed AdaptCNN, StandardCNN -- the entry point and what it takes between cnn_w and the stream (`terms`: the digit the precision's
-# name ends in; the f16 entries serve both counts).
-Precision = collections.namedtuple('Precision', 'cnn_mode td pack_cnn adapt segments standard')
+# segment-fed AdaptCNN, StandardCNN, segment-fed StandardCNN -- the entry point and what it takes between cnn_w and the stream (`terms`:
+# the digit the precision's name ends in; the f16 entries serve both counts).
+Precision = collections.namedtuple('Precision', 'cnn_mode td pack_cnn adapt segments standard standard_segments')
 _WB, _F16 = 'cnn_wb feat', 'cnn_wb terms feat'
 PRECISION = {
-    'f32': Precision(0, 'f32', None, ('nisqa_cnn_adapt', 'p3 feat'), ('nisqa_cnn_adapt_segments', 'p3 feat'), ('nisqa_cnn_standard', 'p3 feat')),
+    'f32': Precision(0, 'f32', None, ('nisqa_cnn_adapt', 'p3 feat'), ('nisqa_cnn_adapt_segments', 'p3 feat'), ('nisqa_cnn_standard', 'p3 feat'),
+                     ('nisqa_cnn_standard_segments', 'p3 feat')),
     'bf16x3': Precision(1, 'bf16x3', _pack_bf16(2), ('nisqa_cnn_adapt_bf16', 'cnn_wb p3 feat'), ('nisqa_cnn_adapt_segments_bf16', _WB),
-                        ('nisqa_cnn_standard_bf16', _WB)),
+                        ('nisqa_cnn_standard_bf16', _WB), ('nisqa_cnn_standard_segments_bf16', _WB)),
     'bf16x6': Precision(2, 'bf16x6', _pack_bf16(3), ('nisqa_cnn_adapt_bf16x6', _WB), ('nisqa_cnn_adapt_segments_bf16x6', _WB),
-                        ('nisqa_cnn_standard_bf16x6', _WB)),
+                        ('nisqa_cnn_standard_bf16x6', _WB), ('nisqa_cnn_standard_segments_bf16x6', _WB)),
     'f16x3': Precision(3, 'bf16x6', _w.pack_adapt_cnn_f16, ('nisqa_cnn_adapt_f16', _F16), ('nisqa_cnn_adapt_segments_f16', _F16),
-                       ('nisqa_cnn_standard_f16', _F16)),
+                       ('nisqa_cnn_standard_f16', _F16), ('nisqa_cnn_standard_segments_f16', _F16)),
     'f16x4': Precision(4, 'bf16x6', _w.pack_adapt_cnn_f16, ('nisqa_cnn_adapt_f16', _F16), ('nisqa_cnn_adapt_segments_f16', _F16),
-                       ('nisqa_cnn_standard_f16', _F16)),
+                       ('nisqa_cnn_standard_f16', _F16), ('nisqa_cnn_standard_segments_f16', _F16)),
 }
 PRECISIONS = tuple(PRECISION)
 CNN_MODE = {p: row.cnn_mode for p, row in PRECISION.items()}
@@ -64,11 +65,12 @@ TD = {
 }
 # the name a failing entry is reported under, where that is not its own
 WHAT = {'nisqa_cnn_adapt_segments_bf16': 'nisqa_cnn_adapt_segments_bf16x3', 'nisqa_cnn_standard_bf16': 'nisqa_cnn_standard_bf16x3',
+        'nisqa_cnn_standard_segments_bf16': 'nisqa_cnn_standard_segments_bf16x3',
         'nisqa_td_selfatt_bf16': 'nisqa_td_selfatt_bf16x3', 'nisqa_pool_att_bf16': 'nisqa_pool_att_bf16x3'}
 
 
 def cnn_call(precision, stage, head, cnn_wb, p3, feat, stream):
-    """stage: 'adapt' | 'segments' | 'standard'; head: the entry's arguments up to and including cnn_w
+    """stage: 'adapt' | 'segments' | 'standard' | 'standard_segments'; head: the entry's arguments up to and including cnn_w
     -> (entry name, the name _lib.check reports, the entry's whole argument list)"""
     name, tail = getattr(PRECISION[precision], stage)
     vals = {'cnn_wb': cnn_wb, 'p3': p3, 'feat': feat, 'terms': int(precision[-1])}
@@ -163,6 +165,29 @@ def _ptr(t):
 
 def _or(value, default):
     return default if value is None else value
+
+
+def check_segments(x, n_wins, channels):
+    """The arguments of the reference's inner operator model(x, n_wins): x [B, L, channels, 48, 15] (1 channel: NL:137-142; 2, degraded
+    and reference: NL:399-404), n_wins one count in [1, L] per clip and channel -> the counts as int64 [B] (channels == 1) or
+    [B, channels].  Raises ValueError; no device is touched here beyond reading n_wins."""
+    if not torch.is_tensor(x) or x.dim() != 5 or tuple(x.shape[2:]) != (channels, 48, SEG_LEN):
+        raise ValueError('expected x of shape [B, L, {}, 48, 15], got {}'.format(
+            channels, tuple(x.shape) if torch.is_tensor(x) else type(x).__name__))
+    n = np.asarray(n_wins.detach().cpu().numpy() if torch.is_tensor(n_wins) else n_wins)
+    B, L = x.shape[0], x.shape[1]
+    if channels == 1:
+        if n.size != B or B == 0:
+            raise ValueError('n_wins must hold one count in [1, L] per clip')
+        n = n.reshape(-1)
+    elif n.shape != (B, channels) or B == 0:
+        raise ValueError('n_wins must be of shape [B, {}], got {}'.format(channels, tuple(n.shape)))
+    if not np.issubdtype(n.dtype, np.integer) and not (np.isfinite(n).all() and (n == np.floor(n)).all()):
+        raise ValueError('n_wins must hold whole numbers')
+    n = n.astype(np.int64)
+    if (n < 1).any() or (n > L).any():
+        raise ValueError('n_wins must hold one count in [1, L] per clip' + ('' if channels == 1 else ' and channel'))
+    return n
 
 
 # pool option of a StandardCNN + BiLSTM model -> nisqa_model_dev.arch / nisqa_lstm_pool's pool_mode
@@ -410,22 +435,30 @@ class HipNisqa(object):
         feat = torch.zeros((plan.total_tok, 384), dtype=torch.float32, device=self.device)
         return feat, self._cnn_stage('adapt', self._mel_head(mel_tm, clip_floor, plan), plan, feat, 18)
 
+    def _segments_head(self, x, plan):
+        d = plan.to(self.device)
+        return (_ptr(x), x.shape[1], _ptr(d['tok_off']), _ptr(d['n_wins']), plan.n_clips, plan.total_tok)
+
+    def cnn_segments(self, x, plan):
+        """AdaptCNN on the segment tensor x [B, L, 1, 48, 15] (device, float32, contiguous) -> feat [NP, 384]"""
+        feat = torch.empty((plan.total_tok, 384), dtype=torch.float32, device=self.device)
+        self._cnn_stage('segments', self._segments_head(x, plan), plan, feat, 18)
+        return feat
+
+    def cnn_std_segments(self, x, plan):
+        """StandardCNN + fc_out on the segment tensor x [B, L, 1, 48, 15] (device, float32, contiguous) -> feat20 [NP, 20]"""
+        feat = torch.zeros((plan.total_tok, 20), dtype=torch.float32, device=self.device)
+        self._cnn_stage('standard_segments', self._segments_head(x, plan), plan, feat, 12)
+        return feat
+
     def forward_segments(self, x, n_wins):
         """Reference inner operator model(x[B,L,1,48,15], n_wins[B]) -> [B, heads] (NL:137-142, NL:260-268)."""
-        if self.arch != 0:
-            raise NotImplementedError('segment-tensor forward is implemented for the CNN-SA-AP architecture only')
-        if x.dim() != 5 or tuple(x.shape[2:]) != (1, 48, SEG_LEN):
-            raise ValueError('expected x of shape [B, L, 1, 48, 15], got {}'.format(tuple(x.shape)))
+        n = check_segments(x, n_wins, 1)
         x = x.to(self.device, dtype=torch.float32).contiguous()
-        n = np.asarray(n_wins.detach().cpu().numpy() if torch.is_tensor(n_wins) else n_wins, dtype=np.int64).reshape(-1)
-        B, L = x.shape[0], x.shape[1]
-        if len(n) != B or (n < 1).any() or (n > L).any():
-            raise ValueError('n_wins must hold one count in [1, L] per clip')
         plan = BatchPlan.from_n_wins(n)
-        d = plan.to(self.device)
-        feat = torch.empty((plan.total_tok, 384), dtype=torch.float32, device=self.device)
-        self._cnn_stage('segments', (_ptr(x), L, _ptr(d['tok_off']), _ptr(d['n_wins']), B, plan.total_tok), plan, feat, 18)
-        return self.td_pool(feat, plan)
+        if self.arch >= 1:
+            return self.lstm(self.cnn_std_segments(x, plan), plan)[0]
+        return self.td_pool(self.cnn_segments(x, plan), plan)
 
     # -- nisqa_tts.tar stages ------------------------------------------------------------------------
     def cnn_std(self, mel_tm, clip_floor, plan):
@@ -605,6 +638,17 @@ class HipNisqaDE(object):
     def features(self, pcm, plan, sr):
         mel, floor = self.base.mel(pcm, plan, sr, clamp=False)
         return self.base.cnn(mel, floor, plan)[0]
+
+    def forward_segments(self, x, n_wins):
+        """Reference inner operator model(x[B,L,2,48,15], n_wins[B,2]) -> [B, 1] (NL:399-424): channel 0 holds the degraded clip's
+        segments, channel 1 the reference clip's (torch.chunk(x, 2, dim=2), NL:399-404).  One plan of 2B clips, degraded first;
+        each channel is copied into a contiguous [2B, L, 1, 48, 15] tensor for the segment-fed AdaptCNN (not the throughput path:
+        predict never materialises segments)."""
+        n = check_segments(x, n_wins, 2)
+        x = x.to(self.device, dtype=torch.float32)
+        x2 = torch.cat([x[:, :, 0:1], x[:, :, 1:2]], 0).contiguous()
+        plan = BatchPlan.from_n_wins(np.concatenate([n[:, 0], n[:, 1]]))
+        return self.forward_features(self.base.cnn_segments(x2, plan), plan)
 
     def forward_pcm(self, pcm, plan, sr, want_idx=False):
         """pcm: device tensor of the plan's 2B clips back to back (degraded, then reference; float32 or int16 PCM) -> [B, 1]"""
