@@ -340,6 +340,35 @@ int nisqa_predict_batch_pcm16(const int16_t* pcm, const int64_t* clip_off, const
 /* int16 PCM -> float32 (x / 32768), the soundfile scaling lb.load applies (NISQA_lib.py:2304). */
 int nisqa_pcm16_to_f32(const int16_t* pcm16, float* pcm, int64_t n, void* stream);
 
+/* lb.load(path, sr=None, mono=...) for WAV data chunks already on the device (NISQA_lib.py:2299-2304: soundfile's float32 read of every
+ * WAV encoding, then ms_channel or librosa.to_mono): raw holds the data chunks as the files have them (what the native ingest copies
+ * verbatim), clips [dev] says where each one lies and how to read it, out receives float32 mono samples, clip i at out + dst_off.
+ * PCM in 1 (unsigned, offset 128), 2, 3 and 4-byte containers scales by 1 / 2^(8 * container - 1) (12- and 20-bit samples are
+ * left-justified: the container is read, as libsndfile reads it); A-law / mu-law expand to the G.711 16-bit value, then 1 / 32768;
+ * float32 passes through bit for bit, float64 is rounded to nearest even (overflow to +-inf); big-endian samples are byte-swapped
+ * first.  channel >= 0 selects that channel; -1 takes the float32 mean of 2..32 channels in numpy's summation order (in sequence below
+ * eight channels, through eight accumulators from eight on, the sum added to +0.0) and divides by the channel count.  Denormals are kept.
+ * Limits: raw 16-byte aligned, channels * container <= 1024, every src_off a multiple of 16 with src_off + n_frames * channels *
+ * container <= raw_bytes, n_frames <= max_frames (the longest clip: the grid is n_clips x ceil(max_frames / 1024) workgroups).  The
+ * 16-byte spans that hold a clip are loaded whole where they end inside raw_bytes and byte by byte where they do not: nothing past
+ * raw_bytes is read.  A table entry outside these limits is skipped on the device (its samples are not written). */
+#define NISQA_WAVENC_PCM 1
+#define NISQA_WAVENC_FLOAT 3
+#define NISQA_WAVENC_ALAW 6
+#define NISQA_WAVENC_MULAW 7
+#define NISQA_WAVENC_BIG_ENDIAN 0x10000   /* the values of nisqa_ingest.h's NISQA_WAV_TAG_*: a probed tag is an encoding */
+typedef struct nisqa_wav_clip {      /* 40 bytes, device array */
+    int64_t src_off;    /* byte offset of the clip's data chunk in `raw`, multiple of 16 */
+    int64_t dst_off;    /* sample offset of the clip in `out` */
+    int64_t n_frames;
+    int32_t channels;
+    int32_t container;  /* bytes per sample = block_align / channels: 1, 2, 3, 4, 8 */
+    int32_t encoding;   /* NISQA_WAVENC_PCM | _FLOAT | _ALAW | _MULAW, possibly | NISQA_WAVENC_BIG_ENDIAN */
+    int32_t channel;    /* >= 0: ms_channel (NISQA_lib.py:2300-2302); -1: librosa.to_mono */
+} nisqa_wav_clip;
+int nisqa_wav_decode(const void* raw, int64_t raw_bytes, const nisqa_wav_clip* clips, int32_t n_clips,
+                     int64_t max_frames, float* out, void* stream);
+
 /* lb.load(path, sr=ms_sr) for clips already on the device (NISQA_lib.py:2300, 2304 -> librosa.resample(y, sr_file, ms_sr,
  * res_type='kaiser_best') -> resampy): clip b = pcm[in_off[b] .. in_off[b + 1]) (float32 samples, or int16 PCM scaled by 1 / 32768
  * when is_pcm16) at the file's rate -> out[out_off[b] .. out_off[b + 1]) at ratio = ms_sr / sr_file.  out_off[b + 1] - out_off[b] =

@@ -581,7 +581,11 @@ def _predict(model, ds, bs, dev, num_workers, on_rows=None):
         # batch k + 1 is queued a whole batch time before the link needs it, not 0.8 ms before (kernels 3 ms + enqueue 0.5 ms
         # against a 4.3 ms copy: with one batch in flight any jitter left the link idle, 89 % of its rate over 98 304 rows)
         ing = _ingest.Ingest(ds, batches, pin=on_gpu, num_workers=num_workers, depth=int(os.environ.get('NISQA_LOOP_DEPTH', '3')),
-                             device=eng.device if on_gpu else None)
+                             device=eng.device if on_gpu else None,
+                             # files that are not mono PCM16 travel as raw data chunks and are decoded by nisqa_wav_decode
+                             # (ingest.copy_group on the copy stream, ingest.decode_group on a kernel stream: the two halves of
+                             # ingest.group_pcm); NISQA_HOST_DECODE=1: the staging thread decodes them, as before
+                             device_decode=on_gpu and _ingest.device_decode_default())
         copy_stream, streams = _loop_streams(eng.device) if on_gpu else (None, [None, None])
         inflight = []                                                   # (ids, host rows, event behind them)
         keep_inflight = max(1, int(os.environ.get('NISQA_LOOP_INFLIGHT', '2')))
@@ -618,12 +622,10 @@ def _predict(model, ds, bs, dev, num_workers, on_rows=None):
                     for g in staged.groups:                          # files of one rate share the mel tables
                         plan = eng.audio_plan(g.lengths, g.sr, names=g.names)
                         tables = plan.to(eng.device)
-                        host = raw[g.offset:g.offset + g.nbytes].view(torch.int16 if g.is_i16 else torch.float32)
-                        # PCM16 stays int16: 2 bytes/sample over PCIe.  (Round 5 sent the halves of a batch through TWO copy-only
+                        # PCM16 stays int16, 2 bytes/sample over PCIe; a raw group crosses as its data chunks.  (Round 5 sent the halves of a batch through TWO copy-only
                         # streams so that one engine's set-up would be covered by the other's transfer: 48.6 / 47.7 k clips/s against
                         # 50.4 / 52.3 k with one stream on the same box -- two SDMA queues share the link worse than one fills it.)
-                        pcm = host.to(eng.device, non_blocking=True)
-                        sent.append((g, plan, tables, pcm))
+                        sent.append((g, plan, tables, _ingest.copy_group(raw, g, eng.device)))
                     if on_gpu:
                         ev = torch.cuda.Event(enable_timing=time_copies)
                         ev.record(copy_stream)
@@ -634,10 +636,11 @@ def _predict(model, ds, bs, dev, num_workers, on_rows=None):
             if on_gpu:
                 st.wait_event(ev)
             with (torch.cuda.stream(st) if on_gpu else _nullcontext()):
-                for g, plan, tables, pcm in sent:
+                for g, plan, tables, sent_pcm in sent:
+                    pcm = _ingest.decode_group(sent_pcm, g, eng)     # (a raw group: every WAV encoding -> float32, on this stream)
                     out = eng.forward_audio(pcm, g.lengths, g.sr, plan)      # (resampled to ms_sr first when the checkpoint sets it)
                     if on_gpu:
-                        pcm.record_stream(st)                        # allocated on the copy stream, consumed on this one
+                        sent_pcm.record_stream(st)                   # allocated on the copy stream, consumed on this one
                         tables['_buf'].record_stream(st)
                         rows = torch.empty(out.shape, dtype=out.dtype, pin_memory=True)
                         rows.copy_(out, non_blocking=True)           # [B, heads] floats, behind the kernels

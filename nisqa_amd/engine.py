@@ -391,6 +391,36 @@ class HipNisqa(object):
         _lib.check(rc, 'nisqa_predict_batch')
         return out
 
+    def decode(self, raw_dev, clips, n_samples, out=None):
+        """raw_dev: uint8 device tensor, WAV data chunks as the files hold them; clips: their nisqa_wav_clip table (numpy structured
+        array of lib.WavClip's layout, src_off into raw_dev, dst_off into the result) -> float32 device tensor [n_samples], what
+        lb.load(path, sr=None) returns for each clip (nisqa_wav_decode).  The table is checked here, on the host: the kernel skips
+        an entry it cannot take, it does not report it."""
+        t = np.ascontiguousarray(clips, dtype=np.dtype(_lib.WavClip)).reshape(-1)
+        n_samples = int(n_samples)
+        assert raw_dev.dtype == torch.uint8 and raw_dev.is_cuda and raw_dev.is_contiguous()
+        if out is None:
+            out = torch.empty(n_samples, dtype=torch.float32, device=self.device)
+        assert out.dtype == torch.float32 and out.numel() >= n_samples and out.is_contiguous()
+        if len(t) == 0 or int(t['n_frames'].max()) <= 0:
+            return out
+        ch, cont, enc = t['channels'].astype(np.int64), t['container'].astype(np.int64), t['encoding'] & ~_lib.WAVENC_BIG_ENDIAN
+        enc_ok = ((enc == _lib.WAVENC_PCM) & (cont >= 1) & (cont <= 4)) | ((enc == _lib.WAVENC_FLOAT) & ((cont == 4) | (cont == 8))) \
+            | (((enc == _lib.WAVENC_ALAW) | (enc == _lib.WAVENC_MULAW)) & (cont == 1))
+        ok = enc_ok & (ch >= 1) & (ch * cont <= _lib.WAV_DECODE_MAX_BLOCK) & (t['channel'] >= -1) & (t['channel'] < ch) \
+            & ((t['channel'] >= 0) | (ch <= _lib.WAV_DECODE_MAX_MEAN)) & (t['n_frames'] >= 0) \
+            & (t['src_off'] >= 0) & (t['src_off'] % 16 == 0) & (t['src_off'] + t['n_frames'] * ch * cont <= raw_dev.numel()) \
+            & (t['dst_off'] >= 0) & (t['dst_off'] + t['n_frames'] <= n_samples)
+        if not ok.all():
+            raise ValueError('nisqa_wav_decode: table entry %d is outside what the kernel takes: %r' % (int(np.flatnonzero(~ok)[0]), t[~ok][0]))
+        host = torch.empty(t.nbytes, dtype=torch.uint8, pin_memory=True)         # page-locked + non-blocking, like the tables of resample
+        host.numpy()[...] = t.view(np.uint8)
+        dev = host.to(self.device, non_blocking=True)
+        rc = self.lib.nisqa_wav_decode(_ptr(raw_dev), raw_dev.numel(), _ptr(dev), len(t), max(1, int(t['n_frames'].max())),
+                                       _ptr(out), self._stream())
+        _lib.check(rc, 'nisqa_wav_decode')
+        return out
+
     def pcm16_to_f32(self, pcm16):
         out = torch.empty(pcm16.numel(), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.nisqa_pcm16_to_f32(_ptr(pcm16), _ptr(out), pcm16.numel(), self._stream()), 'nisqa_pcm16_to_f32')

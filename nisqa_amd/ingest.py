@@ -9,9 +9,13 @@ alone, and the same pool then ``pread``-s every data chunk straight into its sli
 buffer (page cache -> pinned memory).  Three such buffers rotate: one being filled by the producer thread, one in flight over PCIe, one spare;
 a slot is recycled only after the HIP event recorded behind its H2D copy has completed.
 
-Files that are not mono PCM16 (stereo, 8/24/32-bit, float) are decoded by ``wavio.read_wav`` with the reference's
-``lb.load`` semantics and staged as float32 through the same buffers.  FLAC files (lb.load reads them through the same
-soundfile call) are decoded by the native reader threads: mono 16-bit streams straight into their int16 slot, others via ``wavio``.
+Files that are not mono PCM16 (stereo, 8/24/32-bit, float, G.711, RIFX) take one of two roads.  With ``device_decode`` (what the
+predict and the training loop ask for) their data chunks are copied VERBATIM like the mono PCM16 ones, the rate group travels as raw
+bytes with a table of ``nisqa_wav_clip`` records, and ``nisqa_wav_decode`` turns it into float32 mono samples on the GPU
+(``group_pcm``): no Python runs per sample.  Without it (the default of ``Ingest``, and ``NISQA_HOST_DECODE=1`` in the loops) they
+are decoded by ``wavio.read_wav`` with the reference's ``lb.load`` semantics and staged as float32 through the same buffers.  FLAC
+files (lb.load reads them through the same soundfile call) are decoded by the native reader threads: mono 16-bit streams straight
+into their int16 slot, others via ``wavio``.
 """
 import ctypes
 import os
@@ -26,6 +30,8 @@ from . import lib as _lib
 from . import wavio
 
 _ALIGN = 64
+_RAW_ALIGN = 16                                    # nisqa_wav_decode: every data chunk of a raw group starts on a 16-byte boundary
+WAV_CLIP = np.dtype(_lib.WavClip)                  # one row of a raw group's table (nisqa_wav_clip)
 _noted = set()
 
 
@@ -176,12 +182,17 @@ def _give_ring(ring):
 
 
 class Group(object):
-    """Clips of one sample rate inside a staged batch."""
-    __slots__ = ('ids', 'lengths', 'sr', 'offset', 'nbytes', 'is_i16', 'names')
+    """Clips of one sample rate inside a staged batch.  ``kind``: 'i16' (mono PCM16 back to back), 'f32' (host-decoded float32 back to
+    back) or 'raw' (data chunks as the files hold them, each on a 16-byte boundary, ``nbytes`` of them from ``offset`` on; ``clips``
+    is then the nisqa_wav_clip table, a numpy structured array of dtype WAV_CLIP whose src_off counts from ``offset`` and whose dst_off
+    is the clip's sample offset in the decoded group).  ``lengths`` are frames in every kind."""
+    __slots__ = ('ids', 'lengths', 'sr', 'offset', 'nbytes', 'is_i16', 'names', 'kind', 'clips')
 
-    def __init__(self, ids, lengths, sr, offset, nbytes, is_i16, names=None):
+    def __init__(self, ids, lengths, sr, offset, nbytes, is_i16, names=None, kind=None, clips=None):
         self.ids, self.lengths, self.sr, self.offset, self.nbytes, self.is_i16 = ids, lengths, sr, offset, nbytes, is_i16
         self.names = names
+        self.kind = kind if kind is not None else ('i16' if is_i16 else 'f32')
+        self.clips = clips
 
 
 class Staged(object):
@@ -216,15 +227,23 @@ class LengthAware(object):
 
     @staticmethod
     def staged_bytes(frames, srs, widths, pos):
-        """Bytes Ingest._stage lays out for the clips ``pos``: clips of one sample rate form a group, and a group is staged
-        as int16 only if ALL its clips are mono PCM16 (width 2) -- one stereo / 24-bit / float / G.711 file widens its whole
-        group to float32."""
+        """Bytes Ingest._stage lays out for the clips ``pos`` when it decodes on the host: clips of one sample rate form a group, and a
+        group is staged as int16 only if ALL its clips are mono PCM16 (width 2) -- one stereo / 24-bit / float / G.711 file widens
+        its whole group to float32."""
         pos = np.asarray(pos, dtype=np.int64)
         total = 0
         for sr in np.unique(srs[pos]):
             sel = pos[srs[pos] == sr]
             total += int(frames[sel].sum()) * (2 if (widths[sel] == 2).all() else 4)
         return total
+
+    @staticmethod
+    def raw_bytes(frames, widths, pos):
+        """Bytes Ingest._stage lays out for the clips ``pos`` with device decode: every clip at its own staged width (``widths``:
+        block_align of a verbatim data chunk, 4 of a host-decoded entry), each on a 16-byte boundary.  (A group of mono PCM16 clips
+        alone is packed without the pads: at most 15 bytes per clip less.)"""
+        pos = np.asarray(pos, dtype=np.int64)
+        return int(((frames[pos] * widths[pos] + _RAW_ALIGN - 1) // _RAW_ALIGN * _RAW_ALIGN).sum())
 
     def cut(self, frames, srs, widths):
         """Batches (lists of POSITIONS into the window) for clips with the given header fields.  Within a sample rate the
@@ -236,41 +255,62 @@ class LengthAware(object):
         n = len(frames)
         if n == 0:
             return []
-        tokens = np.maximum(1, np.asarray(self.tokens_of(frames, srs), dtype=np.int64))
         order = np.lexsort((np.arange(n), frames, widths, srs))        # by rate, then int16-before-float, then length, then input order
-        out, cur, ct = [], [], 0
-        grp, cost = {}, 0                                              # rate -> [int16 frames, float frames] of the open batch; its staged bytes
-        need = max(self.bs, self.min_clips)
-        cap, min_tokens = self.byte_cap, self.min_tokens
-        fr_l, sr_l, w_l, tk_l = frames.tolist(), srs.tolist(), widths.tolist(), tokens.tolist()   # (plain ints: this loop runs per item)
+        fr_l, sr_l, slow_l = frames.tolist(), srs.tolist(), (np.asarray(widths) != 2).tolist()      # (plain ints: the loop runs per item)
 
         def rate_cost(a, b):
             return 4 * (a + b) if b else 2 * a
 
-        for k in order.tolist():
+        def cost(k, grp):
+            # grp: rate -> (int16 frames, float frames) of the open batch -> (bytes clip k adds to it, the entry it leaves behind)
             sr, f = sr_l[k], fr_l[k]
-            slow = w_l[k] != 2
             a, b = grp.get(sr, (0, 0))
-            a2, b2 = (a, b + f) if slow else (a + f, b)
-            add = rate_cost(a2, b2) - rate_cost(a, b)
-            if cur and (cost + add > cap or sr != sr_l[cur[-1]] and len(cur) >= need):
+            a2, b2 = (a, b + f) if slow_l[k] else (a + f, b)
+            return rate_cost(a2, b2) - rate_cost(a, b), (sr, (a2, b2))
+        return self._cut(frames, srs, order, cost, lambda pos: self.staged_bytes(frames, srs, widths, pos))
+
+    def cut_raw(self, frames, srs, widths, fast):
+        """cut for an Ingest that stages for the device decoder: ``widths`` are the bytes per frame each clip is STAGED with
+        (block_align of a verbatim data chunk, 4 of a host-decoded entry) and a clip costs what raw_bytes says, whatever shares its
+        group; ``fast`` (bool per clip) marks the mono PCM16 clips, which come first within a rate so that a group of them alone
+        stays an int16 group."""
+        n = len(frames)
+        if n == 0:
+            return []
+        order = np.lexsort((np.arange(n), frames, ~np.asarray(fast, dtype=bool), srs))
+        size_l = ((frames * widths + _RAW_ALIGN - 1) // _RAW_ALIGN * _RAW_ALIGN).tolist()
+        return self._cut(frames, srs, order, lambda k, grp: (size_l[k], None), lambda pos: self.raw_bytes(frames, widths, pos))
+
+    def _cut(self, frames, srs, order, cost, total_bytes):
+        """The walk both cuts share.  cost(k, state of the open batch: a dict) -> (bytes clip k adds, (key, value) to record in the
+        state or None); total_bytes(positions) -> the staged bytes of a would-be batch."""
+        tokens = np.maximum(1, np.asarray(self.tokens_of(frames, srs), dtype=np.int64))
+        out, cur, ct = [], [], 0
+        grp, total = {}, 0
+        need = max(self.bs, self.min_clips)
+        cap, min_tokens = self.byte_cap, self.min_tokens
+        sr_l, tk_l = srs.tolist(), tokens.tolist()
+        for k in order.tolist():
+            sr = sr_l[k]
+            add, entry = cost(k, grp)
+            if cur and (total + add > cap or sr != sr_l[cur[-1]] and len(cur) >= need):
                 out.append(cur)
-                cur, ct, grp, cost = [], 0, {}, 0
-                a2, b2 = (0, f) if slow else (f, 0)
-                add = rate_cost(a2, b2)
+                cur, ct, grp, total = [], 0, {}, 0
+                add, entry = cost(k, grp)
             cur.append(k)
-            grp[sr] = (a2, b2)
-            cost += add
+            if entry is not None:
+                grp[entry[0]] = entry[1]
+            total += add
             ct += tk_l[k]
             if len(cur) >= need and ct >= min_tokens:
                 out.append(cur)
-                cur, ct, grp, cost = [], 0, {}, 0
+                cur, ct, grp, total = [], 0, {}, 0
         if cur:
             out.append(cur)
         # a small remainder does not get a launch chain of its own when the batch before it can take it (the byte cap is a
         # staging-buffer size, soft by half): a BiLSTM launch over 7 long clips lasts as long as one over 128 of them
         if len(out) >= 2 and len(out[-1]) * 2 < need and srs[out[-1][0]] == srs[out[-2][-1]] \
-                and self.staged_bytes(frames, srs, widths, out[-2] + out[-1]) <= self.byte_cap + self.byte_cap // 2:
+                and total_bytes(out[-2] + out[-1]) <= self.byte_cap + self.byte_cap // 2:
             tail = out.pop()
             out[-1] = out[-1] + tail
         return out
@@ -281,10 +321,12 @@ class Ingest(object):
     turns ``staged.groups`` into H2D copies out of ``ring.buf[staged.slot]`` and reports the event behind them with
     ``ring.release_after``.  Batches are prepared ``depth`` ahead on a producer thread."""
 
-    def __init__(self, ds, batches, pin, num_workers, depth=2, device=None):
+    def __init__(self, ds, batches, pin, num_workers, depth=2, device=None, device_decode=False):
         """``batches``: a list of index lists (staged exactly as given), or a LengthAware policy (the producer forms the
-        batches itself from the headers)."""
+        batches itself from the headers).  ``device_decode``: a rate group that is not all mono PCM16 is staged as a 'raw' group
+        (data chunks verbatim + a nisqa_wav_clip table, decoded by group_pcm on the GPU) instead of being decoded here."""
         self.ds, self.batches = ds, batches
+        self.device_decode = bool(device_decode)
         self.device = device
         self.ring = _take_ring(depth + 1, pin)
         # reader threads: what the caller asked for, but never more than the CPU budget leaves next to the producer and
@@ -368,18 +410,28 @@ class Ingest(object):
         infos = ctypes.cast(info.ctypes.data, ctypes.POINTER(_lib.WavInfo))
         frames, srs = info['n_frames'], info['sample_rate']
         fast = _verbatim_i16(info)
+        widths, verbatim = self._staged_widths(info) if self.device_decode else (None, None)
         # batch layout from the headers alone: clips of one rate are contiguous, int16 if ALL of them are mono PCM16
         layout, total = [], 0
         dst_off = np.full(n, -1, dtype=np.int64)
         for sr in dict.fromkeys(srs.tolist()):
             sel = np.flatnonzero(srs == sr)
             is_i16 = bool(fast[sel].all())
+            if self.device_decode and not is_i16:                   # raw group: every clip at its own width, on a 16-byte boundary
+                size = frames[sel] * widths[sel]
+                padded = (size + _RAW_ALIGN - 1) // _RAW_ALIGN * _RAW_ALIGN      # (the last clip's pad is the tail pad of the group)
+                off = total + np.concatenate(([0], np.cumsum(padded[:-1])))
+                nbytes = int(padded.sum())
+                dst_off[sel] = np.where(verbatim[sel], off, -1)
+                layout.append((int(sr), sel, 'raw', off, nbytes))
+                total = (total + nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
+                continue
             width = 2 if is_i16 else 4
             off = total + np.concatenate(([0], np.cumsum(frames[sel][:-1]))) * width
             nbytes = int(frames[sel].sum()) * width
             if is_i16:
                 dst_off[sel] = off
-            layout.append((int(sr), sel, is_i16, off, nbytes))
+            layout.append((int(sr), sel, 'i16' if is_i16 else 'f32', off, nbytes))
             total = (total + nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
         t3 = time.perf_counter()
         T['layout'] += t3 - t2
@@ -397,17 +449,52 @@ class Ingest(object):
             raise ValueError('Could not load file {}'.format(names[bad]))
         groups = []
         raw = None
-        for sr, sel, is_i16, off, nbytes in layout:
-            if not is_i16:                                          # stereo / 8, 24, 32-bit / float: host decode
+        for sr, sel, kind, off, nbytes in layout:
+            clips = None
+            if kind != 'i16':                                       # stereo / 8, 24, 32-bit / float: host decode ...
                 raw = buf.numpy() if raw is None else raw
                 for k, o in zip(sel.tolist(), off.tolist()):
+                    if dst_off[k] >= 0:                             # ... unless the data chunk went in verbatim (raw group)
+                        continue
                     y, _ = wavio.read_wav(names[k], ds.ms_channel)
                     if y.dtype == np.int16:
                         y = y.astype(np.float32) / np.float32(32768.0)
                     raw[o:o + 4 * len(y)].view(np.float32)[:] = y
+            if kind == 'raw':
+                clips = self._clip_table(info[sel], verbatim[sel], off - int(off[0]))
             groups.append(Group([idx[k] for k in sel.tolist()], frames[sel].tolist(), sr, int(off[0]) if len(off) else 0,
-                                nbytes, is_i16, [names[k] for k in sel.tolist()]))
+                                nbytes, kind == 'i16', [names[k] for k in sel.tolist()], kind, clips))
         return Staged(slot, groups)
+
+    def _staged_widths(self, info):
+        """Device decode: (bytes per frame each file is staged with, which files nisqa_ingest_read puts into the slot itself).  A WAV
+        file nisqa_wav_decode takes goes in verbatim at block_align bytes per frame, a mono 16-bit FLAC stream is decoded into the
+        slot as int16 by the reader threads; what is left -- other FLAC streams, a mean over more than 32 channels, a frame wider
+        than the kernel stages, an ms_channel the file does not have (the host decoder raises the reference's error for it) -- is
+        decoded on the host into float32."""
+        ch, blk = info['channels'].astype(np.int64), info['block_align'].astype(np.int64)
+        flac = info['tag'] == _lib.WAV_TAG_FLAC
+        sel = getattr(self.ds, 'ms_channel', None)
+        one = (ch == 1) | ((ch <= _lib.WAV_DECODE_MAX_MEAN) if sel is None else (ch > int(sel)) & (int(sel) >= 0))
+        wav = ~flac & one & (blk <= _lib.WAV_DECODE_MAX_BLOCK)
+        flac16 = flac & (info['bits'] == 16) & (ch == 1)
+        return np.where(wav, blk, np.where(flac16, 2, 4)), wav | flac16
+
+    def _clip_table(self, info, verbatim, src_off):
+        """nisqa_wav_clip rows of a raw group's files (header records ``info``, byte offsets ``src_off`` from the group's start)."""
+        t = np.zeros(len(info), dtype=WAV_CLIP)
+        ch = info['channels']
+        wav = verbatim & (info['tag'] != _lib.WAV_TAG_FLAC)
+        sel = getattr(self.ds, 'ms_channel', None)
+        t['src_off'] = src_off
+        t['dst_off'] = np.concatenate(([0], np.cumsum(info['n_frames'][:-1])))
+        t['n_frames'] = info['n_frames']
+        t['channels'] = np.where(wav, ch, 1)
+        t['container'] = np.where(wav, info['block_align'] // np.maximum(ch, 1), np.where(verbatim, 2, 4))
+        # a mono 16-bit FLAC stream lies in its slot as mono PCM16, a host-decoded file as mono little-endian float32
+        t['encoding'] = np.where(wav, info['tag'], np.where(verbatim, _lib.WAVENC_PCM, _lib.WAVENC_FLOAT))
+        t['channel'] = -1 if sel is None else np.where(wav & (ch > 1), int(sel), 0)
+        return t
 
     def _planned(self):
         """Batches of a LengthAware policy: yields (idx, probed) window by window; the headers of window w + 1 are
@@ -432,7 +519,11 @@ class Ingest(object):
                 # the window's batches are cut HERE, on the helper thread: sorting and walking 16 384 items in Python is
                 # 10-20 ms during which the producer staged nothing and the link ran dry once per window
                 fast = _verbatim_i16(info)
-                cuts = pol.cut(info['n_frames'].astype(np.int64), info['sample_rate'].astype(np.int64), np.where(fast, 2, 4))
+                if self.device_decode:                                  # the byte cap is charged with the staged widths
+                    cuts = pol.cut_raw(info['n_frames'].astype(np.int64), info['sample_rate'].astype(np.int64),
+                                       self._staged_widths(info)[0], fast)
+                else:
+                    cuts = pol.cut(info['n_frames'].astype(np.int64), info['sample_rate'].astype(np.int64), np.where(fast, 2, 4))
                 box[w] = ('ok', (names, enc, info, cuts), loc)
             except BaseException as e:
                 box[w] = ('err', e, loc)
@@ -506,3 +597,33 @@ class Ingest(object):
         if not self.thread.is_alive():
             _give_ring(self.ring)                  # the consumer's release events are still attached: reset() waits for them
         self.ring = None
+
+
+# -- what both loops do with a staged group ------------------------------------------------------------------
+def device_decode_default():
+    """Whether the predict and the training loop stage for the device decoder: yes, unless NISQA_HOST_DECODE=1 asks for the
+    host-decoding Ingest (the A/B switch and the cross-check of nisqa_wav_decode)."""
+    return os.environ.get('NISQA_HOST_DECODE') != '1'
+
+
+def copy_group(buf, g, device):
+    """H2D copy of group ``g`` out of the ring buffer ``buf`` (on the current stream): int16 / float32 samples, or the bytes of a raw
+    group."""
+    host = buf[g.offset:g.offset + g.nbytes]
+    if g.kind != 'raw':
+        host = host.view(torch.int16 if g.kind == 'i16' else torch.float32)
+    return host.to(device, non_blocking=True)
+
+
+def decode_group(x, g, eng):
+    """The device PCM of group ``g`` from what copy_group sent (on the current stream): int16 and float32 groups as they are, a raw
+    group through nisqa_wav_decode -> float32 [sum of lengths]."""
+    if g.kind != 'raw':
+        return x
+    return eng.decode(x, g.clips, int(sum(g.lengths)))
+
+
+def group_pcm(buf, g, eng):
+    """(ring buffer, Group, engine) -> the group's PCM on the engine's device: int16 for an 'i16' group, float32 for an 'f32' group,
+    copy + decode for a 'raw' one.  (A loop that copies and computes on different streams calls the two halves itself.)"""
+    return decode_group(copy_group(buf, g, eng.device), g, eng)

@@ -33,6 +33,15 @@ class ModelDev(ctypes.Structure):
                 ('cnn_wb', c_p), ('cnn_mode', c_i32), ('td_wb', c_p), ('pool_wb', c_p), ('arch', c_i32)]
 
 
+class WavClip(ctypes.Structure):
+    """nisqa_wav_clip"""
+    _fields_ = [('src_off', c_i64), ('dst_off', c_i64), ('n_frames', c_i64), ('channels', c_i32), ('container', c_i32),
+                ('encoding', c_i32), ('channel', c_i32)]
+
+
+WAVENC_PCM, WAVENC_FLOAT, WAVENC_ALAW, WAVENC_MULAW, WAVENC_BIG_ENDIAN = 1, 3, 6, 7, 0x10000      # NISQA_WAVENC_*
+WAV_DECODE_MAX_BLOCK, WAV_DECODE_MAX_MEAN = 1024, 32     # nisqa_wav_decode's limits: channels * container, channels of a mean
+
 # name -> (restype, argtypes); every symbol include/nisqa_hip.h declares
 SYMBOLS = {
     'nisqa_abi_version': (ctypes.c_int, []),
@@ -77,6 +86,7 @@ SYMBOLS = {
     'nisqa_predict_batch_pcm16': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, ctypes.POINTER(MelCfg),
                                                  ctypes.POINTER(ModelDev), c_p, ctypes.c_size_t, c_p, c_p]),
     'nisqa_pcm16_to_f32': (ctypes.c_int, [c_p, c_p, c_i64, c_p]),
+    'nisqa_wav_decode': (ctypes.c_int, [c_p, c_i64, c_p, c_i32, c_i64, c_p, c_p]),
     'nisqa_resample_workspace_bytes': (ctypes.c_size_t, [c_i32, c_i64]),
     'nisqa_resample': (ctypes.c_int, [c_p, c_i32, c_p, c_p, c_p, c_i32, c_i64, ctypes.c_double, c_p, c_i32, c_i32, c_p, ctypes.c_size_t, c_p, c_p]),
     'nisqa_de_align_fuse': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p]),

@@ -195,17 +195,15 @@ def train(nm):
             batches = [b[rank::world] for b in batches]
         y_hat_train = np.zeros((n_train, len(names)))
         loss_sum = 0.0
-        ing = _ingest.Ingest(nm.ds_train, batches, pin=True, num_workers=a['tr_num_workers'])
+        ing = _ingest.Ingest(nm.ds_train, batches, pin=True, num_workers=a['tr_num_workers'],
+                             device_decode=_ingest.device_decode_default())      # (NISQA_HOST_DECODE=1: decode on the staging thread)
         pending = None                                                   # (idx, device y_hat, device loss) of the last step
         try:
             for staged in ing:
                 # one group per sample rate in the batch (the reference loads every file at its own rate, NISQA_lib.py:2299-2310):
                 # train-mode BatchNorm spans the batch, so the groups stay ONE step -- only the spectrogram is per group
                 raw = ing.ring.buf[staged.slot]
-                pcms = []
-                for g in staged.groups:
-                    host = raw[g.offset:g.offset + g.nbytes].view(torch.int16 if g.is_i16 else torch.float32)
-                    pcms.append(host.to(tr.device, non_blocking=True))
+                pcms = [_ingest.group_pcm(raw, g, tr.eng) for g in staged.groups]     # (a raw group: copy + nisqa_wav_decode)
                 ev = torch.cuda.Event()
                 ev.record()                                              # behind the last group's copy
                 ing.ring.release_after(staged.slot, ev)
