@@ -346,6 +346,41 @@ int nisqa_tdtrain_plan(int32_t n_clips, int32_t n_tokens, int32_t n_tokens_padde
 int nisqa_tdtrain_step(const nisqa_tdtrain_args* args, void* stream);
 int nisqa_tdtrain_step_heads(const nisqa_tdtrain_args* args, void* stream);
 
+/* ---- NISQA_DE (double-ended) training: alignment + fusion between the two self-attention blocks, forward and backward --------
+ * Replaces, in the training step, Alignment.forward with AttDot / AttCosine and ApplyHardAttention (nisqa/NISQA_lib.py:
+ * 1264-1294, 1359-1366), Fusion.forward without lin_fusion (:1405-1417) as NISQA_DE.forward calls them (:414-419), and what
+ * autograd derives from them in loss.backward() (NISQA_model.py:139).
+ *
+ * Layout (both entries): PACKED token rows, as the training step keeps them -- no padding rows anywhere.  x / d_deg / d_ref are
+ * [tokens][64]; pair b's degraded tokens are rows deg_tok_off[b] .. + deg_n_wins[b] - 1, its reference tokens rows
+ * ref_tok_off[b] .. + ref_n_wins[b] - 1 (offsets in rows; every n_wins >= 1).  out / d_fused / idx are indexed by the DEGRADED
+ * rows: row deg_tok_off[b] + i holds token i of pair b (ld_out / ld floats per row, the fused width F = 192 for fuse 0 'x/y/-',
+ * 128 for 1 '+/-' and 2 'x/y' in columns 0 .. F-1; columns behind F are neither read nor written).
+ *
+ * nisqa_de_align_fuse_packed: nisqa_de_align_fuse (nisqa_hip.h: same kernel source, same arithmetic, same argmax rule -- raw
+ *   scores, lowest index on a tie) with apply = hard at packed offsets.  tile_off [n_pairs + 1]: exclusive prefix sum of
+ *   ceil(deg_n_wins[b] / 64); n_tiles = tile_off[n_pairs].  Writes out and idx (the chosen reference token, 0-based within the
+ *   pair's reference clip) for every degraded row and nothing else.
+ *
+ * nisqa_de_align_fuse_bwd: d_fused = d loss / d fused, idx as written by the forward ->
+ *     d_deg[deg row i]  = g0 + g2 (fuse 0) | g0 + g1 (fuse 1) | g0 (fuse 2)
+ *     d_ref[ref row j]  = sum over i with idx[i] == j of dya[i],  dya = g1 - g2 (0) | g0 - g1 (1) | g1 (2)
+ *   with g0, g1, g2 the 64-column blocks of a d_fused row.  d_deg and d_ref may be the same buffer (the forward's x layout) or
+ *   two buffers, each addressed by its own side's offsets.  max_n_wins >= every n_wins of both sides (it sizes the grid).
+ *   Contract:
+ *     - no floating-point atomics: each reference row's sum is taken in ascending i, in fp32, starting from +0 -- deterministic,
+ *       and bit for bit the sequential fp32 sum;
+ *     - every row of every token of both sides is written, reference rows no degraded token chose as zeros: the caller does
+ *       not pre-zero;
+ *     - the layout has no padding rows; no other row of d_deg / d_ref is touched;
+ *     - an idx outside [0, ref_n_wins[b]) matches no row and contributes nowhere (it cannot cause an access out of bounds). */
+int nisqa_de_align_fuse_packed(const float* x, const int32_t* deg_tok_off, const int32_t* deg_n_wins, const int32_t* ref_tok_off,
+                               const int32_t* ref_n_wins, const int32_t* tile_off, int32_t n_pairs, int32_t n_tiles, int32_t align,
+                               int32_t fuse, int32_t ld_out, float* out, int32_t* idx_out, void* stream);
+int nisqa_de_align_fuse_bwd(const float* d_fused, int32_t ld, const int32_t* idx, const int32_t* deg_tok_off,
+                            const int32_t* deg_n_wins, const int32_t* ref_tok_off, const int32_t* ref_n_wins, int32_t n_pairs,
+                            int32_t max_n_wins, int32_t fuse, float* d_deg, float* d_ref, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

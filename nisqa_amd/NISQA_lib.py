@@ -6,12 +6,12 @@ argument meaning and error behaviour, with the arithmetic moved to the HIP engin
   predict_mos / predict_dim (NL:1420-1467)        batching loop: WAV ingest -> device -> HIP forward
   NISQA / NISQA_DIM     (NL:29-268)                parameter containers with the reference's
                                                    state_dict keys; forward() runs the HIP path
-  NISQA_DE              (NL:272-424)               the same for the double-ended model (inference only)
+  NISQA_DE              (NL:272-424)               the same for the double-ended model
 
 Evaluation statistics (eval_results and helpers, NL:1469-1852) are re-exported from nisqa_amd/evaluation.py.
 Training runs through nisqa_amd/trainloop.py (CNN-SA-AP: nisqa_amd/train.py; StandardCNN + BiLSTM with pool last_step_bi / avg /
-max: nisqa_amd/train_lstm.py).  Out of scope here (raise NotImplementedError): NISQA_DE training, alternative blocks no shipped
-checkpoint uses.
+max: nisqa_amd/train_lstm.py; NISQA_DE: nisqa_amd/train_de.py).  Out of scope here (raise NotImplementedError): alternative blocks
+no shipped checkpoint uses.
 """
 import os
 import sys

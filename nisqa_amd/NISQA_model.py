@@ -413,6 +413,8 @@ class nisqaModel(object):
         else:
             dcon_train = dcon_val = None
         print('Training size: {}, Validation size: {}'.format(len(df_train), len(df_val)))
+        if self.args['double_ended'] and not self.args.get('csv_ref'):
+            raise ValueError('NISQA_DE needs csv_ref: the csv column with the reference file of each row (--csv_ref)')
         self.ds_train = self._dataset(df_train, dcon_train, self.args['data_dir'], self.args['csv_deg'], False,
                                       mos_column=self.args['csv_mos_train'])
         self.ds_val = self._dataset(df_val, dcon_val, self.args['data_dir'], self.args['csv_deg'], False,
@@ -449,7 +451,7 @@ class nisqaModel(object):
     def _loadDatasetsCSVpredict(self):
         csv_file_path = os.path.join(self.args['data_dir'], self.args['csv_file'])
         dfile = pd.read_csv(csv_file_path)
-        if 'csv_con' in self.args:
+        if self.args.get('csv_con') is not None:                     # (a checkpoint trained without a condition table carries csv_con: null)
             dcon = pd.read_csv(os.path.join(self.args['data_dir'], self.args['csv_con']))
         else:
             dcon = None
@@ -478,9 +480,12 @@ class nisqaModel(object):
             self.args['dim'] = False
         if self.args['model'] == 'NISQA_DE':
             self.args['double_ended'] = True
-            if self.args['mode'] == 'main':
-                raise NotImplementedError('NISQA_DE (double-ended) training is out of scope of nisqa_amd (inference only: '
-                                          'predict_csv with csv_ref)')
+            if self.args['mode'] == 'main':                            # what the HIP training step builds; no GPU work yet
+                from .train_de import check_de_train_args
+                check_de_train_args(self.args)
+                if self.dev.type != 'cuda':                            # (single-ended training fails on this later, in the trainer)
+                    raise NotImplementedError('NISQA_DE training runs as HIP kernels on a GPU: device {} has no training path '
+                                              '(nisqa_amd has no CPU path)'.format(self.dev))
         else:
             self.args['double_ended'] = False
             self.args['csv_ref'] = None

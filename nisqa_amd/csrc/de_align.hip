@@ -18,6 +18,7 @@
 // are written as zeros: the second self-attention multiplies them by zero probabilities, where a NaN would survive.
 #include "common.hpp"
 #include "../../include/nisqa_hip.h"
+#include "../../include/nisqa_train.h"
 
 namespace {
 
@@ -27,22 +28,34 @@ constexpr int DA_BLK = 64;                             // reference tokens per L
 constexpr int DA_WAVES = 4;
 constexpr int DA_ROWS = DA_BLK / DA_WAVES;             // rows of a block one wave scores
 
+// PACKED = false: the inference layout -- every degraded clip starts at a multiple of 64 rows, workgroup g owns rows 64 g .. 64 g
+// + 63 of x / out / idx_out, rows behind a clip's n_wins are padding and written as zeros.  PACKED = true: the training layout
+// (nisqa_de_align_fuse_packed, nisqa_train.h) -- clips back to back at deg_off[b], tile_off the exclusive prefix sum of
+// ceil(n_wins / 64) over the pairs, workgroup g owns up to 64 VALID rows of one clip and touches no other row.  Everything else,
+// the arithmetic included, is the same code.
+template <bool PACKED>
 __global__ __launch_bounds__(256) void de_align_fuse_kernel(const float* __restrict__ x, const int32_t* __restrict__ deg_off,
                                                             const int32_t* __restrict__ deg_n, const int32_t* __restrict__ ref_off,
                                                             const int32_t* __restrict__ ref_n, int n_pairs, int cosine, int soft,
                                                             int fuse, int ld_out, float* __restrict__ out,
-                                                            int32_t* __restrict__ idx_out) {
+                                                            int32_t* __restrict__ idx_out, const int32_t* __restrict__ tile_off) {
     __shared__ float yb[DA_BLK][DA_D];                                 // one block of reference rows (normalised for cosine)
     __shared__ float mm[DA_WAVES][DA_TILE], ml[DA_WAVES][DA_TILE];     // (max, sum) or (best score, index) per wave and token
     const int t = threadIdx.x, i = t & 63, w = t >> 6;
-    const int tile0 = blockIdx.x * DA_TILE;
-    const int b = find_segment(deg_off, n_pairs, tile0);
+    int tile0, b;                                                      // row of lane 0 in x / out / idx_out, the pair
+    if constexpr (PACKED) {
+        b = find_segment(tile_off, n_pairs, (int)blockIdx.x);
+        tile0 = deg_off[b] + ((int)blockIdx.x - tile_off[b]) * DA_TILE;
+    } else {
+        tile0 = blockIdx.x * DA_TILE;
+        b = find_segment(deg_off, n_pairs, tile0);
+    }
     const int nx = deg_n[b], ny = ref_n[b];
     const int ti = tile0 - deg_off[b] + i;                             // this lane's token within its clip
     const bool valid = ti < nx;
     const int F = fuse == 0 ? 3 * DA_D : 2 * DA_D;
     const int q0 = 16 * w;                                             // output: features q0 .. q0 + 15 of every part
-    if (tile0 - deg_off[b] >= nx) {                                    // a tile of padding rows only
+    if (!PACKED && tile0 - deg_off[b] >= nx) {                         // a tile of padding rows only
         float* o = out + (size_t)(tile0 + i) * ld_out;
         for (int p = 0; p < F / DA_D; ++p)
 #pragma unroll
@@ -196,6 +209,7 @@ __global__ __launch_bounds__(256) void de_align_fuse_kernel(const float* __restr
     // fusion: every wave writes features q0 .. q0 + 15 of each part of row i
     float* orow = out + (size_t)(tile0 + i) * ld_out;
     if (!valid) {
+        if constexpr (PACKED) return;                                  // the next clip's row: not this workgroup's
         for (int p = 0; p < F / DA_D; ++p)
 #pragma unroll
             for (int e = 0; e < 16; e += 4) *(f32x4*)(orow + p * DA_D + q0 + e) = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -224,6 +238,62 @@ __global__ __launch_bounds__(256) void de_align_fuse_kernel(const float* __restr
     }
 }
 
+// Backward of hard alignment + fusion (nisqa_de_align_fuse_bwd, nisqa_train.h): the argmax carries no gradient, so what is left
+// is the adjoint of Fusion.forward (NISQA_lib.py:1405-1417) and of the gather ApplyHardAttention does (:1359-1366).
+// Workgroup (r, b, side): four waves, wave w owns row 4 r + w of pair b's degraded (side 0) or reference (side 1) clip; lane =
+// feature, so every row read or written is one 256-byte access.
+//   side 0: dx[i] = g0 + g2 ('x/y/-'), g0 + g1 ('+/-'), g0 ('x/y') of row i of d_fused.
+//   side 1: d_ref[j] = sum over the degraded tokens i with idx[i] == j, ASCENDING i, of dya[i] = g1 - g2, g0 - g1, g1 -- a gather:
+//           the pair's idx goes through LDS in chunks of DB_CHUNK, every wave scans it 64 entries at a time (one ballot) and adds
+//           the rows that chose its j, lowest i first, to one fp32 accumulator per lane, starting from 0.  No atomics: the bits are those of the sequential
+//           sum.  A reference row nobody chose ends as zeros.
+constexpr int DB_ROWS = 4;                             // rows (waves) per workgroup
+constexpr int DB_CHUNK = 1024;                         // idx entries staged per pass
+
+__global__ __launch_bounds__(64 * DB_ROWS) void de_align_fuse_bwd_kernel(const float* __restrict__ dF, int ld,
+                                                                        const int32_t* __restrict__ idx,
+                                                                        const int32_t* __restrict__ deg_off,
+                                                                        const int32_t* __restrict__ deg_n,
+                                                                        const int32_t* __restrict__ ref_off,
+                                                                        const int32_t* __restrict__ ref_n, int fuse,
+                                                                        float* __restrict__ d_deg, float* __restrict__ d_ref) {
+    __shared__ int32_t sidx[DB_CHUNK];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    const int b = blockIdx.y;
+    const int nx = deg_n[b], ny = ref_n[b];
+    const int r = blockIdx.x * DB_ROWS + w;
+    const size_t x0 = (size_t)deg_off[b];
+    if (blockIdx.z == 0) {
+        if (r >= nx) return;
+        const float* g = dF + (x0 + r) * ld;
+        float v = g[lane];
+        if (fuse == 0) v = v + g[2 * DA_D + lane];
+        else if (fuse == 1) v = v + g[DA_D + lane];
+        d_deg[(x0 + r) * DA_D + lane] = v;
+        return;
+    }
+    if ((int)blockIdx.x * DB_ROWS >= ny) return;                      // uniform over the workgroup: no wave of it has a row
+    float acc = 0.f;
+    for (int c0 = 0; c0 < nx; c0 += DB_CHUNK) {
+        const int nc = min(DB_CHUNK, nx - c0);
+        __syncthreads();                                               // the previous chunk is consumed
+        for (int k = threadIdx.x; k < nc; k += 64 * DB_ROWS) sidx[k] = idx[x0 + c0 + k];
+        __syncthreads();
+        if (r < ny)                                                    // (r is uniform over the wave)
+            for (int k0 = 0; k0 < nc; k0 += 64) {                      // 64 entries per ballot, then the matches in ascending order
+                unsigned long long hit = __ballot(k0 + lane < nc && sidx[k0 + lane] == r);
+                while (hit) {
+                    const int k = k0 + __ffsll(hit) - 1;
+                    hit &= hit - 1;
+                    const float* g = dF + (x0 + c0 + k) * ld;
+                    const float dya = fuse == 0 ? g[DA_D + lane] - g[2 * DA_D + lane] : fuse == 1 ? g[lane] - g[DA_D + lane] : g[DA_D + lane];
+                    acc = acc + dya;
+                }
+            }
+    }
+    if (r < ny) d_ref[((size_t)ref_off[b] + r) * DA_D + lane] = acc;
+}
+
 }  // namespace
 
 extern "C" int nisqa_de_align_fuse(const float* x, const int32_t* deg_tok_off, const int32_t* deg_n_wins, const int32_t* ref_tok_off,
@@ -234,7 +304,35 @@ extern "C" int nisqa_de_align_fuse(const float* x, const int32_t* deg_tok_off, c
         apply > 1 || fuse < 0 || fuse > 2 || ld_out < F || (ld_out & 3))
         return NISQA_ERR_ARG;
     NQ_LAUNCH_BEGIN();
-    hipLaunchKernelGGL(de_align_fuse_kernel, dim3(total_deg_tok_padded / DA_TILE), dim3(256), 0, (hipStream_t)stream, x, deg_tok_off,
-                       deg_n_wins, ref_tok_off, ref_n_wins, n_pairs, align, apply, fuse, ld_out, out, idx_out);
+    hipLaunchKernelGGL(de_align_fuse_kernel<false>, dim3(total_deg_tok_padded / DA_TILE), dim3(256), 0, (hipStream_t)stream, x,
+                       deg_tok_off, deg_n_wins, ref_tok_off, ref_n_wins, n_pairs, align, apply, fuse, ld_out, out, idx_out,
+                       (const int32_t*)nullptr);
+    return NQ_LAUNCH_STATUS();
+}
+
+extern "C" int nisqa_de_align_fuse_packed(const float* x, const int32_t* deg_tok_off, const int32_t* deg_n_wins,
+                                          const int32_t* ref_tok_off, const int32_t* ref_n_wins, const int32_t* tile_off,
+                                          int32_t n_pairs, int32_t n_tiles, int32_t align, int32_t fuse, int32_t ld_out, float* out,
+                                          int32_t* idx_out, void* stream) {
+    const int F = fuse == 0 ? 3 * DA_D : 2 * DA_D;
+    if (!x || !deg_tok_off || !deg_n_wins || !ref_tok_off || !ref_n_wins || !tile_off || !out || !idx_out || n_pairs <= 0 ||
+        n_tiles < n_pairs || align < 0 || align > 1 || fuse < 0 || fuse > 2 || ld_out < F || (ld_out & 3))
+        return NISQA_ERR_ARG;
+    NQ_LAUNCH_BEGIN();
+    hipLaunchKernelGGL(de_align_fuse_kernel<true>, dim3(n_tiles), dim3(256), 0, (hipStream_t)stream, x, deg_tok_off, deg_n_wins,
+                       ref_tok_off, ref_n_wins, n_pairs, align, 0, fuse, ld_out, out, idx_out, tile_off);
+    return NQ_LAUNCH_STATUS();
+}
+
+extern "C" int nisqa_de_align_fuse_bwd(const float* d_fused, int32_t ld, const int32_t* idx, const int32_t* deg_tok_off,
+                                       const int32_t* deg_n_wins, const int32_t* ref_tok_off, const int32_t* ref_n_wins,
+                                       int32_t n_pairs, int32_t max_n_wins, int32_t fuse, float* d_deg, float* d_ref, void* stream) {
+    const int F = fuse == 0 ? 3 * DA_D : 2 * DA_D;
+    if (!d_fused || !idx || !deg_tok_off || !deg_n_wins || !ref_tok_off || !ref_n_wins || !d_deg || !d_ref || n_pairs <= 0 ||
+        n_pairs > 65535 || max_n_wins <= 0 || fuse < 0 || fuse > 2 || ld < F)
+        return NISQA_ERR_ARG;
+    NQ_LAUNCH_BEGIN();
+    hipLaunchKernelGGL(de_align_fuse_bwd_kernel, dim3((max_n_wins + DB_ROWS - 1) / DB_ROWS, n_pairs, 2), dim3(64 * DB_ROWS), 0,
+                       (hipStream_t)stream, d_fused, ld, idx, deg_tok_off, deg_n_wins, ref_tok_off, ref_n_wins, fuse, d_deg, d_ref);
     return NQ_LAUNCH_STATUS();
 }

@@ -164,6 +164,8 @@ TRAIN_SYMBOLS = {
     'nisqa_dropout_mask': (ctypes.c_int, [ctypes.c_uint64, ctypes.c_uint64, c_f, c_i64, c_p, c_p]),
     'nisqa_cast_scatter': (ctypes.c_int, [c_p, c_p, c_i32, c_p, c_p]),
     'nisqa_adam_step': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_f, c_i32, c_p]),
+    'nisqa_de_align_fuse_packed': (ctypes.c_int, [c_p] * 6 + [c_i32] * 5 + [c_p] * 3),
+    'nisqa_de_align_fuse_bwd': (ctypes.c_int, [c_p, c_i32] + [c_p] * 5 + [c_i32] * 3 + [c_p] * 3),
 }
 
 _lib = None

@@ -249,9 +249,13 @@ class _FlatTrainer(object):
         self._ck(self.lib.nisqa_cast_scatter(self._sums.data_ptr(), self._cast_table.data_ptr(), len(self._casts),
                                              _ptr(self.gflat), self._st()), 'nisqa_cast_scatter')
 
+    def _mask_draws(self):
+        """(first, end, probability) of every stretch of the step's mask buffer that one nisqa_dropout_mask launch fills"""
+        return ((0, self._mask_split, self.p_cnn), (self._mask_split, self._mask_total, self.p_td))
+
     def _draw_masks(self):
         self._mask_buf = self._new(self._mask_total)
-        for lo, hi, p in ((0, self._mask_split, self.p_cnn), (self._mask_split, self._mask_total, self.p_td)):
+        for lo, hi, p in self._mask_draws():
             if hi > lo and p > 0:
                 self._ck(self.lib.nisqa_dropout_mask(self._rng_seed, self._rng_off, p, hi - lo, _ptr(self._mask_buf, lo),
                                                      self._st()), 'nisqa_dropout_mask')
@@ -282,22 +286,35 @@ class _FlatTrainer(object):
         returned ``y_hat`` are in the concatenated clip order (concat_groups).  One group is exactly ``step_pcm``."""
         if len(groups) == 1:
             return self.step_pcm(groups[0][0], groups[0][1], groups[0][2], y, masks, bias)
+        return self._step(*self._mel_groups(groups), y, masks, bias)
+
+    def _mel_groups(self, groups):
+        """[(pcm, plan, sr), ...] -> (mel [frames][48], frame offsets on the device, n_wins, clip floors) of the groups' clips,
+        group after group (concat_groups)."""
+        if len(groups) == 1:
+            pcm, plan, sr = groups[0]
+            mel, floor = self.eng.mel(pcm, plan, sr, clamp=False)
+            return mel, plan.to(self.device)['frame_off'], plan.n_wins, floor
         mels, floors = zip(*[self.eng.mel(pcm, plan, sr, clamp=False) for pcm, plan, sr in groups])
         frame_off, n_wins, _ = concat_groups([plan.frame_off for _, plan, _ in groups], [plan.n_wins for _, plan, _ in groups])
         pin = self.device.type == 'cuda'
         host = torch.empty(frame_off.shape, dtype=torch.int32, pin_memory=pin)
         host.numpy()[...] = frame_off
-        return self._step(torch.cat(mels), host.to(self.device, non_blocking=pin), n_wins, torch.cat(floors), y, masks, bias)
+        return torch.cat(mels), host.to(self.device, non_blocking=pin), n_wins, torch.cat(floors)
 
-    def step_spec(self, specs, y, masks=None, bias=None):
-        """specs: list of [48, T] dB spectrograms (the input of segment_specs) -- used by the parity tests."""
+    def _spec_batch(self, specs):
+        """list of [48, T] dB spectrograms -> the same four things"""
         T = np.array([s.shape[1] for s in specs], dtype=np.int64)
         hop = int(self.args['ms_seg_hop_length'])
         n_wins = np.ceil((T - (SEG_LEN - 1)) / hop).astype(np.int64)
         mel = torch.from_numpy(np.ascontiguousarray(np.concatenate([np.asarray(s, np.float32).T for s in specs], 0))).to(self.device)
         frame_off = torch.from_numpy(np.concatenate(([0], np.cumsum(T))).astype(np.int32)).to(self.device)
         floor = torch.full((len(specs),), -3.0e38, dtype=torch.float32, device=self.device)
-        return self._step(mel, frame_off, n_wins, floor, y, masks, bias)
+        return mel, frame_off, n_wins, floor
+
+    def step_spec(self, specs, y, masks=None, bias=None):
+        """specs: list of [48, T] dB spectrograms (the input of segment_specs) -- used by the parity tests."""
+        return self._step(*self._spec_batch(specs), y, masks, bias)
 
     def _ksplit(self, rows, m=64, n=64):
         """K-chunks of a weight-gradient GEMM (K = rows of the batch): enough workgroups to fill 256 CUs a few times
@@ -382,19 +399,22 @@ class _FlatTrainer(object):
         for fn, n, arrays in self._packs:
             self._ck(fn(n, *arrays, self._st()), fn.__name__)
 
-    def _cnn_fwd(self, mel, frame_off, floor, masks, out6=None):
+    def _cnn_fwd(self, mel, frame_off, floor, masks, out6=None, mask_pfx='', pack=True):
         """The CNN in train mode from the [frames][48] spectrogram (BatchNorm on the batch statistics of the valid segments,
         the buffers updated) -> (per-layer records for _cnn_bwd, conv6's pooled activation [S][pixels][64]); out6: the buffer
-        that activation goes to (default: a new one)."""
+        that activation goes to (default: a new one).  One call is one call of the reference's module on the clips self.B /
+        self.S / self.seg_off describe; a step that calls it again (HipTrainerDE: the reference clips) gives that call's
+        dropout sites their own keys through mask_pfx and passes pack=False (the weight fragments are those of the first call)."""
         L_, P, B, S, st = self.lib, self.P, self.B, self.S, self._st()
-        self._pack_frags()
+        if pack:
+            self._pack_frags()
         cnn, act = [], None
         for i in range(1, 7):
             ci, co = _CONV[i - 1]
             h, w, (ho, wo) = self._geo[i - 1]
             wk, bk = 'cnn.model.conv%d.weight' % i, 'cnn.model.conv%d.bias' % i
             g, b_ = P['cnn.model.bn%d.weight' % i], P['cnn.model.bn%d.bias' % i]
-            drop = self._mask(masks, _DROP_AFTER[i], (S, co), self.p_cnn) if i in _DROP_AFTER else None
+            drop = self._mask(masks, mask_pfx + _DROP_AFTER[i], (S, co), self.p_cnn) if i in _DROP_AFTER else None
             dp = _ptr(drop) if drop is not None else None
             out = self._new(S, ho * wo, co) if i < 6 or out6 is None else out6.view(S, ho * wo, co)
             arg = self._new(S, ho * wo, co, dtype=torch.int32)
@@ -435,7 +455,9 @@ class _FlatTrainer(object):
         """Backward of _cnn_fwd from box = [d loss / d (its last activation)]: the gradients of conv1..6.weight and
         bn1..6.weight / .bias.  The conv biases' gradients are exactly zero under train-mode BatchNorm and stay at the
         cleared value.  The gradient comes in a list that is emptied here, so that it is freed once layer 6 has used it
-        (an argument would stay referenced by the caller until the call returns)."""
+        (an argument would stay referenced by the caller until the call returns).  bn1..6.weight / .bias and conv1.weight
+        are OVERWRITTEN, conv2..6.weight are ADDED to what self.G holds: a step with two CNN calls (HipTrainerDE) points self.G
+        at a second, cleared buffer for the second call and adds the two buffers afterwards."""
         L_, P, G, B, S, st = self.lib, self.P, self.G, self.B, self.S, self._st()
         da = box.pop()
         for i in range(6, 1, -1):
@@ -519,7 +541,208 @@ class _FlatTrainer(object):
         return loss
 
 
-class HipTrainer(_FlatTrainer):
+class _ClipSet(object):
+    """What the attention operators need to know about one set of clips of L[b] tokens: the device tables of step_tables(L)
+    (``tv[pfx + name]``) and the tile counts of its grouped GEMMs."""
+
+    def __init__(self, L, tv, tiles, pfx=''):
+        L = np.asarray(L, dtype=np.int64)
+        self.L, self.B, self.S, self.n_sq = L, len(L), int(L.sum()), int((L * L).sum())
+        self.seg_off = tv[pfx + 'seg_off']
+        self.desc = {k: (tv[pfx + 'desc_' + k], n) for k, n in tiles.items()}
+        self.att_off, self.att_len = tv[pfx + 'att_off'], tv[pfx + 'att_len']
+        self.pool_off, self.pool_len = tv[pfx + 'pool_off'], tv[pfx + 'pool_len']
+
+
+class _AttTrainer(_FlatTrainer):
+    """The attention half of a step, operator by operator, shared by HipTrainer (its cross-check path) and HipTrainerDE: a
+    self-attention block forward / backward for a parameter prefix, an input width and a clip set, and the attention-pooling
+    heads with the loss, forward and backward."""
+
+    def _upload_tables(self, parts):
+        """[(name, host array)] packed into ONE page-locked buffer and sent with one asynchronous copy -> (host buffer, which
+        must stay alive until the copy has run, device buffer, {name: device view})."""
+        offs, total = [], 0
+        for _, a in parts:
+            offs.append(total)
+            total += (a.nbytes + 15) // 16 * 16
+        pin = self.device.type == 'cuda'
+        host = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=pin)
+        hv = host.numpy()
+        for (_, a), o in zip(parts, offs):
+            hv[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
+        buf = host.to(self.device, non_blocking=pin)
+        tv = {}
+        for (k, a), o in zip(parts, offs):
+            tv[k] = buf[o:o + a.nbytes].view({'int32': torch.int32, 'int64': torch.int64}[a.dtype.name]).view(a.shape)
+        return host, buf, tv
+
+    # ---- thin wrappers over the C ABI ------------------------------------------------------------------------
+    def _ggemm(self, cs, kind, A, B, C, ta=0, tb=0, ao=0, bo=0, co=0):
+        d, tiles = cs.desc[kind]
+        self._ck(self.lib.nisqa_gemm_f32(_ptr(A, ao), _ptr(B, bo), _ptr(C, co), d.data_ptr(), d.shape[0], tiles, ta, tb, 1,
+                                         1.0, self._st()), 'nisqa_gemm_f32')
+
+    def _ew(self, op, x, aux=None, bias=None, rows=None, cols=None, out=None):
+        out = x if out is None else out
+        rows = x.numel() // (cols or x.shape[-1]) if rows is None else rows
+        cols = cols or x.shape[-1]
+        self._ck(self.lib.nisqa_elementwise(op, _ptr(x), _ptr(aux) if aux is not None else None,
+                                            _ptr(bias) if bias is not None else None, rows, cols, _ptr(out), self._st()),
+                 'nisqa_elementwise')
+        return out
+
+    def _ln_fwd(self, X, gk, bk, rows):
+        y, xh, rs = self._new(rows, 64), self._new(rows, 64), self._new(rows)
+        self._ck(self.lib.nisqa_layernorm_fwd(_ptr(X), _ptr(self.P[gk]), _ptr(self.P[bk]), rows, _ptr(y), _ptr(xh), _ptr(rs),
+                                              self._st()), 'nisqa_layernorm_fwd')
+        return y, xh, rs
+
+    def _ln_bwd(self, dY, xh, rs, gk, bk, rows):
+        s = self._coldot(dY, xh, rows, 64)
+        self._defer_cast(s, 0, 64, self.G[bk])
+        self._defer_cast(s, 64, 64, self.G[gk])
+        dX = self._new(rows, 64)
+        self._ck(self.lib.nisqa_layernorm_bwd(_ptr(dY), _ptr(xh), _ptr(rs), _ptr(self.P[gk]), rows, _ptr(dX), self._st()),
+                 'nisqa_layernorm_bwd')
+        return dX
+
+    # ---- self-attention block (NISQA_lib.py:988-996, 1025-1040 in train mode) -------------------------------------------
+    def _sa_fwd(self, cs, feat, n_in, pfx, n_layers, masks, mkey, p_drop):
+        """feat [cs.S][n_in] -> (x [cs.S][64], the record _sa_bwd needs).  pfx: the block's parameter prefix; mkey % (layer,
+        site): the key of a dropout mask, sites 'p' (attention probabilities, packed [sum L^2]), '1', 'f', '2' ([S][64])."""
+        L_ = self.lib
+        S, st = cs.S, self._st()
+        x0 = self._linear_fwd(feat, pfx + 'linear.weight', pfx + 'linear.bias', S, n_in, 64)
+        x, xh0, rs0 = self._ln_fwd(x0, pfx + 'norm1.weight', pfx + 'norm1.bias', S)
+        scale = 1.0 / math.sqrt(64.0)
+        n_sq = cs.n_sq
+        td = []
+        for l in range(n_layers):
+            p = pfx + 'layers.%d.' % l
+            r = {'x_in': x}
+            qkv = self._linear_fwd(x, p + 'self_attn.in_proj_weight', p + 'self_attn.in_proj_bias', S, 64, 192)
+            prob = self._new(n_sq)
+            self._ggemm(cs, 'qk', qkv, qkv, prob, tb=1, bo=64)
+            self._ck(L_.nisqa_softmax_rows_fwd(_ptr(prob), cs.att_off.data_ptr(), cs.att_len.data_ptr(), S, scale,
+                                               _ptr(prob), st), 'nisqa_softmax_rows_fwd')
+            mp = self._mask(masks, mkey % (l, 'p'), (n_sq,), p_drop)
+            pd = prob if mp is None else self._ew(3, prob, aux=mp, rows=1, cols=n_sq, out=self._new(n_sq))
+            ctx = self._new(S, 64)
+            self._ggemm(cs, 'pv', pd, qkv, ctx, bo=128)
+            att = self._linear_fwd(ctx, p + 'self_attn.out_proj.weight', p + 'self_attn.out_proj.bias', S, 64, 64)
+            m1 = self._mask(masks, mkey % (l, '1'), (S, 64), p_drop)
+            if m1 is not None:
+                self._ew(3, att, aux=m1)
+            r1 = self._ew(4, att, aux=x, out=self._new(S, 64))
+            x1, xh1, rs1 = self._ln_fwd(r1, p + 'norm1.weight', p + 'norm1.bias', S)
+            hh = self._linear_fwd(x1, p + 'linear1.weight', p + 'linear1.bias', S, 64, 64, relu=True)
+            mf = self._mask(masks, mkey % (l, 'f'), (S, 64), p_drop)
+            hd = hh if mf is None else self._ew(3, hh, aux=mf, out=self._new(S, 64))
+            f = self._linear_fwd(hd, p + 'linear2.weight', p + 'linear2.bias', S, 64, 64)
+            m2 = self._mask(masks, mkey % (l, '2'), (S, 64), p_drop)
+            if m2 is not None:
+                self._ew(3, f, aux=m2)
+            r2 = self._ew(4, f, aux=x1, out=self._new(S, 64))
+            x, xh2, rs2 = self._ln_fwd(r2, p + 'norm2.weight', p + 'norm2.bias', S)
+            r.update(qkv=qkv, prob=prob, mp=mp, pd=pd, ctx=ctx, m1=m1, x1=x1, xh1=xh1, rs1=rs1, hh=hh, mf=mf, hd=hd, m2=m2,
+                     xh2=xh2, rs2=rs2)
+            td.append(r)
+        return x, dict(cs=cs, pfx=pfx, n_in=n_in, feat=feat, xh0=xh0, rs0=rs0, layers=td)
+
+    def _sa_bwd(self, rec, dx):
+        """d loss / d (the block's output) [S][64] -> d loss / d feat [S][n_in]; the block's parameter gradients go to self.G."""
+        L_ = self.lib
+        cs, pfx = rec['cs'], rec['pfx']
+        S, n_sq, st = cs.S, cs.n_sq, self._st()
+        scale = 1.0 / math.sqrt(64.0)
+        for l in reversed(range(len(rec['layers']))):
+            p = pfx + 'layers.%d.' % l
+            r = rec['layers'][l]
+            dr2 = self._ln_bwd(dx, r['xh2'], r['rs2'], p + 'norm2.weight', p + 'norm2.bias', S)
+            df = dr2 if r['m2'] is None else self._ew(3, dr2, aux=r['m2'], out=self._new(S, 64))
+            dhd = self._linear_bwd(df, r['hd'], p + 'linear2.weight', p + 'linear2.bias', S, 64, 64)
+            if r['mf'] is not None:
+                self._ew(3, dhd, aux=r['mf'])
+            self._ew(2, dhd, aux=r['hh'])
+            dx1 = self._linear_bwd(dhd, r['x1'], p + 'linear1.weight', p + 'linear1.bias', S, 64, 64)
+            self._ew(4, dx1, aux=dr2)
+            dr1 = self._ln_bwd(dx1, r['xh1'], r['rs1'], p + 'norm1.weight', p + 'norm1.bias', S)
+            datt = dr1 if r['m1'] is None else self._ew(3, dr1, aux=r['m1'], out=self._new(S, 64))
+            dctx = self._linear_bwd(datt, r['ctx'], p + 'self_attn.out_proj.weight', p + 'self_attn.out_proj.bias', S, 64, 64)
+            dqkv = self._new(S, 192)
+            dp = self._new(n_sq)
+            self._ggemm(cs, 'dp', dctx, r['qkv'], dp, tb=1, bo=128)
+            self._ggemm(cs, 'dv', r['pd'], dctx, dqkv, ta=1, co=128)
+            if r['mp'] is not None:
+                self._ew(3, dp, aux=r['mp'], rows=1, cols=n_sq)
+            self._ck(L_.nisqa_softmax_rows_bwd(_ptr(r['prob']), _ptr(dp), cs.att_off.data_ptr(), cs.att_len.data_ptr(), S,
+                                               scale, _ptr(dp), st), 'nisqa_softmax_rows_bwd')
+            self._ggemm(cs, 'dq', dp, r['qkv'], dqkv, bo=64)
+            self._ggemm(cs, 'dk', dp, r['qkv'], dqkv, ta=1, co=64)
+            dxin = self._linear_bwd(dqkv, r['x_in'], p + 'self_attn.in_proj_weight', p + 'self_attn.in_proj_bias', S, 64, 192)
+            dx = self._ew(4, dxin, aux=dr1)
+        dx0 = self._ln_bwd(dx, rec['xh0'], rec['rs0'], pfx + 'norm1.weight', pfx + 'norm1.bias', S)
+        return self._linear_bwd(dx0, rec['feat'], pfx + 'linear.weight', pfx + 'linear.bias', S, rec['n_in'], 64)
+
+    # ---- attention-pooling heads + loss (NISQA_lib.py:1171-1183, 1946-1950), forward and backward ------------------------
+    def _heads_loss(self, cs, x, y, y_dev, bias_dev, per_head):
+        """x [cs.S][64]: the last self-attention block's output -> (y_hat [B][heads], loss [1], d loss / d x [S][64]); the heads'
+        parameter gradients go to self.G."""
+        L_ = self.lib
+        B, S, st = cs.B, cs.S, self._st()
+        H = len(self.heads)
+        y_hat = self._new(B, H)
+        pool = []
+        for hi_, hp in enumerate(self.heads):
+            u = self._linear_fwd(x, hp + 'linear1.weight', hp + 'linear1.bias', S, 64, 128, relu=True)
+            sc = self._linear_fwd(u, hp + 'linear2.weight', hp + 'linear2.bias', S, 128, 1)
+            att = self._new(S)
+            self._ck(L_.nisqa_softmax_rows_fwd(_ptr(sc), cs.pool_off.data_ptr(), cs.pool_len.data_ptr(), B, 1.0,
+                                               _ptr(att), st), 'nisqa_softmax_rows_fwd')
+            pooled = self._new(B, 64)
+            self._ggemm(cs, 'pool', att, x, pooled)
+            self._gemm(pooled, self.P[hp + 'linear3.weight'], y_hat, B, 1, 64, 64, 64, H, tb=1, co=hi_)
+            pool.append(dict(u=u, att=att, pooled=pooled))
+        b3 = torch.cat([self.P[hp + 'linear3.bias'] for hp in self.heads])
+        self._ew(0, y_hat, bias=b3, rows=B, cols=H)
+        loss_v = self._new(1 + H)
+        dyh = self._new(B, H)
+        entry = 'nisqa_mse_loss_heads' if per_head else 'nisqa_mse_loss'
+        self._ck(getattr(L_, entry)(_ptr(y_hat), _ptr(y_dev), _ptr(bias_dev) if bias_dev is not None else None, B, H,
+                                    _ptr(loss_v), _ptr(dyh), st), entry)
+        loss = loss_v[:1]
+        if _dist.world()[1] > 1:
+            # the loss is a mean over the labelled clips of the WHOLE batch: rescale this rank's share per head
+            cnt = torch.as_tensor((~np.isnan(np.asarray(y, np.float32).reshape(B, H))).sum(0), dtype=torch.float32)
+            tot = _dist.all_reduce_sum_(cnt.clone())
+            share = torch.where(tot > 0, cnt / tot.clamp(min=1), torch.zeros_like(cnt)).to(self.device)
+            self._ew(5, dyh, bias=share, rows=B, cols=H)
+            loss = _dist.all_reduce_sum_((loss_v[1:] * share).sum().reshape(1))
+
+        s = self._coldot(dyh, dyh, B, H)
+        dx = torch.zeros((S, 64), dtype=torch.float32, device=self.device)
+        tmp = self._new(S, 64)
+        for hi_, hp in enumerate(self.heads):
+            pr = pool[hi_]
+            self._defer_cast(s, hi_, 1, self.G[hp + 'linear3.bias'])
+            self._gemm(dyh, pr['pooled'], self.G[hp + 'linear3.weight'], 1, 64, B, H, 64, 64, ta=1, ao=hi_)
+            dpooled = self._new(B, 64)
+            self._gemm(dyh, self.P[hp + 'linear3.weight'], dpooled, B, 64, 1, H, 64, 64, ao=hi_)
+            datt = self._new(S)
+            self._ggemm(cs, 'datt', dpooled, x, datt, tb=1)
+            self._ggemm(cs, 'outer', pr['att'], dpooled, tmp, ta=1)
+            self._ew(4, dx, aux=tmp)
+            self._ck(L_.nisqa_softmax_rows_bwd(_ptr(pr['att']), _ptr(datt), cs.pool_off.data_ptr(), cs.pool_len.data_ptr(),
+                                               B, 1.0, _ptr(datt), st), 'nisqa_softmax_rows_bwd')
+            du = self._linear_bwd(datt, pr['u'], hp + 'linear2.weight', hp + 'linear2.bias', S, 128, 1)
+            self._ew(2, du, aux=pr['u'])
+            dxh = self._linear_bwd(du, x, hp + 'linear1.weight', hp + 'linear1.bias', S, 64, 128)
+            self._ew(4, dx, aux=dxh)
+        return y_hat, loss, dx
+
+
+class HipTrainer(_AttTrainer):
     LAYOUT = 'nisqa_amd flat buffer (HipTrainer.keys / kshape order)'
     FEAT_W = 'time_dependency.model.linear.weight'
 
@@ -586,36 +809,6 @@ class HipTrainer(_FlatTrainer):
                      hp + 'linear3.bias']
         return np.array([self.off[k] for k in keys], dtype=np.int32)
 
-    # ---- thin wrappers over the C ABI ------------------------------------------------------------------------
-    def _ggemm(self, kind, A, B, C, ta=0, tb=0, ao=0, bo=0, co=0):
-        d, tiles = self._desc[kind]
-        self._ck(self.lib.nisqa_gemm_f32(_ptr(A, ao), _ptr(B, bo), _ptr(C, co), d.data_ptr(), d.shape[0], tiles, ta, tb, 1,
-                                         1.0, self._st()), 'nisqa_gemm_f32')
-
-    def _ew(self, op, x, aux=None, bias=None, rows=None, cols=None, out=None):
-        out = x if out is None else out
-        rows = x.numel() // (cols or x.shape[-1]) if rows is None else rows
-        cols = cols or x.shape[-1]
-        self._ck(self.lib.nisqa_elementwise(op, _ptr(x), _ptr(aux) if aux is not None else None,
-                                            _ptr(bias) if bias is not None else None, rows, cols, _ptr(out), self._st()),
-                 'nisqa_elementwise')
-        return out
-
-    def _ln_fwd(self, X, gk, bk, rows):
-        y, xh, rs = self._new(rows, 64), self._new(rows, 64), self._new(rows)
-        self._ck(self.lib.nisqa_layernorm_fwd(_ptr(X), _ptr(self.P[gk]), _ptr(self.P[bk]), rows, _ptr(y), _ptr(xh), _ptr(rs),
-                                              self._st()), 'nisqa_layernorm_fwd')
-        return y, xh, rs
-
-    def _ln_bwd(self, dY, xh, rs, gk, bk, rows):
-        s = self._coldot(dY, xh, rows, 64)
-        self._defer_cast(s, 0, 64, self.G[bk])
-        self._defer_cast(s, 64, 64, self.G[gk])
-        dX = self._new(rows, 64)
-        self._ck(self.lib.nisqa_layernorm_bwd(_ptr(dY), _ptr(xh), _ptr(rs), _ptr(self.P[gk]), rows, _ptr(dX), self._st()),
-                 'nisqa_layernorm_bwd')
-        return dX
-
     # ---- batch bookkeeping ---------------------------------------------------------------------------------
     def _prepare(self, n_wins):
         L = np.asarray(n_wins, dtype=np.int64)
@@ -634,27 +827,14 @@ class HipTrainer(_FlatTrainer):
             if self.fused_td:
                 tparts, td_plan = self._td_plan(L)
                 parts = parts + tparts
-            offs, total = [], 0
-            for _, a in parts:
-                offs.append(total)
-                total += (a.nbytes + 15) // 16 * 16
-            pin = self.device.type == 'cuda'
-            host = torch.empty(max(total, 16), dtype=torch.uint8, pin_memory=pin)
-            hv = host.numpy()
-            for (_, a), o in zip(parts, offs):
-                hv[o:o + a.nbytes] = np.ascontiguousarray(a).view(np.uint8).reshape(-1)
-            buf = host.to(self.device, non_blocking=pin)
-            tv = {}
-            for (k, a), o in zip(parts, offs):
-                tv[k] = buf[o:o + a.nbytes].view({'int32': torch.int32, 'int64': torch.int64}[a.dtype.name]).view(a.shape)
+            host, buf, tv = self._upload_tables(parts)
             self._prep_key, self._prep_host, self._prep_buf = key, host, buf       # host stays alive until the copy has run
             self._prep_tables = (tv, tiles)
             self._td_plan_cur = td_plan
         tv, tiles = self._prep_tables
         self._tv = tv
         self.seg_off = tv['seg_off']
-        self._desc = {k: (tv['desc_' + k], n) for k, n in tiles.items()}
-        self.att_off, self.att_len, self.pool_off, self.pool_len = tv['att_off'], tv['att_len'], tv['pool_off'], tv['pool_len']
+        self._cs = _ClipSet(L, tv, tiles)
         self._sums.zero_()
         self._sum_i = 0
         self._casts = []
@@ -761,128 +941,9 @@ class HipTrainer(_FlatTrainer):
     def _td_unfused(self, feat, y, y_dev, bias_dev, per_head, masks):
         """The self-attention block, the pooling heads and the loss operator by operator (round-3 path, ~116 launches; kept
         behind NISQA_HIP_TRAIN_FUSED_TD=0 as the cross-check of csrc/train_td.hip) -> (y_hat, loss, d loss / d feat)."""
-        L_ = self.lib
-        B, S, st = self.B, self.S, self._st()
-        # ================= forward: self-attention =================
-        pfx = 'time_dependency.model.'
-        x0 = self._linear_fwd(feat, pfx + 'linear.weight', pfx + 'linear.bias', S, 384, 64)
-        x, xh0, rs0 = self._ln_fwd(x0, pfx + 'norm1.weight', pfx + 'norm1.bias', S)
-        scale = 1.0 / math.sqrt(64.0)
-        n_sq = int(self.sq[-1])
-        td = []
-        for l in range(self.n_layers):
-            p = pfx + 'layers.%d.' % l
-            r = {'x_in': x}
-            qkv = self._linear_fwd(x, p + 'self_attn.in_proj_weight', p + 'self_attn.in_proj_bias', S, 64, 192)
-            prob = self._new(n_sq)
-            self._ggemm('qk', qkv, qkv, prob, tb=1, bo=64)
-            self._ck(L_.nisqa_softmax_rows_fwd(_ptr(prob), self.att_off.data_ptr(), self.att_len.data_ptr(), S, scale,
-                                               _ptr(prob), st), 'nisqa_softmax_rows_fwd')
-            mp = self._mask(masks, 'td%d_p' % l, (n_sq,), self.p_td)
-            pd = prob if mp is None else self._ew(3, prob, aux=mp, rows=1, cols=n_sq, out=self._new(n_sq))
-            ctx = self._new(S, 64)
-            self._ggemm('pv', pd, qkv, ctx, bo=128)
-            att = self._linear_fwd(ctx, p + 'self_attn.out_proj.weight', p + 'self_attn.out_proj.bias', S, 64, 64)
-            m1 = self._mask(masks, 'td%d_1' % l, (S, 64), self.p_td)
-            if m1 is not None:
-                self._ew(3, att, aux=m1)
-            r1 = self._ew(4, att, aux=x, out=self._new(S, 64))
-            x1, xh1, rs1 = self._ln_fwd(r1, p + 'norm1.weight', p + 'norm1.bias', S)
-            hh = self._linear_fwd(x1, p + 'linear1.weight', p + 'linear1.bias', S, 64, 64, relu=True)
-            mf = self._mask(masks, 'td%d_f' % l, (S, 64), self.p_td)
-            hd = hh if mf is None else self._ew(3, hh, aux=mf, out=self._new(S, 64))
-            f = self._linear_fwd(hd, p + 'linear2.weight', p + 'linear2.bias', S, 64, 64)
-            m2 = self._mask(masks, 'td%d_2' % l, (S, 64), self.p_td)
-            if m2 is not None:
-                self._ew(3, f, aux=m2)
-            r2 = self._ew(4, f, aux=x1, out=self._new(S, 64))
-            x, xh2, rs2 = self._ln_fwd(r2, p + 'norm2.weight', p + 'norm2.bias', S)
-            r.update(qkv=qkv, prob=prob, mp=mp, pd=pd, ctx=ctx, m1=m1, x1=x1, xh1=xh1, rs1=rs1, hh=hh, mf=mf, hd=hd, m2=m2,
-                     xh2=xh2, rs2=rs2)
-            td.append(r)
-
-        # ================= forward: attention pooling heads, loss =================
-        H = len(self.heads)
-        y_hat = self._new(B, H)
-        pool = []
-        for hi_, hp in enumerate(self.heads):
-            u = self._linear_fwd(x, hp + 'linear1.weight', hp + 'linear1.bias', S, 64, 128, relu=True)
-            sc = self._linear_fwd(u, hp + 'linear2.weight', hp + 'linear2.bias', S, 128, 1)
-            att = self._new(S)
-            self._ck(L_.nisqa_softmax_rows_fwd(_ptr(sc), self.pool_off.data_ptr(), self.pool_len.data_ptr(), B, 1.0,
-                                               _ptr(att), st), 'nisqa_softmax_rows_fwd')
-            pooled = self._new(B, 64)
-            self._ggemm('pool', att, x, pooled)
-            self._gemm(pooled, self.P[hp + 'linear3.weight'], y_hat, B, 1, 64, 64, 64, H, tb=1, co=hi_)
-            pool.append(dict(u=u, att=att, pooled=pooled))
-        b3 = torch.cat([self.P[hp + 'linear3.bias'] for hp in self.heads])
-        self._ew(0, y_hat, bias=b3, rows=B, cols=H)
-        loss_v = self._new(1 + H)
-        dyh = self._new(B, H)
-        entry = 'nisqa_mse_loss_heads' if per_head else 'nisqa_mse_loss'
-        self._ck(getattr(L_, entry)(_ptr(y_hat), _ptr(y_dev), _ptr(bias_dev) if bias_dev is not None else None, B, H,
-                                    _ptr(loss_v), _ptr(dyh), st), entry)
-        loss = loss_v[:1]
-        if _dist.world()[1] > 1:
-            # the loss is a mean over the labelled clips of the WHOLE batch: rescale this rank's share per head
-            cnt = torch.as_tensor((~np.isnan(np.asarray(y, np.float32).reshape(B, H))).sum(0), dtype=torch.float32)
-            tot = _dist.all_reduce_sum_(cnt.clone())
-            share = torch.where(tot > 0, cnt / tot.clamp(min=1), torch.zeros_like(cnt)).to(self.device)
-            self._ew(5, dyh, bias=share, rows=B, cols=H)
-            loss = _dist.all_reduce_sum_((loss_v[1:] * share).sum().reshape(1))
-
-        # ================= backward: pooling heads =================
-        s = self._coldot(dyh, dyh, B, H)
-        dx = torch.zeros((S, 64), dtype=torch.float32, device=self.device)
-        tmp = self._new(S, 64)
-        for hi_, hp in enumerate(self.heads):
-            pr = pool[hi_]
-            self._defer_cast(s, hi_, 1, self.G[hp + 'linear3.bias'])
-            self._gemm(dyh, pr['pooled'], self.G[hp + 'linear3.weight'], 1, 64, B, H, 64, 64, ta=1, ao=hi_)
-            dpooled = self._new(B, 64)
-            self._gemm(dyh, self.P[hp + 'linear3.weight'], dpooled, B, 64, 1, H, 64, 64, ao=hi_)
-            datt = self._new(S)
-            self._ggemm('datt', dpooled, x, datt, tb=1)
-            self._ggemm('outer', pr['att'], dpooled, tmp, ta=1)
-            self._ew(4, dx, aux=tmp)
-            self._ck(L_.nisqa_softmax_rows_bwd(_ptr(pr['att']), _ptr(datt), self.pool_off.data_ptr(), self.pool_len.data_ptr(),
-                                               B, 1.0, _ptr(datt), st), 'nisqa_softmax_rows_bwd')
-            du = self._linear_bwd(datt, pr['u'], hp + 'linear2.weight', hp + 'linear2.bias', S, 128, 1)
-            self._ew(2, du, aux=pr['u'])
-            dxh = self._linear_bwd(du, x, hp + 'linear1.weight', hp + 'linear1.bias', S, 64, 128)
-            self._ew(4, dx, aux=dxh)
-
-        # ================= backward: self-attention layers =================
-        for l in reversed(range(self.n_layers)):
-            p = pfx + 'layers.%d.' % l
-            r = td[l]
-            dr2 = self._ln_bwd(dx, r['xh2'], r['rs2'], p + 'norm2.weight', p + 'norm2.bias', S)
-            df = dr2 if r['m2'] is None else self._ew(3, dr2, aux=r['m2'], out=self._new(S, 64))
-            dhd = self._linear_bwd(df, r['hd'], p + 'linear2.weight', p + 'linear2.bias', S, 64, 64)
-            if r['mf'] is not None:
-                self._ew(3, dhd, aux=r['mf'])
-            self._ew(2, dhd, aux=r['hh'])
-            dx1 = self._linear_bwd(dhd, r['x1'], p + 'linear1.weight', p + 'linear1.bias', S, 64, 64)
-            self._ew(4, dx1, aux=dr2)
-            dr1 = self._ln_bwd(dx1, r['xh1'], r['rs1'], p + 'norm1.weight', p + 'norm1.bias', S)
-            datt = dr1 if r['m1'] is None else self._ew(3, dr1, aux=r['m1'], out=self._new(S, 64))
-            dctx = self._linear_bwd(datt, r['ctx'], p + 'self_attn.out_proj.weight', p + 'self_attn.out_proj.bias', S, 64, 64)
-            dqkv = self._new(S, 192)
-            dp = self._new(n_sq)
-            self._ggemm('dp', dctx, r['qkv'], dp, tb=1, bo=128)
-            self._ggemm('dv', r['pd'], dctx, dqkv, ta=1, co=128)
-            if r['mp'] is not None:
-                self._ew(3, dp, aux=r['mp'], rows=1, cols=n_sq)
-            self._ck(L_.nisqa_softmax_rows_bwd(_ptr(r['prob']), _ptr(dp), self.att_off.data_ptr(), self.att_len.data_ptr(), S,
-                                               scale, _ptr(dp), st), 'nisqa_softmax_rows_bwd')
-            self._ggemm('dq', dp, r['qkv'], dqkv, bo=64)
-            self._ggemm('dk', dp, r['qkv'], dqkv, ta=1, co=64)
-            dxin = self._linear_bwd(dqkv, r['x_in'], p + 'self_attn.in_proj_weight', p + 'self_attn.in_proj_bias', S, 64, 192)
-            dx = self._ew(4, dxin, aux=dr1)
-        dx0 = self._ln_bwd(dx, xh0, rs0, pfx + 'norm1.weight', pfx + 'norm1.bias', S)
-        da = self._linear_bwd(dx0, feat, pfx + 'linear.weight', pfx + 'linear.bias', S, 384, 64)        # [S][6][64]
-
-        return y_hat, loss, da
+        x, rec = self._sa_fwd(self._cs, feat, 384, 'time_dependency.model.', self.n_layers, masks, 'td%d_%s', self.p_td)
+        y_hat, loss, dx = self._heads_loss(self._cs, x, y, y_dev, bias_dev, per_head)
+        return y_hat, loss, self._sa_bwd(rec, dx)                                                       # [S][6][64]
 
     def _step(self, mel, frame_off, n_wins, floor, y, masks, bias):
         self._prepare(n_wins)

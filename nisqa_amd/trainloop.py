@@ -1,7 +1,8 @@
 """Host side of ``nisqaModel.train()`` (reference nisqa/NISQA_model.py:83-570, ``_train_mos`` / ``_train_dim``): epochs,
 shuffled mini-batches, the bias-aware loss bookkeeping, per-epoch evaluation on the training and validation sets,
 ReduceLROnPlateau, early stopping, results CSV and checkpoints -- around the per-batch step, which runs as HIP kernels
-(``nisqa_amd.train.HipTrainer`` for CNN-SA-AP, ``nisqa_amd.train_lstm.HipTrainerLSTM`` for StandardCNN + BiLSTM: forward in
+(``nisqa_amd.train.HipTrainer`` for CNN-SA-AP, ``nisqa_amd.train_lstm.HipTrainerLSTM`` for StandardCNN + BiLSTM,
+``nisqa_amd.train_de.HipTrainerDE`` for the double-ended NISQA_DE, whose batches are pairs of files (``stage_pairs``): forward in
 train mode, backward, Adam).  WAV files reach the GPU through the same
 native ingest as prediction (``nisqa_amd.ingest``); the validation pass is the inference engine on the current weights.
 
@@ -33,6 +34,7 @@ from . import dist as _dist
 from . import ingest as _ingest
 from .evaluation import eval_results
 from .train import HipTrainer
+from .train_de import HipTrainerDE
 from .train_lstm import HipTrainerLSTM
 
 
@@ -131,7 +133,10 @@ class ReduceLROnPlateau(object):
 
 # ---- the loop -----------------------------------------------------------------------------------------------------
 def trainer_class(args):
-    """HipTrainerLSTM for cnn_model=standard / td=lstm, else HipTrainer (which refuses what it does not build)"""
+    """HipTrainerDE for model=NISQA_DE, HipTrainerLSTM for cnn_model=standard / td=lstm, else HipTrainer (each refuses what it
+    does not build)"""
+    if args.get('model') == 'NISQA_DE':
+        return HipTrainerDE
     if args.get('cnn_model') == 'standard' and args.get('td') == 'lstm':
         return HipTrainerLSTM
     return HipTrainer
@@ -142,6 +147,36 @@ def make_trainer(args, state_dict, device, lr):
 
 
 _DIM = ['mos', 'noi', 'dis', 'col', 'loud']
+
+
+def stage_pairs(tr, ds, ids):
+    """One batch of a double-ended training set -> (row ids in the step's clip order, degraded groups, reference groups) for
+    HipTrainerDE.step_groups.  Both files of every row are read on the host with the dataset's readers, as NISQA_lib._predict_de
+    reads pairs (no page-locked ring: feed rate is not what this path is about).  The rows are ordered by the sample rates and
+    sample types of their two files, so that each side falls into runs of one rate -- its groups (train.concat_groups) -- while
+    clip k of either side stays row k: a pair whose files differ in rate simply has its two clips in groups of different rates."""
+    refs = ds.ref_view()
+    items = [(ds.load_audio(i), refs.load_audio(i)) for i in ids]
+    kind = lambda it: (int(it[1]), it[0].dtype.str)
+    order = sorted(range(len(ids)), key=lambda k: kind(items[k][0]) + kind(items[k][1]))      # stable: ties keep the batch's order
+    eng = tr.eng
+    sides = []
+    for side, view in ((0, ds), (1, refs)):
+        groups, run = [], []
+        for pos, k in enumerate(order):
+            run.append(k)
+            if pos + 1 == len(order) or kind(items[order[pos + 1]][side]) != kind(items[k][side]):
+                sr = int(items[k][side][1])
+                lengths = [len(items[j][side][0]) for j in run]
+                plan = eng.audio_plan(lengths, sr, names=[view.file_path(ids[j]) for j in run])
+                pcm = torch.from_numpy(np.concatenate([items[j][side][0] for j in run])).to(eng.device)
+                pcm = eng.resample(pcm, lengths, sr)                     # a no-op unless ms_sr is set and differs from the files' rate
+                if pcm.dtype == torch.int16:
+                    pcm = eng.pcm16_to_f32(pcm)
+                groups.append((pcm, plan, eng.rate(sr)))
+                run = []
+        sides.append(groups)
+    return np.asarray([ids[k] for k in order]), sides[0], sides[1]
 
 
 def _targets(nm):
@@ -195,11 +230,27 @@ def train(nm):
             batches = [b[rank::world] for b in batches]
         y_hat_train = np.zeros((n_train, len(names)))
         loss_sum = 0.0
-        ing = _ingest.Ingest(nm.ds_train, batches, pin=True, num_workers=a['tr_num_workers'],
-                             device_decode=_ingest.device_decode_default())      # (NISQA_HOST_DECODE=1: decode on the staging thread)
         pending = None                                                   # (idx, device y_hat, device loss) of the last step
+
+        def run_step(ids, step):
+            nonlocal pending, loss_sum
+            bias = None
+            if losses[0].apply_bias_loss:                                # [B, heads, 4]: every head's own line per database
+                bias = np.stack([bl.rows(ids) for bl in losses], 1)
+            if pending is not None:                                      # fetch the previous step's numbers while this one runs
+                y_hat_train[pending[0]] = pending[1].cpu().numpy()
+                loss_sum += float(pending[2])
+            loss = step(y_train[ids].astype(np.float32), bias)
+            pending = (ids, tr.last['y_hat'], loss)
+
+        ing = None if a['double_ended'] else _ingest.Ingest(
+            nm.ds_train, batches, pin=True, num_workers=a['tr_num_workers'],
+            device_decode=_ingest.device_decode_default())                # (NISQA_HOST_DECODE=1: decode on the staging thread)
         try:
-            for staged in ing:
+            for b in (batches if ing is None else ()):                   # pairs: both files of every row, the two sides in row order
+                ids, g_deg, g_ref = stage_pairs(tr, nm.ds_train, b)
+                run_step(ids, lambda y, bias: tr.step_groups(g_deg, g_ref, y, bias=bias))
+            for staged in (() if ing is None else ing):
                 # one group per sample rate in the batch (the reference loads every file at its own rate, NISQA_lib.py:2299-2310):
                 # train-mode BatchNorm spans the batch, so the groups stay ONE step -- only the spectrogram is per group
                 raw = ing.ring.buf[staged.slot]
@@ -215,19 +266,13 @@ def train(nm):
                         pcm = tr.eng.pcm16_to_f32(pcm)
                     groups.append((pcm, plan, tr.eng.rate(g.sr)))
                 ids = np.concatenate([np.asarray(g.ids) for g in staged.groups])     # the clip order of the step: group after group
-                bias = None
-                if losses[0].apply_bias_loss:                            # [B, heads, 4]: every head's own line per database
-                    bias = np.stack([bl.rows(ids) for bl in losses], 1)
-                if pending is not None:                                  # fetch the previous step's numbers while this one runs
-                    y_hat_train[pending[0]] = pending[1].cpu().numpy()
-                    loss_sum += float(pending[2])
-                loss = tr.step_groups(groups, y_train[ids].astype(np.float32), bias=bias)
-                pending = (ids, tr.last['y_hat'], loss)
+                run_step(ids, lambda y, bias: tr.step_groups(groups, y, bias=bias))
             if pending is not None:
                 y_hat_train[pending[0]] = pending[1].cpu().numpy()
                 loss_sum += float(pending[2])
         finally:
-            ing.close()
+            if ing is not None:
+                ing.close()
         loss = loss_sum / max(1, len(batches))
         if world > 1:                                                    # ranks filled disjoint rows of the prediction table
             y_hat_train = _dist.all_reduce_sum_(torch.from_numpy(y_hat_train)).numpy()
