@@ -369,6 +369,53 @@ typedef struct nisqa_wav_clip {      /* 40 bytes, device array */
 int nisqa_wav_decode(const void* raw, int64_t raw_bytes, const nisqa_wav_clip* clips, int32_t n_clips,
                      int64_t max_frames, float* out, void* stream);
 
+/* FLAC streams already on the device -> what the host path produces for the same files, bit for bit: int16 samples (out_i16: every
+ * clip a mono 16-bit stream, the form the pcm16 entries take) or float32 mono samples (value / 2^(bits - 1); of two channels the one
+ * `channel` names, or for -1 their float32 mean as numpy computes it).  raw holds each clip's frame region (first audio frame to end of
+ * file, verbatim) at src_off; frames [dev, n_frames rows] is the frame table the native ingest writes next to the regions: row g belongs
+ * to clip `clip`, starts at byte `offset` of that clip's region and ends where row g + 1 starts (the last row of a clip: at or before
+ * the region's end), and carries samples [first_sample, first_sample + block_size) with first_sample = (g - frame0) * block_size.
+ * Streams: fixed block size, 4-24 bits, 1-2 channels.  One lane decodes one frame (header with CRC-8, CONSTANT / VERBATIM / FIXED /
+ * LPC subframes, Rice residuals, wasted bits, CRC-16); a second kernel undoes the stereo decorrelation and writes out; a third checks
+ * the MD5 of the samples against md5 where md5_set.  status [dev, n_clips + 1 words, zeroed by the caller]: bits NISQA_FLAC_BAD_*
+ * (1 << the failed frame check, the MD5, the table) are OR-ed into word `clip`, a row that names no clip into the last word; a clip
+ * whose word is not 0 has undefined samples.  Every row is checked against its clip on the device before it is used: no load leaves
+ * [src_off, src_off + src_bytes) and no store leaves [dst_off, dst_off + n_samples) of out, whatever the tables say.
+ * ws: at least what the workspace-size entry below returns, 256-byte aligned; md5_bytes: bytes reserved in it for the samples of the
+ * clips with md5_set when out_i16 is 0 (each clip's md5_off .. + n_samples * channels * ((bits + 7) / 8), multiples of 4). */
+#define NISQA_FLAC_BAD_MD5 0x80
+#define NISQA_FLAC_BAD_TABLE 0x100
+typedef struct nisqa_flac_clip {      /* 88 bytes, device array */
+    int64_t src_off;     /* byte offset of the clip's frame region in `raw`, multiple of 16 */
+    int64_t src_bytes;
+    int64_t dst_off;     /* sample offset of the clip in `out` */
+    int64_t n_samples;   /* per channel */
+    int64_t md5_off;     /* see md5_bytes */
+    int32_t frame0;      /* first row of the clip in `frames` */
+    int32_t n_frames;
+    int32_t block_size;  /* STREAMINFO's: every frame but the last carries this many samples */
+    int32_t bits;
+    int32_t channels;
+    int32_t channel;     /* >= 0: ms_channel; -1: the mean */
+    int32_t md5_set;
+    int32_t reserved;
+    uint8_t md5[16];
+} nisqa_flac_clip;
+#ifndef NISQA_FLAC_FRAME_DEFINED
+#define NISQA_FLAC_FRAME_DEFINED
+typedef struct nisqa_flac_frame {     /* 16 bytes; the same record in nisqa_ingest.h */
+    int32_t offset;
+    int32_t first_sample;
+    int32_t block_size;
+    int32_t clip;
+} nisqa_flac_frame;
+#endif
+size_t nisqa_flac_workspace_bytes(int32_t n_frames, int32_t max_block, int32_t max_channels, int64_t md5_bytes);
+int nisqa_flac_decode(const void* raw, int64_t raw_bytes, const nisqa_flac_clip* clips, int32_t n_clips,
+                      const nisqa_flac_frame* frames, int32_t n_frames, int32_t max_block, int32_t max_channels,
+                      int32_t out_i16, void* out, int64_t out_samples, int64_t md5_bytes, void* ws, size_t ws_bytes,
+                      int32_t* status, void* stream);
+
 /* lb.load(path, sr=ms_sr) for clips already on the device (NISQA_lib.py:2300, 2304 -> librosa.resample(y, sr_file, ms_sr,
  * res_type='kaiser_best') -> resampy): clip b = pcm[in_off[b] .. in_off[b + 1]) (float32 samples, or int16 PCM scaled by 1 / 32768
  * when is_pcm16) at the file's rate -> out[out_off[b] .. out_off[b + 1]) at ratio = ms_sr / sr_file.  out_off[b + 1] - out_off[b] =

@@ -74,6 +74,47 @@ int nisqa_ingest_read(const char* const* paths, int32_t n, nisqa_wav_info* info,
  * float32 is that value / 2^(bits - 1)).  Returns NISQA_WAV_OK or an NISQA_WAV_ERR_* code. */
 int nisqa_ingest_decode_flac(const char* path, const nisqa_wav_info* info, int32_t* dst);
 
+/* ---- FLAC streams for the device decoder (nisqa_flac_decode of libnisqa_hip.so) ----
+ * The reader threads do not decode such a stream: they copy its frame region (first audio frame to end of file) verbatim and index
+ * its frames; a HIP kernel decodes them, one lane per frame. */
+typedef struct nisqa_flac_plan {
+    int32_t eligible;      /* 1: the device path takes the stream.  That is: STREAMINFO has min_block == max_block (a fixed block
+                              size) and the first frame's blocking-strategy bit agrees, the total length is known and >= the block
+                              size, 4-24 bits, 1 or 2 channels, region and length below 2^31.  0: the host path (everything below 0) */
+    int32_t n_frames;      /* ceil(total / block_size) */
+    int64_t region_off;    /* file offset of the first audio frame */
+    int64_t region_bytes;  /* from there to the end of the file */
+    int64_t n_samples;     /* per channel: STREAMINFO's total */
+    int32_t block_size, bits, channels;
+    int32_t md5_set;       /* STREAMINFO carries the MD5 of the samples */
+    uint8_t md5[16];
+} nisqa_flac_plan;
+
+/* One row per frame, written by the flac-read entry below next to the clip's region; the kernel's frame table. */
+#ifndef NISQA_FLAC_FRAME_DEFINED
+#define NISQA_FLAC_FRAME_DEFINED
+typedef struct nisqa_flac_frame {
+    int32_t offset;        /* byte offset of the frame in its clip's region */
+    int32_t first_sample;  /* running sum of the block sizes before it */
+    int32_t block_size;
+    int32_t clip;          /* the caller's clip_id of the file (the row of the device clip table) */
+} nisqa_flac_frame;
+#endif
+
+/* plan[i] for every file i with info[i].status == OK and tag NISQA_WAV_TAG_FLAC (info from the probe entry; every other plan[i] is
+ * zeroed: not eligible).  Reads the metadata blocks and the first frame header of each such file.  Returns the number eligible, or -1. */
+int nisqa_ingest_flac_plan(const char* const* paths, int32_t n, const nisqa_wav_info* info, nisqa_flac_plan* plan, int32_t n_threads);
+
+/* For every file i with region_off[i] >= 0 (plan[i].eligible): pread its frame region verbatim to (char*)dst + region_off[i] and write
+ * plan[i].n_frames rows of nisqa_flac_frame to (char*)dst + table_off[i] (a multiple of 4), each stamped with clip_id[i].  The walk
+ * starts at the first frame and scans forward for the next sync whose header parses, whose CRC-8 holds, whose sample format is the
+ * stream's and whose frame number is the previous + 1 (the number only filters false syncs: the first may be anything); positions are
+ * the running sum of the block sizes.  status[i] = NISQA_WAV_OK, or an NISQA_WAV_ERR_* code when the file cannot be read or indexed (a
+ * missing successor, a block size other than the stream's before the last frame, more frames than planned, a sum other than the stream
+ * length): the caller then sends the file down the host path.  Returns the number of such files, or -1. */
+int nisqa_ingest_flac_read(const char* const* paths, int32_t n, const nisqa_flac_plan* plan, void* dst, const int64_t* region_off,
+                           const int64_t* table_off, const int32_t* clip_id, int32_t* status, int32_t n_threads);
+
 #ifdef __cplusplus
 }
 #endif

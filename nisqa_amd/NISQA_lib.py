@@ -585,7 +585,10 @@ def _predict(model, ds, bs, dev, num_workers, on_rows=None):
                              # files that are not mono PCM16 travel as raw data chunks and are decoded by nisqa_wav_decode
                              # (ingest.copy_group on the copy stream, ingest.decode_group on a kernel stream: the two halves of
                              # ingest.group_pcm); NISQA_HOST_DECODE=1: the staging thread decodes them, as before
-                             device_decode=on_gpu and _ingest.device_decode_default())
+                             device_decode=on_gpu and _ingest.device_decode_default(),
+                             # FLAC streams travel as their frame regions and are decoded by nisqa_flac_decode (NISQA_HOST_FLAC=1:
+                             # by the reader threads, as before)
+                             device_flac=on_gpu and _ingest.device_flac_default())
         copy_stream, streams = _loop_streams(eng.device) if on_gpu else (None, [None, None])
         inflight = []                                                   # (ids, host rows, event behind them)
         keep_inflight = max(1, int(os.environ.get('NISQA_LOOP_INFLIGHT', '2')))
@@ -599,9 +602,11 @@ def _predict(model, ds, bs, dev, num_workers, on_rows=None):
             # 256 clips; which it was depended on the order streams were created in)
             t0 = clock()
             while len(inflight) > keep:
-                ids, rows, done = inflight.pop(0)
+                ids, rows, done, flagged = inflight.pop(0)
                 if done is not None:
                     done.synchronize()
+                if flagged is not None:                             # (g, the status words nisqa_flac_decode left for it)
+                    _ingest.check_flac_status(flagged[0], flagged[1].numpy(), getattr(ds, 'ms_channel', None))
                 y_local[np.asarray(ids) - lo] = rows.numpy()
                 if on_rows is not None:
                     on_rows(ids, rows.numpy())
@@ -644,11 +649,16 @@ def _predict(model, ds, bs, dev, num_workers, on_rows=None):
                         tables['_buf'].record_stream(st)
                         rows = torch.empty(out.shape, dtype=out.dtype, pin_memory=True)
                         rows.copy_(out, non_blocking=True)           # [B, heads] floats, behind the kernels
+                        flagged = None
+                        if g.kind == 'flac':                         # the decoder's status words come back with the rows
+                            words = torch.empty(g.status.shape, dtype=g.status.dtype, pin_memory=True)
+                            words.copy_(g.status, non_blocking=True)
+                            flagged = (g, words)
                         done = torch.cuda.Event()
                         done.record(st)
-                        inflight.append((g.ids, rows, done))
+                        inflight.append((g.ids, rows, done, flagged))
                     else:
-                        inflight.append((g.ids, out, None))
+                        inflight.append((g.ids, out, None, None))
             T['enqueue'] += clock() - t_got
             drain(keep=keep_inflight * len(staged.groups))           # results of the batch before the previous one
             t_it = clock()

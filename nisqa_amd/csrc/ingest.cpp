@@ -8,6 +8,8 @@
 // (nisqa_amd/wavio.py) with lb.load's semantics.  FLAC files (flac.hpp) ARE decoded here, by the same threads: a mono
 // 16-bit stream straight into its int16 slot of the staging buffer (the same fast path as PCM16 from then on), any other
 // stream to interleaved int32 for the host mirror (nisqa_ingest_decode_flac).
+// For the device decoder (nisqa_flac_decode) the threads only plan a FLAC stream (nisqa_ingest_flac_plan) and copy its frame region
+// verbatim with a frame table (nisqa_ingest_flac_read, flac_frame.hpp).
 #include <atomic>
 #include <condition_variable>
 #include <cstring>
@@ -21,6 +23,7 @@
 
 #include "../../include/nisqa_ingest.h"
 #include "flac.hpp"
+#include "flac_frame.hpp"
 
 namespace {
 
@@ -209,6 +212,61 @@ int decode_flac_file(const char* path, const nisqa_wav_info* info, char* dst, bo
     return done == info->n_frames ? NISQA_WAV_OK : NISQA_WAV_ERR_READ;
 }
 
+// ---- FLAC for the device decoder: plan (eligibility, frame region) and read (region verbatim + frame table) ----
+const nqff::Tables& frame_tables() {
+    static const nqff::Tables* t = [] { auto* x = new nqff::Tables(); nqff::fill_tables(*x); return x; }();
+    return *t;
+}
+
+void plan_flac(const char* path, const nisqa_wav_info* info, nisqa_flac_plan* out) {
+    std::memset(out, 0, sizeof(*out));
+    if (info->status != NISQA_WAV_OK || info->tag != NISQA_WAV_TAG_FLAC) return;
+    const int fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return;
+    struct stat sb;
+    unsigned char b[64];
+    nqflac::Stream s;
+    bool ok = fstat(fd, &sb) == 0 && info->data_offset + 42 <= (int64_t)sb.st_size && pread_full(fd, b, 42, (off_t)info->data_offset) &&
+              nqflac::stream_info(b, 42, s) == 0;
+    int64_t pos = info->data_offset + 4;
+    while (ok) {                                             // the metadata blocks (walk_metadata, without the file in memory)
+        ok = pos + 4 <= (int64_t)sb.st_size && pread_full(fd, b, 4, (off_t)pos);
+        if (!ok) break;
+        pos += 4 + (((int64_t)b[1] << 16) | ((int64_t)b[2] << 8) | b[3]);
+        ok = pos <= (int64_t)sb.st_size;
+        if (b[0] >> 7) break;
+    }
+    const int64_t region = ok ? (int64_t)sb.st_size - pos : 0;
+    nqff::Header h;
+    ok = ok && region >= 16 && region < ((int64_t)1 << 31) && pread_full(fd, b, 16, (off_t)pos) &&
+         nqff::parse_header(frame_tables(), b, 16, h) == nqff::HDR_OK;
+    close(fd);
+    if (!ok) return;
+    out->region_off = pos;
+    out->region_bytes = region;
+    out->block_size = s.max_block;
+    out->bits = s.bits;
+    out->channels = s.channels;
+    out->md5_set = s.have_md5;
+    std::memcpy(out->md5, s.md5, 16);
+    out->n_samples = info->n_frames;
+    out->n_frames = (int32_t)((info->n_frames + s.max_block - 1) / s.max_block);
+    out->eligible = s.min_block == s.max_block && !h.variable && s.total > 0 && s.total == info->n_frames && s.total >= s.max_block &&
+                    s.total < ((int64_t)1 << 31) && s.bits >= 4 && s.bits <= 24 && s.channels >= 1 && s.channels <= 2;
+}
+
+int read_flac_region(const char* path, const nisqa_flac_plan* pl, unsigned char* dst, nisqa_flac_frame* rows, int32_t clip) {
+    if (!pl->eligible) return NISQA_WAV_ERR_FORMAT;
+    const int fd = open(path, O_RDONLY | O_CLOEXEC);
+    if (fd < 0) return NISQA_WAV_ERR_OPEN;
+    const bool got = pread_full(fd, dst, (size_t)pl->region_bytes, (off_t)pl->region_off);
+    close(fd);
+    if (!got) return NISQA_WAV_ERR_READ;
+    const int rc = nqff::index_region(frame_tables(), dst, (uint32_t)pl->region_bytes, pl->bits, pl->channels, pl->block_size, pl->n_frames,
+                                      pl->n_samples, clip, rows);
+    return rc == nqff::INDEX_OK ? NISQA_WAV_OK : rc == nqff::INDEX_MISSING ? NISQA_WAV_ERR_READ : NISQA_WAV_ERR_FORMAT;
+}
+
 // Walk the RIFF (or RF64, or big-endian RIFX) chunks like soundfile/libsndfile does for the cases lb.load meets: 'fmt ' (PCM, IEEE float,
 // WAVE_FORMAT_EXTENSIBLE with the sub-format in the GUID's first two bytes) then 'data'; other chunks are skipped
 // (word-aligned); a data size of 0xFFFFFFFF or one that overruns the file means "to end of file".
@@ -314,4 +372,30 @@ extern "C" int nisqa_ingest_read(const char* const* paths, int32_t n, nisqa_wav_
 extern "C" int nisqa_ingest_decode_flac(const char* path, const nisqa_wav_info* info, int32_t* dst) {
     if (!path || !info || !dst || info->status != NISQA_WAV_OK || info->tag != NISQA_WAV_TAG_FLAC) return NISQA_WAV_ERR_FORMAT;
     return decode_flac_file(path, info, (char*)dst, false);
+}
+
+extern "C" int nisqa_ingest_flac_plan(const char* const* paths, int32_t n, const nisqa_wav_info* info, nisqa_flac_plan* plan,
+                                      int32_t n_threads) {
+    if (n < 0 || (n > 0 && (!paths || !info || !plan))) return -1;
+    pool().run(n, thread_count(n_threads), [&](int i) { plan_flac(paths[i], info + i, plan + i); });
+    int good = 0;
+    for (int i = 0; i < n; ++i) good += plan[i].eligible != 0;
+    return good;
+}
+
+extern "C" int nisqa_ingest_flac_read(const char* const* paths, int32_t n, const nisqa_flac_plan* plan, void* dst,
+                                      const int64_t* region_off, const int64_t* table_off, const int32_t* clip_id, int32_t* status,
+                                      int32_t n_threads) {
+    if (n < 0 || (n > 0 && (!paths || !plan || !dst || !region_off || !table_off || !clip_id || !status))) return -1;
+    for (int i = 0; i < n; ++i)
+        if (region_off[i] >= 0 && (table_off[i] < 0 || (table_off[i] & 3))) return -1;
+    pool().run(n, thread_count(n_threads), [&](int i) {
+        status[i] = NISQA_WAV_OK;
+        if (region_off[i] >= 0)
+            status[i] = read_flac_region(paths[i], plan + i, (unsigned char*)dst + region_off[i],
+                                         (nisqa_flac_frame*)((char*)dst + table_off[i]), clip_id[i]);
+    });
+    int bad = 0;
+    for (int i = 0; i < n; ++i) bad += status[i] != NISQA_WAV_OK;
+    return bad;
 }

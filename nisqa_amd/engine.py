@@ -271,6 +271,7 @@ class HipNisqa(object):
         self.cnn_wb = up(row.pack_cnn(state_dict).view(np.int16)) if row.pack_cnn else None
         self._mel = {}
         self._ws = {}                      # one workspace per stream (batches may be in flight on several)
+        self._flac_ws = {}                 # the same for nisqa_flac_decode
         if self.arch >= 1:
             # StandardCNN (split 16-bit or exact-fp32 MFMA) + BiLSTM + last-step / average / max pooling (fp32 VALU in every mode)
             self.n_layers, self.n_heads = 0, 1
@@ -420,6 +421,55 @@ class HipNisqa(object):
                                        _ptr(out), self._stream())
         _lib.check(rc, 'nisqa_wav_decode')
         return out
+
+    def flac_decode(self, raw_dev, clips, frames_off, n_rows, n_samples, out_i16, out=None, ws=None):
+        """raw_dev: uint8 device tensor holding FLAC frame regions as the files have them and, from byte ``frames_off`` on, their
+        ``n_rows`` nisqa_flac_frame rows (what nisqa_ingest_flac_read writes); clips: the nisqa_flac_clip table (numpy structured array
+        of lib.FlacClip's layout; frame0 and md5_off are filled in here) -> (out, status): out an int16 (``out_i16``: mono 16-bit
+        streams only) or float32 device tensor [n_samples] with clip i at dst_off, status an int32 device tensor [n_clips + 1], all
+        zero when every frame and every MD5 held (nisqa_flac_decode).  Nothing is synchronised: the caller reads ``status`` with the
+        batch's results (ingest.check_flac_status).  The clip table is checked here on the host; the frame rows, which native code
+        wrote, are checked against it on the device."""
+        t = np.ascontiguousarray(clips, dtype=np.dtype(_lib.FlacClip)).reshape(-1).copy()
+        n_samples, n_rows, frames_off = int(n_samples), int(n_rows), int(frames_off)
+        assert raw_dev.dtype == torch.uint8 and raw_dev.is_cuda and raw_dev.is_contiguous()
+        dtype = torch.int16 if out_i16 else torch.float32
+        if out is None:
+            out = torch.empty(n_samples, dtype=dtype, device=self.device)
+        assert out.dtype == dtype and out.numel() >= n_samples and out.is_contiguous()
+        ch, bits, nf = t['channels'].astype(np.int64), t['bits'].astype(np.int64), t['n_frames'].astype(np.int64)
+        t['frame0'] = np.concatenate(([0], np.cumsum(nf[:-1]))) if len(t) else 0
+        ok = (ch >= 1) & (ch <= 2) & (bits >= 4) & (bits <= 24) & (t['channel'] >= -1) & (t['channel'] < ch) \
+            & (t['n_samples'] >= 1) & (t['n_samples'] < 2 ** 31) & (t['block_size'] >= 1) & (t['block_size'] <= 65535) \
+            & (nf == (t['n_samples'] + t['block_size'] - 1) // np.maximum(t['block_size'], 1)) \
+            & (t['src_off'] >= 0) & (t['src_off'] % 16 == 0) & (t['src_bytes'] >= 1) & (t['src_bytes'] < 2 ** 31) \
+            & (t['src_off'] + t['src_bytes'] <= raw_dev.numel()) & (t['dst_off'] >= 0) & (t['dst_off'] + t['n_samples'] <= n_samples)
+        if out_i16:
+            ok &= (bits == 16) & (ch == 1)
+        if len(t) == 0 or not ok.all() or int(nf.sum()) != n_rows or frames_off < 0 or frames_off % 4 or frames_off + 16 * n_rows > raw_dev.numel():
+            bad = t[~ok][0] if len(t) and not ok.all() else (n_rows, frames_off)
+            raise ValueError('nisqa_flac_decode: the tables are outside what the kernel takes: %r' % (bad,))
+        need_md5 = (t['md5_set'] != 0) & (not out_i16)
+        sizes = np.where(need_md5, (t['n_samples'] * ch * ((bits + 7) // 8) + 3) // 4 * 4, 0)
+        t['md5_off'] = np.cumsum(sizes) - sizes
+        md5_bytes = int(sizes.sum())
+        max_block, max_ch = int(t['block_size'].max()), int(ch.max())
+        need = self.lib.nisqa_flac_workspace_bytes(n_rows, max_block, max_ch, md5_bytes)
+        if ws is None:
+            skey = torch.cuda.current_stream(self.device).cuda_stream
+            ws = self._flac_ws.get(skey)
+            if ws is None or ws.numel() < need:
+                ws = self._flac_ws[skey] = None              # (the old one goes back to the allocator first)
+                ws = self._flac_ws[skey] = torch.empty(int(need * 1.25) + 256, dtype=torch.uint8, device=self.device)
+        status = torch.zeros(len(t) + 1, dtype=torch.int32, device=self.device)
+        host = torch.empty(t.nbytes, dtype=torch.uint8, pin_memory=True)
+        host.numpy()[...] = t.view(np.uint8)
+        dev = host.to(self.device, non_blocking=True)
+        rc = self.lib.nisqa_flac_decode(_ptr(raw_dev), raw_dev.numel(), _ptr(dev), len(t), ctypes.c_void_p(raw_dev.data_ptr() + frames_off),
+                                        n_rows, max_block, max_ch, 1 if out_i16 else 0, _ptr(out), n_samples, md5_bytes, _ptr(ws),
+                                        ws.numel(), _ptr(status), self._stream())
+        _lib.check(rc, 'nisqa_flac_decode')
+        return out, status
 
     def pcm16_to_f32(self, pcm16):
         out = torch.empty(pcm16.numel(), dtype=torch.float32, device=self.device)

@@ -15,7 +15,9 @@ bytes with a table of ``nisqa_wav_clip`` records, and ``nisqa_wav_decode`` turns
 (``group_pcm``): no Python runs per sample.  Without it (the default of ``Ingest``, and ``NISQA_HOST_DECODE=1`` in the loops) they
 are decoded by ``wavio.read_wav`` with the reference's ``lb.load`` semantics and staged as float32 through the same buffers.  FLAC
 files (lb.load reads them through the same soundfile call) are decoded by the native reader threads: mono 16-bit streams straight
-into their int16 slot, others via ``wavio``.
+into their int16 slot, others via ``wavio`` -- unless the loop also asks for ``device_flac``: then the threads only copy the frame region
+of a fixed-block-size stream (first audio frame to end of file, about half the bytes of its PCM) and index its frames, the group
+travels as a 'flac' group, and ``nisqa_flac_decode`` decodes it on the GPU, one lane per frame, every CRC and the MD5 checked there.
 """
 import ctypes
 import os
@@ -32,6 +34,9 @@ from . import wavio
 _ALIGN = 64
 _RAW_ALIGN = 16                                    # nisqa_wav_decode: every data chunk of a raw group starts on a 16-byte boundary
 WAV_CLIP = np.dtype(_lib.WavClip)                  # one row of a raw group's table (nisqa_wav_clip)
+FLAC_CLIP = np.dtype(_lib.FlacClip)                # one row of a flac group's device table (nisqa_flac_clip)
+FLAC_PLAN = np.dtype(_lib.FlacPlan)                # nisqa_flac_plan
+FLAC_FRAME = np.dtype(_lib.FlacFrame)              # nisqa_flac_frame
 _noted = set()
 
 
@@ -185,14 +190,19 @@ class Group(object):
     """Clips of one sample rate inside a staged batch.  ``kind``: 'i16' (mono PCM16 back to back), 'f32' (host-decoded float32 back to
     back) or 'raw' (data chunks as the files hold them, each on a 16-byte boundary, ``nbytes`` of them from ``offset`` on; ``clips``
     is then the nisqa_wav_clip table, a numpy structured array of dtype WAV_CLIP whose src_off counts from ``offset`` and whose dst_off
-    is the clip's sample offset in the decoded group).  ``lengths`` are frames in every kind."""
-    __slots__ = ('ids', 'lengths', 'sr', 'offset', 'nbytes', 'is_i16', 'names', 'kind', 'clips')
+    is the clip's sample offset in the decoded group).  A 'flac' group is a raw group some of whose clips are FLAC frame regions for
+    the device decoder: ``flac`` is then a dict -- 'clips' (the nisqa_flac_clip table of those clips, src_off from ``offset``),
+    'pos' (their positions in the group), 'frames_off' / 'n_rows' (the nisqa_flac_frame rows behind the clips' bytes), 'as_i16' (every
+    clip of the group is mono 16-bit: the group decodes to int16) -- and ``clips`` holds the rows of the other clips only; ``status``
+    receives the device status words when the group is decoded.  ``lengths`` are frames in every kind."""
+    __slots__ = ('ids', 'lengths', 'sr', 'offset', 'nbytes', 'is_i16', 'names', 'kind', 'clips', 'flac', 'status')
 
-    def __init__(self, ids, lengths, sr, offset, nbytes, is_i16, names=None, kind=None, clips=None):
+    def __init__(self, ids, lengths, sr, offset, nbytes, is_i16, names=None, kind=None, clips=None, flac=None):
         self.ids, self.lengths, self.sr, self.offset, self.nbytes, self.is_i16 = ids, lengths, sr, offset, nbytes, is_i16
         self.names = names
         self.kind = kind if kind is not None else ('i16' if is_i16 else 'f32')
         self.clips = clips
+        self.flac, self.status = flac, None
 
 
 class Staged(object):
@@ -269,17 +279,20 @@ class LengthAware(object):
             return rate_cost(a2, b2) - rate_cost(a, b), (sr, (a2, b2))
         return self._cut(frames, srs, order, cost, lambda pos: self.staged_bytes(frames, srs, widths, pos))
 
-    def cut_raw(self, frames, srs, widths, fast):
+    def cut_raw(self, frames, srs, widths, fast, sizes=None):
         """cut for an Ingest that stages for the device decoder: ``widths`` are the bytes per frame each clip is STAGED with
         (block_align of a verbatim data chunk, 4 of a host-decoded entry) and a clip costs what raw_bytes says, whatever shares its
         group; ``fast`` (bool per clip) marks the mono PCM16 clips, which come first within a rate so that a group of them alone
-        stays an int16 group."""
+        stays an int16 group.  ``sizes``: the staged bytes per clip where they are not frames x width (a FLAC frame region with its
+        frame table)."""
         n = len(frames)
         if n == 0:
             return []
         order = np.lexsort((np.arange(n), frames, ~np.asarray(fast, dtype=bool), srs))
-        size_l = ((frames * widths + _RAW_ALIGN - 1) // _RAW_ALIGN * _RAW_ALIGN).tolist()
-        return self._cut(frames, srs, order, lambda k, grp: (size_l[k], None), lambda pos: self.raw_bytes(frames, widths, pos))
+        size = (frames * widths if sizes is None else np.asarray(sizes, dtype=np.int64))
+        size = (size + _RAW_ALIGN - 1) // _RAW_ALIGN * _RAW_ALIGN
+        size_l = size.tolist()
+        return self._cut(frames, srs, order, lambda k, grp: (size_l[k], None), lambda pos: int(size[np.asarray(pos, dtype=np.int64)].sum()))
 
     def _cut(self, frames, srs, order, cost, total_bytes):
         """The walk both cuts share.  cost(k, state of the open batch: a dict) -> (bytes clip k adds, (key, value) to record in the
@@ -321,12 +334,15 @@ class Ingest(object):
     turns ``staged.groups`` into H2D copies out of ``ring.buf[staged.slot]`` and reports the event behind them with
     ``ring.release_after``.  Batches are prepared ``depth`` ahead on a producer thread."""
 
-    def __init__(self, ds, batches, pin, num_workers, depth=2, device=None, device_decode=False):
+    def __init__(self, ds, batches, pin, num_workers, depth=2, device=None, device_decode=False, device_flac=False):
         """``batches``: a list of index lists (staged exactly as given), or a LengthAware policy (the producer forms the
         batches itself from the headers).  ``device_decode``: a rate group that is not all mono PCM16 is staged as a 'raw' group
-        (data chunks verbatim + a nisqa_wav_clip table, decoded by group_pcm on the GPU) instead of being decoded here."""
+        (data chunks verbatim + a nisqa_wav_clip table, decoded by group_pcm on the GPU) instead of being decoded here.
+        ``device_flac`` (with device_decode): a FLAC stream nisqa_ingest_flac_plan finds eligible is staged as its frame region
+        and frame table and decoded by nisqa_flac_decode; without it FLAC files are decoded by the reader threads."""
         self.ds, self.batches = ds, batches
         self.device_decode = bool(device_decode)
+        self.device_flac = bool(device_flac) and self.device_decode
         self.device = device
         self.ring = _take_ring(depth + 1, pin)
         # reader threads: what the caller asked for, but never more than the CPU budget leaves next to the producer and
@@ -397,26 +413,77 @@ class Ingest(object):
         if rc:
             bad = next(k for k in range(n) if infos[k].status != _lib.WAV_OK)
             raise ValueError('Could not load file {}'.format(names[bad]))      # NISQA_lib.py:2305-2306
-        return names, enc, np.ctypeslib.as_array(infos).copy()
+        info = np.ctypeslib.as_array(infos).copy()
+        return names, enc, info, self._plan_flac(enc, info)
+
+    def _plan_flac(self, enc, info):
+        """nisqa_flac_plan records of the probed files (numpy structured array of lib.FlacPlan), or None when the device FLAC
+        decoder is not asked for or no file is a FLAC stream (an all-WAV job plans nothing)."""
+        if not self.device_flac:
+            return None
+        sel = np.flatnonzero(info['tag'] == _lib.WAV_TAG_FLAC)
+        if len(sel) == 0:
+            return None
+        plans = np.zeros(len(info), dtype=FLAC_PLAN)
+        sub_info = np.ascontiguousarray(info[sel])
+        sub = np.zeros(len(sel), dtype=FLAC_PLAN)
+        paths = (ctypes.c_char_p * len(sel))(*[enc[k] for k in sel.tolist()])
+        for s0 in range(0, len(sel), 1024):                          # (in chunks: the native pool runs one job at a time, see _probe)
+            m = min(1024, len(sel) - s0)
+            rc = self.lib.nisqa_ingest_flac_plan(
+                ctypes.cast(ctypes.byref(paths, s0 * ctypes.sizeof(ctypes.c_char_p)), ctypes.POINTER(ctypes.c_char_p)), m,
+                ctypes.cast(sub_info.ctypes.data + s0 * sub_info.itemsize, ctypes.POINTER(_lib.WavInfo)),
+                ctypes.cast(sub.ctypes.data + s0 * sub.itemsize, ctypes.POINTER(_lib.FlacPlan)), self.workers)
+            if rc < 0:
+                raise RuntimeError('nisqa_ingest_flac_plan failed')
+        plans[sel] = sub
+        return plans
 
     def _stage(self, idx, probed=None):
-        """Stage one batch: layout from the headers, then every data chunk straight into a page-locked slot."""
+        """Stage one batch: layout from the headers, then every data chunk straight into a page-locked slot.  A FLAC stream whose
+        frames the readers cannot index (nisqa_ingest_flac_read refuses it) sends the batch round again with that file on the host
+        path: the host decoder then accepts it or raises the reference's error."""
+        names, enc, info, plans = probed if probed is not None else self._probe(idx)
+        info = np.ascontiguousarray(info)
+        plans = None if plans is None else np.ascontiguousarray(plans).copy()
+        while True:
+            st = self._stage_once(idx, names, enc, info, plans)
+            if st is not None:
+                return st
+
+    def _stage_once(self, idx, names, enc, info, plans):
         ds, L, n = self.ds, self.lib, len(idx)
         T = self.stats
-        names, enc, info = probed if probed is not None else self._probe(idx)
         t2 = time.perf_counter()
         paths = (ctypes.c_char_p * n)(*enc)
-        info = np.ascontiguousarray(info)
         infos = ctypes.cast(info.ctypes.data, ctypes.POINTER(_lib.WavInfo))
         frames, srs = info['n_frames'], info['sample_rate']
         fast = _verbatim_i16(info)
         widths, verbatim = self._staged_widths(info) if self.device_decode else (None, None)
+        dev_flac = np.zeros(n, dtype=bool) if plans is None else (plans['eligible'] != 0) & self._flac_takes(info)
         # batch layout from the headers alone: clips of one rate are contiguous, int16 if ALL of them are mono PCM16
         layout, total = [], 0
         dst_off = np.full(n, -1, dtype=np.int64)
+        region_off, table_off = np.full(n, -1, dtype=np.int64), np.zeros(n, dtype=np.int64)
+        clip_id = np.zeros(n, dtype=np.int32)
         for sr in dict.fromkeys(srs.tolist()):
             sel = np.flatnonzero(srs == sr)
             is_i16 = bool(fast[sel].all())
+            fl = dev_flac[sel]
+            if fl.any():                                            # flac group: a raw group + frame regions + their frame rows
+                size = np.where(fl, plans['region_bytes'][sel], frames[sel] * widths[sel])
+                padded = (size + _RAW_ALIGN - 1) // _RAW_ALIGN * _RAW_ALIGN
+                off = total + np.concatenate(([0], np.cumsum(padded[:-1])))
+                rows = np.where(fl, plans['n_frames'][sel], 0).astype(np.int64)
+                tab = total + int(padded.sum())
+                nbytes = int(padded.sum()) + FLAC_FRAME.itemsize * int(rows.sum())
+                dst_off[sel] = np.where(verbatim[sel] & ~fl, off, -1)
+                region_off[sel] = np.where(fl, off, -1)
+                table_off[sel] = tab + FLAC_FRAME.itemsize * (np.cumsum(rows) - rows)
+                clip_id[sel] = np.cumsum(fl) - 1
+                layout.append((int(sr), sel, 'flac', off, nbytes))
+                total = (total + nbytes + _ALIGN - 1) // _ALIGN * _ALIGN
+                continue
             if self.device_decode and not is_i16:                   # raw group: every clip at its own width, on a 16-byte boundary
                 size = frames[sel] * widths[sel]
                 padded = (size + _RAW_ALIGN - 1) // _RAW_ALIGN * _RAW_ALIGN      # (the last clip's pad is the tail pad of the group)
@@ -441,6 +508,20 @@ class Ingest(object):
         T['slot_wait'] += t4 - t3
         rc = L.nisqa_ingest_read(paths, n, infos, ctypes.c_void_p(buf.data_ptr()),
                                  dst_off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)), self.workers)
+        if dev_flac.any() and not rc:
+            status = np.zeros(n, dtype=np.int32)
+            bad = L.nisqa_ingest_flac_read(paths, n, ctypes.cast(plans.ctypes.data, ctypes.POINTER(_lib.FlacPlan)),
+                                           ctypes.c_void_p(buf.data_ptr()), region_off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                           table_off.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                           clip_id.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                                           status.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), self.workers)
+            if bad:                                                 # these files take the host path: lay the batch out again
+                T['read'] += time.perf_counter() - t4
+                self.ring.release_after(slot, None)
+                if bad < 0:
+                    raise RuntimeError('nisqa_ingest_flac_read failed')
+                plans['eligible'][status != 0] = 0
+                return None
         T['read'] += time.perf_counter() - t4
         T['batches'] += 1
         if rc:
@@ -450,11 +531,11 @@ class Ingest(object):
         groups = []
         raw = None
         for sr, sel, kind, off, nbytes in layout:
-            clips = None
+            clips = flac = None
             if kind != 'i16':                                       # stereo / 8, 24, 32-bit / float: host decode ...
                 raw = buf.numpy() if raw is None else raw
                 for k, o in zip(sel.tolist(), off.tolist()):
-                    if dst_off[k] >= 0:                             # ... unless the data chunk went in verbatim (raw group)
+                    if dst_off[k] >= 0 or region_off[k] >= 0:       # ... unless the data chunk / frame region went in verbatim
                         continue
                     y, _ = wavio.read_wav(names[k], ds.ms_channel)
                     if y.dtype == np.int16:
@@ -462,9 +543,33 @@ class Ingest(object):
                     raw[o:o + 4 * len(y)].view(np.float32)[:] = y
             if kind == 'raw':
                 clips = self._clip_table(info[sel], verbatim[sel], off - int(off[0]))
+            elif kind == 'flac':
+                fl = dev_flac[sel]
+                dst = np.concatenate(([0], np.cumsum(frames[sel][:-1])))
+                clips = self._clip_table(info[sel], verbatim[sel], off - int(off[0]))[~fl]
+                flac = {'clips': self._flac_table(plans[sel][fl], (off - int(off[0]))[fl], dst[fl]), 'pos': np.flatnonzero(fl),
+                        'frames_off': int(table_off[sel][0]) - int(off[0]), 'n_rows': int(plans['n_frames'][sel][fl].sum()),
+                        'as_i16': bool(fast[sel].all())}
             groups.append(Group([idx[k] for k in sel.tolist()], frames[sel].tolist(), sr, int(off[0]) if len(off) else 0,
-                                nbytes, kind == 'i16', [names[k] for k in sel.tolist()], kind, clips))
+                                nbytes, kind == 'i16', [names[k] for k in sel.tolist()], kind, clips, flac))
         return Staged(slot, groups)
+
+    def _flac_takes(self, info):
+        """Which FLAC files the device decoder can serve for this dataset: an ms_channel the stream does not have stays with the host
+        decoder, which raises the reference's error for it."""
+        sel = getattr(self.ds, 'ms_channel', None)
+        ch = info['channels']
+        return (info['tag'] == _lib.WAV_TAG_FLAC) & ((ch == 1) | (ch == 2) & (True if sel is None else (0 <= int(sel) < 2)))
+
+    def _flac_table(self, plans, src_off, dst_off):
+        """nisqa_flac_clip rows of a flac group's device-decoded streams (frame0 and md5_off are the engine's)."""
+        t = np.zeros(len(plans), dtype=FLAC_CLIP)
+        sel = getattr(self.ds, 'ms_channel', None)
+        t['src_off'], t['src_bytes'], t['dst_off'], t['n_samples'] = src_off, plans['region_bytes'], dst_off, plans['n_samples']
+        for f in ('n_frames', 'block_size', 'bits', 'channels', 'md5_set', 'md5'):
+            t[f] = plans[f]
+        t['channel'] = -1 if sel is None else np.where(plans['channels'] > 1, int(sel), 0)
+        return t
 
     def _staged_widths(self, info):
         """Device decode: (bytes per frame each file is staged with, which files nisqa_ingest_read puts into the slot itself).  A WAV
@@ -515,16 +620,21 @@ class Ingest(object):
                 if self.stop.is_set():
                     box[w] = ('stop', None, loc)
                     return
-                names, enc, info = self._probe(wins[w], loc, chunk=None if w == 0 else 1024)    # (w >= 1: in the background, under window w - 1's staging)
+                names, enc, info, plans = self._probe(wins[w], loc, chunk=None if w == 0 else 1024)    # (w >= 1: in the background, under window w - 1's staging)
                 # the window's batches are cut HERE, on the helper thread: sorting and walking 16 384 items in Python is
                 # 10-20 ms during which the producer staged nothing and the link ran dry once per window
                 fast = _verbatim_i16(info)
                 if self.device_decode:                                  # the byte cap is charged with the staged widths
+                    sizes = None
+                    if plans is not None:                               # (a frame region with its frame rows: what is staged for it)
+                        dev = (plans['eligible'] != 0) & self._flac_takes(info)
+                        sizes = np.where(dev, plans['region_bytes'] + FLAC_FRAME.itemsize * plans['n_frames'].astype(np.int64),
+                                         info['n_frames'].astype(np.int64) * self._staged_widths(info)[0])
                     cuts = pol.cut_raw(info['n_frames'].astype(np.int64), info['sample_rate'].astype(np.int64),
-                                       self._staged_widths(info)[0], fast)
+                                       self._staged_widths(info)[0], fast, sizes)
                 else:
                     cuts = pol.cut(info['n_frames'].astype(np.int64), info['sample_rate'].astype(np.int64), np.where(fast, 2, 4))
-                box[w] = ('ok', (names, enc, info, cuts), loc)
+                box[w] = ('ok', (names, enc, info, cuts, plans), loc)
             except BaseException as e:
                 box[w] = ('err', e, loc)
 
@@ -547,9 +657,9 @@ class Ingest(object):
                 helper.start()
             else:
                 helper = None
-            names, enc, info, cuts = val
+            names, enc, info, cuts, plans = val
             for pos in cuts:
-                yield [wins[w][k] for k in pos], ([names[k] for k in pos], [enc[k] for k in pos], info[pos])
+                yield [wins[w][k] for k in pos], ([names[k] for k in pos], [enc[k] for k in pos], info[pos], None if plans is None else plans[pos])
 
     def _produce(self):
         try:
@@ -606,11 +716,18 @@ def device_decode_default():
     return os.environ.get('NISQA_HOST_DECODE') != '1'
 
 
+def device_flac_default():
+    """Whether the loops also stage FLAC streams for the device decoder (nisqa_flac_decode): yes, unless NISQA_HOST_FLAC=1 (the
+    reader threads decode FLAC, as before: the A/B switch and the cross-check) or NISQA_HOST_DECODE=1 asks for host decoding
+    altogether."""
+    return os.environ.get('NISQA_HOST_FLAC') != '1' and device_decode_default()
+
+
 def copy_group(buf, g, device):
     """H2D copy of group ``g`` out of the ring buffer ``buf`` (on the current stream): int16 / float32 samples, or the bytes of a raw
-    group."""
+    or flac group."""
     host = buf[g.offset:g.offset + g.nbytes]
-    if g.kind != 'raw':
+    if g.kind not in ('raw', 'flac'):
         host = host.view(torch.int16 if g.kind == 'i16' else torch.float32)
     return host.to(device, non_blocking=True)
 
@@ -618,12 +735,49 @@ def copy_group(buf, g, device):
 def decode_group(x, g, eng):
     """The device PCM of group ``g`` from what copy_group sent (on the current stream): int16 and float32 groups as they are, a raw
     group through nisqa_wav_decode -> float32 [sum of lengths]."""
+    if g.kind == 'flac':
+        f, total = g.flac, int(sum(g.lengths))
+        if f['as_i16']:                                              # every clip mono 16-bit: the int16 entry's form
+            out = torch.empty(total, dtype=torch.int16, device=x.device)
+            for row in g.clips:                                      # (mono PCM16 data chunks next to the streams: in place)
+                a, d, m = int(row['src_off']), int(row['dst_off']), int(row['n_frames'])
+                out[d:d + m].copy_(x[a:a + 2 * m].view(torch.int16))
+        else:
+            out = torch.empty(total, dtype=torch.float32, device=x.device)
+            if len(g.clips):
+                eng.decode(x, g.clips, total, out=out)
+        out, g.status = eng.flac_decode(x, f['clips'], f['frames_off'], f['n_rows'], total, f['as_i16'], out=out)
+        return out
     if g.kind != 'raw':
         return x
     return eng.decode(x, g.clips, int(sum(g.lengths)))
 
 
-def group_pcm(buf, g, eng):
+def check_flac_status(g, status, ms_channel=None):
+    """The status words nisqa_flac_decode left for group ``g`` (host array, [clips + 1]): nothing when all are zero.  For a flagged
+    stream the host decoder is asked: if it refuses the file too this is the reference's unreadable file; if it accepts, the device
+    decoder misread a stream or the frame index hit a false sync -- an error either way, never different audio."""
+    if g.kind != 'flac' or status is None:
+        return
+    status = np.asarray(status).reshape(-1)
+    if not status.any():
+        return
+    if status[-1]:
+        raise RuntimeError('nisqa_flac_decode: a frame table row names no clip (status 0x%x)' % int(status[-1]))
+    k = int(np.flatnonzero(status)[0])
+    name = g.names[int(g.flac['pos'][k])]
+    try:
+        wavio.read_wav(name, ms_channel)
+    except Exception:
+        raise ValueError('Could not load file {}'.format(name))      # NISQA_lib.py:2305-2306
+    raise RuntimeError('nisqa_flac_decode refused {} (status 0x{:x}) but the host decoder reads it: a decoder bug or a false frame '
+                       'sync; NISQA_HOST_FLAC=1 decodes FLAC on the host'.format(name, int(status[k])))
+
+
+def group_pcm(buf, g, eng, ms_channel=None):
     """(ring buffer, Group, engine) -> the group's PCM on the engine's device: int16 for an 'i16' group, float32 for an 'f32' group,
     copy + decode for a 'raw' one.  (A loop that copies and computes on different streams calls the two halves itself.)"""
-    return decode_group(copy_group(buf, g, eng.device), g, eng)
+    out = decode_group(copy_group(buf, g, eng.device), g, eng)
+    if g.kind == 'flac':                                             # (this convenience form waits for the words; the predict loop does not)
+        check_flac_status(g, g.status.cpu().numpy(), ms_channel)
+    return out

@@ -39,6 +39,19 @@ class WavClip(ctypes.Structure):
                 ('encoding', c_i32), ('channel', c_i32)]
 
 
+class FlacClip(ctypes.Structure):
+    """nisqa_flac_clip"""
+    _fields_ = [('src_off', c_i64), ('src_bytes', c_i64), ('dst_off', c_i64), ('n_samples', c_i64), ('md5_off', c_i64),
+                ('frame0', c_i32), ('n_frames', c_i32), ('block_size', c_i32), ('bits', c_i32), ('channels', c_i32),
+                ('channel', c_i32), ('md5_set', c_i32), ('reserved', c_i32), ('md5', ctypes.c_uint8 * 16)]
+
+
+class FlacFrame(ctypes.Structure):
+    """nisqa_flac_frame (both headers)"""
+    _fields_ = [('offset', c_i32), ('first_sample', c_i32), ('block_size', c_i32), ('clip', c_i32)]
+
+
+FLAC_BAD_MD5, FLAC_BAD_TABLE = 0x80, 0x100              # NISQA_FLAC_BAD_*; 1 << k below them: the frame check k that failed
 WAVENC_PCM, WAVENC_FLOAT, WAVENC_ALAW, WAVENC_MULAW, WAVENC_BIG_ENDIAN = 1, 3, 6, 7, 0x10000      # NISQA_WAVENC_*
 WAV_DECODE_MAX_BLOCK, WAV_DECODE_MAX_MEAN = 1024, 32     # nisqa_wav_decode's limits: channels * container, channels of a mean
 
@@ -87,6 +100,9 @@ SYMBOLS = {
                                                  ctypes.POINTER(ModelDev), c_p, ctypes.c_size_t, c_p, c_p]),
     'nisqa_pcm16_to_f32': (ctypes.c_int, [c_p, c_p, c_i64, c_p]),
     'nisqa_wav_decode': (ctypes.c_int, [c_p, c_i64, c_p, c_i32, c_i64, c_p, c_p]),
+    'nisqa_flac_workspace_bytes': (ctypes.c_size_t, [c_i32, c_i32, c_i32, c_i64]),
+    'nisqa_flac_decode': (ctypes.c_int, [c_p, c_i64, c_p, c_i32, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_i64, c_i64, c_p,
+                                         ctypes.c_size_t, c_p, c_p]),
     'nisqa_resample_workspace_bytes': (ctypes.c_size_t, [c_i32, c_i64]),
     'nisqa_resample': (ctypes.c_int, [c_p, c_i32, c_p, c_p, c_p, c_i32, c_i64, ctypes.c_double, c_p, c_i32, c_i32, c_p, ctypes.c_size_t, c_p, c_p]),
     'nisqa_de_align_fuse': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p]),
@@ -246,12 +262,23 @@ class WavInfo(ctypes.Structure):
                 ('sample_rate', c_i32), ('data_offset', c_i64), ('n_frames', c_i64)]
 
 
+class FlacPlan(ctypes.Structure):
+    """nisqa_flac_plan"""
+    _fields_ = [('eligible', c_i32), ('n_frames', c_i32), ('region_off', c_i64), ('region_bytes', c_i64), ('n_samples', c_i64),
+                ('block_size', c_i32), ('bits', c_i32), ('channels', c_i32), ('md5_set', c_i32), ('md5', ctypes.c_uint8 * 16)]
+
+
 INGEST_SYMBOLS = {
     'nisqa_ingest_abi_version': (ctypes.c_int, []),
     'nisqa_ingest_probe': (ctypes.c_int, [ctypes.POINTER(ctypes.c_char_p), c_i32, ctypes.POINTER(WavInfo), c_i32]),
     'nisqa_ingest_read': (ctypes.c_int, [ctypes.POINTER(ctypes.c_char_p), c_i32, ctypes.POINTER(WavInfo), c_p,
                                          ctypes.POINTER(c_i64), c_i32]),
     'nisqa_ingest_decode_flac': (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(WavInfo), c_p]),
+    'nisqa_ingest_flac_plan': (ctypes.c_int, [ctypes.POINTER(ctypes.c_char_p), c_i32, ctypes.POINTER(WavInfo), ctypes.POINTER(FlacPlan),
+                                              c_i32]),
+    'nisqa_ingest_flac_read': (ctypes.c_int, [ctypes.POINTER(ctypes.c_char_p), c_i32, ctypes.POINTER(FlacPlan), c_p,
+                                              ctypes.POINTER(c_i64), ctypes.POINTER(c_i64), ctypes.POINTER(c_i32),
+                                              ctypes.POINTER(c_i32), c_i32]),
 }
 
 _ingest = None

@@ -245,7 +245,8 @@ def train(nm):
 
         ing = None if a['double_ended'] else _ingest.Ingest(
             nm.ds_train, batches, pin=True, num_workers=a['tr_num_workers'],
-            device_decode=_ingest.device_decode_default())                # (NISQA_HOST_DECODE=1: decode on the staging thread)
+            device_decode=_ingest.device_decode_default(),                # (NISQA_HOST_DECODE=1: decode on the staging thread)
+            device_flac=_ingest.device_flac_default())                    # (NISQA_HOST_FLAC=1: FLAC on the reader threads)
         try:
             for b in (batches if ing is None else ()):                   # pairs: both files of every row, the two sides in row order
                 ids, g_deg, g_ref = stage_pairs(tr, nm.ds_train, b)
@@ -254,7 +255,8 @@ def train(nm):
                 # one group per sample rate in the batch (the reference loads every file at its own rate, NISQA_lib.py:2299-2310):
                 # train-mode BatchNorm spans the batch, so the groups stay ONE step -- only the spectrogram is per group
                 raw = ing.ring.buf[staged.slot]
-                pcms = [_ingest.group_pcm(raw, g, tr.eng) for g in staged.groups]     # (a raw group: copy + nisqa_wav_decode)
+                pcms = [_ingest.group_pcm(raw, g, tr.eng, getattr(nm.ds_train, 'ms_channel', None))
+                        for g in staged.groups]                          # (a raw group: copy + nisqa_wav_decode; a flac group: + nisqa_flac_decode)
                 ev = torch.cuda.Event()
                 ev.record()                                              # behind the last group's copy
                 ing.ring.release_after(staged.slot, ev)

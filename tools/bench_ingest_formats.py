@@ -1,12 +1,15 @@
 """File-fed predict rate per input format: nisqaModel(predict_dir, bs 64).predict() over a directory of hard links to 64 ten-second
 files, as bench.py's side.predict_dir_bs64 runs it, for mono PCM16 (the control), stereo PCM16, mono / stereo PCM24, mono float32 and
-mu-law at 8 kHz.  Per leg: clips/s, the bytes one clip puts on the host link, and the fraction of what the link alone carries
+mu-law at 8 kHz, and for FLAC streams (flac16, flac16x2, flac24: written by tests/flac_enc.py, a few seconds per file, so only four
+distinct files each; linked under *.wav names because predict_dir lists *.wav -- the ingest goes by the file's magic).  Per leg: clips/s, the bytes one clip puts on the host link, and the fraction of what the link alone carries
 (bench.link_only_probe: the loop's own transport with no loop around it).
 
-    python tools/bench_ingest_formats.py [--clips 8192] [--runs 3] [--formats pcm16,pcm24x2] [--host-decode]
+    python tools/bench_ingest_formats.py [--clips 8192] [--runs 3] [--formats pcm16,pcm24x2] [--host-decode] [--host-flac]
 
 --host-decode sets NISQA_HOST_DECODE=1: the staging thread decodes what is not mono PCM16 (what every commit before the device
-decoder did; use a small --clips, it is a Python thread decoding ten-second clips one at a time).  Not a test: DESIGN.md 6.3."""
+decoder did; use a small --clips, it is a Python thread decoding ten-second clips one at a time).  --host-flac sets NISQA_HOST_FLAC=1:
+the reader threads decode FLAC (the A/B of nisqa_flac_decode; --alternate N runs device and host N times each, in turn, in one
+process).  Not a test: DESIGN.md 6.3."""
 import argparse
 import contextlib
 import io
@@ -29,7 +32,8 @@ from nisqa_amd import synth                              # noqa: E402
 SECONDS = 10.0
 # name -> (format tag, channels, container bytes, bits, sample rate)
 FORMATS = {'pcm16': (1, 1, 2, 16, 48000), 'pcm16x2': (1, 2, 2, 16, 48000), 'pcm24': (1, 1, 3, 24, 48000), 'pcm24x2': (1, 2, 3, 24, 48000),
-           'f32': (3, 1, 4, 32, 48000), 'mulaw8k': (7, 1, 1, 8, 8000)}
+           'f32': (3, 1, 4, 32, 48000), 'mulaw8k': (7, 1, 1, 8, 8000),
+           'flac16': ('flac', 1, 2, 16, 48000), 'flac16x2': ('flac', 2, 2, 16, 48000), 'flac24': ('flac', 1, 3, 24, 48000)}
 
 
 def _mulaw(pcm16):
@@ -46,6 +50,15 @@ def write_file(path, seed, fmt):
     tag, ch, cont, bits, sr = FORMATS[fmt]
     chans = [synth.synth_pcm16(seed + 1000 * c, SECONDS, sr=sr) for c in range(ch)]
     x = np.stack(chans, 1)                                  # int16 [n, ch]
+    if tag == 'flac':                                       # fixed block size 4096, LPC 8 / 12: what a stock encoder writes
+        sys.path.insert(0, os.path.join(ROOT, 'tests'))
+        import flac_enc
+        v = x.astype(np.int64) if bits == 16 else (x.astype(np.int64) << 8) | ((x.astype(np.int64) * 37) & 0xFF)
+        data = flac_enc.encode(v[:, 0] if ch == 1 else v, sr, bits, blocksize=4096, stereo=10,
+                               kinds={'type': 'lpc', 'order': 8, 'precision': 12, 'porder': 4})
+        with open(path, 'wb') as f:
+            f.write(data)
+        return len(data)
     if tag == 7:
         data = _mulaw(x).tobytes()
     elif tag == 3:
@@ -70,6 +83,8 @@ def run_leg(fmt, clips, runs, dev, tmp_dir, bs=64, distinct=64, warm=4):
     shutil.rmtree(d, ignore_errors=True)
     os.makedirs(os.path.join(d, 'dir'))
     os.makedirs(os.path.join(d, 'warm'))
+    if FORMATS[fmt][0] == 'flac':
+        distinct = min(distinct, 4)
     nbytes = [write_file(os.path.join(d, 'c%03d.wav' % i), 3000 + i, fmt) for i in range(distinct)]
     for sub, n in (('dir', clips), ('warm', warm * bs)):
         for i in range(n):
@@ -109,20 +124,28 @@ def main():
     ap.add_argument('--runs', type=int, default=3)
     ap.add_argument('--formats', default=','.join(FORMATS))
     ap.add_argument('--host-decode', action='store_true')
+    ap.add_argument('--host-flac', action='store_true')
     ap.add_argument('--tmp-dir', default=None)
     a = ap.parse_args()
     if a.host_decode:
         os.environ['NISQA_HOST_DECODE'] = '1'
     else:
         os.environ.pop('NISQA_HOST_DECODE', None)
+    if a.host_flac:
+        os.environ['NISQA_HOST_FLAC'] = '1'
+    else:
+        os.environ.pop('NISQA_HOST_FLAC', None)
     dev = torch.device('cuda', 0)
     link = bench.link_only_probe(dev)
     for fmt in a.formats.split(','):
         rates, per_clip, loop = run_leg(fmt, a.clips, a.runs, dev, a.tmp_dir)
-        host_decoded = a.host_decode and fmt != 'pcm16'
+        is_flac = FORMATS[fmt][0] == 'flac'
+        host_decoded = (a.host_decode and fmt != 'pcm16') or (is_flac and a.host_flac and fmt != 'flac16')
+        if is_flac and (a.host_flac or a.host_decode):      # host-decoded mono 16-bit FLAC crosses as int16
+            per_clip = FORMATS[fmt][4] * SECONDS * 2
         link_bytes = FORMATS[fmt][4] * SECONDS * 4 if host_decoded else per_clip         # a host-decoded clip crosses as float32
         best = max(rates)
-        print(json.dumps({'format': fmt, 'decode': 'host' if a.host_decode else 'device', 'clips': a.clips,
+        print(json.dumps({'format': fmt, 'decode': 'host' if a.host_decode or (is_flac and a.host_flac) else 'device', 'clips': a.clips,
                           'clips_per_s': [round(r, 1) for r in rates], 'link_bytes_per_clip': int(link_bytes),
                           'link_only_GBps': round(link, 2), 'link_only_clips_per_s': round(link * 1e9 / link_bytes, 1),
                           'frac_of_link_only': round(best * link_bytes / (link * 1e9), 4),
