@@ -381,6 +381,27 @@ int nisqa_de_align_fuse_bwd(const float* d_fused, int32_t ld, const int32_t* idx
                             const int32_t* deg_n_wins, const int32_t* ref_tok_off, const int32_t* ref_n_wins, int32_t n_pairs,
                             int32_t max_n_wins, int32_t fuse, float* d_deg, float* d_ref, void* stream);
 
+/* ---- resident training spectrograms (tr_ds_to_memory): one batch out of the store --------------------------------------------
+ * The store (nisqa_amd/melstore.py) keeps the dB spectrogram of every clip of a dataset in ONE device arena, store
+ * [store_rows][48] float32, clip after clip: clip i's rows are clip_row[i] .. clip_row[i + 1] - 1 (clip_row [n_store + 1], int64,
+ * an exclusive prefix sum; clip_row[n_store] = store_rows) and store_floor[i] is its top_db floor.  nisqa_mel_gather copies the n
+ * clips ids[0 .. n-1] (any order, repeats allowed) into out_mel [out_frames][48]: clip ids[c] to the rows out_frame_off[c] ..
+ * out_frame_off[c + 1] - 1 (out_frame_off [n + 1], int32, an exclusive prefix sum of the clips' stored lengths; out_frame_off[n]
+ * = out_frames), and writes out_floor[c] = store_floor[ids[c]].  Every pointer is device memory; store and out_mel are 16-byte
+ * aligned (a row is 192 B = twelve 16-byte units; the copy moves whole units).  One launch on `stream`, no workspace.
+ *
+ * Returns NISQA_ERR_ARG before any launch for a NULL pointer, a store or out_mel that is not 16-byte aligned, n <= 0,
+ * n_store <= 0, out_frames <= 0 or store_rows <= 0.  The tables themselves are the caller's to check (melstore.MelStore.batch does,
+ * on the host).  On the device an entry is skipped, not trusted, if its id is outside [0, n_store), if its output span is not
+ * exactly the stored length, or if its stored rows leave [0, store_rows): its output rows are left unwritten and its floor is set
+ * to NaN; every other entry is copied exactly.  No address outside [store, store + store_rows * 48) or outside out_mel
+ * [out_frames][48] / out_floor [n] is ever formed.  The offsets of at most NISQA_MEL_GATHER_LDS_CLIPS clips are staged in LDS; a
+ * longer list is searched in global memory.  Bitwise copies: no arithmetic, no atomics. */
+#define NISQA_MEL_GATHER_LDS_CLIPS 1024
+int nisqa_mel_gather(const float* store, int64_t store_rows, const int64_t* clip_row, const float* store_floor, int32_t n_store,
+                     const int32_t* ids, const int32_t* out_frame_off, int32_t n, int32_t out_frames, float* out_mel,
+                     float* out_floor, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

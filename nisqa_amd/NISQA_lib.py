@@ -287,7 +287,14 @@ class NISQA_DE(nn.Module):
 # ---------------------------------------------------------------------------------------------
 class SpeechQualityDataset(object):
     """File table of the reference dataset (NL:2052-2236).  Same constructor arguments; loading a
-    waveform replaces ``_load_spec`` (the spectrogram itself is produced on the GPU)."""
+    waveform replaces ``_load_spec`` (the spectrogram itself is produced on the GPU).
+
+    ``to_memory`` (the recipes' tr_ds_to_memory) is kept as ``self.to_memory``; no work is done at construction, because the
+    engine does not exist yet: ``nisqaModel.load_to_memory()`` (called by ``train()``) computes every spectrogram once on the
+    GPU and keeps them in device memory (``self.store``, and ``self.ref_store`` over the reference files of a double-ended
+    set: melstore.MelStore).  From then on the training loop, the validation pass and ``__getitem__`` read no file; edits to
+    the files or to the filename column are not seen, as in the reference (NL:2105-2127).  ``to_memory_workers`` stays accepted
+    and unused: the fill is one GPU pass, not a pool of loader processes."""
 
     def __init__(self, df, df_con=None, data_dir='', folder_column='', filename_column='filename', mos_column='MOS',
                  seg_length=15, max_length=None, to_memory=False, to_memory_workers=0, transform=None,
@@ -304,6 +311,8 @@ class SpeechQualityDataset(object):
         self.ms_n_mels, self.ms_sr, self.ms_fmax, self.ms_channel = ms_n_mels, ms_sr, ms_fmax, ms_channel
         self.dim = dim
         self.double_ended, self.filename_column_ref = bool(double_ended), filename_column_ref
+        self.to_memory = bool(to_memory)
+        self.store = self.ref_store = None                         # melstore.MelStore once load_to_memory has run
 
     def ref_view(self):
         """The same table with the reference files as its file column (double-ended datasets): the readers and the header probe
@@ -311,6 +320,7 @@ class SpeechQualityDataset(object):
         v = object.__new__(type(self))
         v.__dict__.update(self.__dict__)
         v.filename_column, v.double_ended = self.filename_column_ref, False
+        v.store, v.ref_store = self.ref_store, None
         return v
 
     def __len__(self):
@@ -342,7 +352,7 @@ class SpeechQualityDataset(object):
         A double-ended dataset gives (x [max_length,2,n_mels,seg_length], y, (index, [n_wins_deg, n_wins_ref])) like NL:2170-2214:
         channel 0 the degraded file's segments, channel 1 the reference file's, both from the HIP front end."""
         assert isinstance(index, int), 'index must be integer (no slice)'
-        if getattr(self, '_engine_factory', None) is None:
+        if getattr(self, '_engine_factory', None) is None and not (self.store is not None and self.store.filled):
             raise RuntimeError('SpeechQualityDataset item access needs bind_engine(...) (spectrograms are computed on the GPU)')
         if self.double_ended:
             (xd, y, (_, nd)), (xr, _, (_, nr)) = self._item(index), self.ref_view()._item(index)
@@ -354,15 +364,18 @@ class SpeechQualityDataset(object):
 
     def _item(self, index):
         """the single-ended item of this dataset's file column"""
-        eng = self._engine_factory()
-        if hasattr(eng, 'base'):                                   # HipNisqaDE: mel, resampling and plans are its single-ended engine's
-            eng = eng.base
-        y, sr = self.load_audio(index)
-        plan = eng.audio_plan([len(y)], sr, names=[self.file_path(index)])
-        pcm = eng.resample(torch.from_numpy(y).to(eng.device), [len(y)], sr)          # (ms_sr: lb.load resamples first, NL:2300-2304)
-        mel, _ = eng.mel(pcm, plan, eng.rate(sr), clamp=True)                         # int16 PCM or float32 samples
-        spec = mel.cpu().numpy()                                   # [T, n_mels]
-        n_wins = int(plan.n_wins[0])
+        if self.store is not None and self.store.filled:           # resident (to_memory): served from the store, NL:2165
+            spec, n_wins = self.store.item(index)
+        else:
+            eng = self._engine_factory()
+            if hasattr(eng, 'base'):                               # HipNisqaDE: mel, resampling and plans are its single-ended engine's
+                eng = eng.base
+            y, sr = self.load_audio(index)
+            plan = eng.audio_plan([len(y)], sr, names=[self.file_path(index)])
+            pcm = eng.resample(torch.from_numpy(y).to(eng.device), [len(y)], sr)      # (ms_sr: lb.load resamples first, NL:2300-2304)
+            mel, _ = eng.mel(pcm, plan, eng.rate(sr), clamp=True)                     # int16 PCM or float32 samples
+            spec = mel.cpu().numpy()                               # [T, n_mels]
+            n_wins = int(plan.n_wins[0])
         idx = self.seg_hop_length * np.arange(n_wins)[:, None] + np.arange(self.seg_length)[None, :]
         x = np.transpose(spec[idx], (0, 2, 1))[:, None]           # [n_wins, 1, n_mels, seg_length]
         if self.max_length is not None:
@@ -459,6 +472,85 @@ def pair_tokens(ds, indices, num_workers=0):
     return tok
 
 
+def _resident(ds):
+    """The filled stores of a dataset that keeps its spectrograms in device memory (to_memory) -> (store, ref_store or None), or
+    None: the file-fed loops."""
+    store = getattr(ds, 'store', None)
+    if store is None or not store.filled:
+        return None
+    ref = getattr(ds, 'ref_store', None) if getattr(ds, 'double_ended', False) else None
+    if getattr(ds, 'double_ended', False) and (ref is None or not ref.filled):
+        return None
+    return store, ref
+
+
+def _predict_resident(model, ds, stores, bs, dev, on_rows=None):
+    """_predict / _predict_de for a resident dataset: no file is opened.  The shard's items are cut into batches by work
+    (melstore.work_batches, the floors of batch_policy), every batch is one nisqa_mel_gather per store and the engine's stage API
+    from (mel, floor, plan) on: cnn + td_pool, cnn_std + lstm, or -- double-ended, one plan of 2B clips, degraded then reference --
+    cnn + forward_features.  Rows do not depend on the batch composition, so they are the file-fed loop's rows."""
+    from . import melstore as _ms
+    store, ref = stores
+    dev = torch.device(dev)
+    eng = model.engine(dev if dev.index is not None else None)
+    base = getattr(eng, 'base', eng)
+    n = len(ds)
+    lo, hi = _dist.shard_range(n)
+    bounds = None
+    rank, world = _dist.world()
+    tok = store.n_wins.astype(np.int64) + (ref.n_wins.astype(np.int64) if ref is not None else 0)
+    if world > 1 and os.environ.get('NISQA_SHARD_BY_COUNT') != '1':
+        bounds = _dist.balanced_bounds(tok, world)                 # every rank holds the whole store: nothing to exchange
+        lo, hi = bounds[rank]
+    y_local = np.zeros((hi - lo, eng.n_heads), dtype=np.float32)
+    loop_err = None
+    try:
+        bs = max(1, int(bs))
+        lstm = getattr(base, 'arch', 0) in (1, 2, 3)
+        if os.environ.get('NISQA_EXACT_BS') == '1':
+            cuts = [list(range(s, min(s + bs, hi - lo))) for s in range(0, hi - lo, bs)]
+        else:
+            cuts = _ms.work_batches(tok[lo:hi], bs, 0 if lstm else int(os.environ.get('NISQA_MIN_TOKENS', MIN_TOKENS_SA)),
+                                    int(os.environ.get('NISQA_MIN_CLIPS', MIN_CLIPS_LSTM)) if lstm else 1)
+        pending = None                                             # (ids, host rows, event): fetched one batch late
+
+        def fetch(p):
+            p[2].synchronize()
+            y_local[p[0] - lo] = p[1].numpy()
+            if on_rows is not None:
+                on_rows(p[0].tolist(), p[1].numpy())
+
+        for cut in cuts:
+            ids = np.asarray(cut, dtype=np.int64) + lo
+            if ref is None:
+                mel, _, n_wins, floor = store.batch(ids)
+                plan = _ms.batch_plan(n_wins, store.frames[ids])
+                out = base.lstm(base.cnn_std(mel, floor, plan), plan)[0] if lstm else base.td_pool(base.cnn(mel, floor, plan)[0], plan)
+            else:
+                (_, off_d), (_, off_r) = store.offsets(ids), ref.offsets(ids)
+                rows_d, B = int(off_d[-1]), len(ids)
+                mel = torch.empty((rows_d + int(off_r[-1]), 48), dtype=torch.float32, device=base.device)
+                floor = torch.empty(2 * B, dtype=torch.float32, device=base.device)
+                store.gather(ids, off_d, mel[:rows_d], floor[:B])
+                ref.gather(ids, off_r, mel[rows_d:], floor[B:])
+                plan = _ms.batch_plan(np.concatenate([store.n_wins[ids], ref.n_wins[ids]]),
+                                      np.concatenate([store.frames[ids], ref.frames[ids]]))
+                out = eng.forward_features(base.cnn(mel, floor, plan)[0], plan)
+            rows = torch.empty(out.shape, dtype=out.dtype, pin_memory=True)
+            rows.copy_(out, non_blocking=True)
+            done = torch.cuda.Event()
+            done.record()
+            if pending is not None:
+                fetch(pending)
+            pending = (ids, rows, done)
+        if pending is not None:
+            fetch(pending)
+    except Exception as e:                                          # noqa: BLE001 (raised on every rank below)
+        loop_err = e
+    _dist.raise_together(loop_err)
+    return _dist.gather_rows(y_local, n, lo, hi, dev, bounds)
+
+
 def _predict_de(model, ds, bs, dev, num_workers, on_rows=None):
     """_predict for a double-ended dataset (NISQA_DE): y_hat [N, 1].  Items are (degraded, reference) file pairs, read with the
     readers of the single-ended loop (WAV / FLAC, ms_channel) and batched in table order: at least ``bs`` pairs and, unless
@@ -519,6 +611,9 @@ def _predict(model, ds, bs, dev, num_workers, on_rows=None):
     (clip-sharded over ranks when torch.distributed is initialised, then gathered).
     on_rows(ids, rows): optional callback with every batch's item indices and [B, heads] float32 rows as they come back from
     the device (nisqaModel.predict formats the table cells there, under the next batches' transfers)."""
+    stores = _resident(ds)
+    if stores is not None:
+        return _predict_resident(model, ds, stores, bs, dev, on_rows)
     if getattr(ds, 'double_ended', False):
         return _predict_de(model, ds, bs, dev, num_workers, on_rows)
     dev = torch.device(dev)

@@ -306,7 +306,27 @@ class nisqaModel(object):
         if self.args['mode'] != 'main' or not hasattr(self, 'ds_train'):
             raise NotImplementedError("train() needs the training configuration (mode 'main': run_train.py --yaml ...)")
         from . import trainloop
+        self.load_to_memory()                                    # (a no-op unless tr_ds_to_memory, and when it has run already)
         trainloop.train(self)
+
+    def load_to_memory(self):
+        """tr_ds_to_memory: compute the spectrograms of every dataset that asks for it once, on the GPU, and keep them in device
+        memory (melstore.MelStore: ``ds.store``; a double-ended dataset gets a second store over its reference files,
+        ``ds.ref_store``).  ``train()`` calls it when it has not been called.  After it returns the files are not opened again:
+        the training loop, the validation pass after every epoch and ``ds[i]`` read the stores, and edits to the files or to the
+        filename column are not seen -- as in the reference, which loads at dataset construction (NISQA_lib.py:2105-2127).
+        Under torchrun every rank fills its own complete stores (the batches are shares of one permutation over the whole set)."""
+        from .melstore import MelStore
+        for ds in (getattr(self, 'ds_train', None), getattr(self, 'ds_val', None)):
+            if ds is None or not getattr(ds, 'to_memory', False) or ds.store is not None:
+                continue
+            eng = self.model.engine(self.dev)
+            eng = getattr(eng, 'base', eng)                      # HipNisqaDE: the mel front end is its single-ended engine's
+            workers = self.args.get('tr_num_workers') or 0
+            store = MelStore(eng, ds).fill(workers)
+            if ds.double_ended:
+                ds.ref_store = MelStore(eng, ds.ref_view()).fill(workers)
+            ds.store = store
 
     def _makeRunnameAndWriteYAML(self):
         from . import trainloop
@@ -415,10 +435,11 @@ class nisqaModel(object):
         print('Training size: {}, Validation size: {}'.format(len(df_train), len(df_val)))
         if self.args['double_ended'] and not self.args.get('csv_ref'):
             raise ValueError('NISQA_DE needs csv_ref: the csv column with the reference file of each row (--csv_ref)')
-        self.ds_train = self._dataset(df_train, dcon_train, self.args['data_dir'], self.args['csv_deg'], False,
-                                      mos_column=self.args['csv_mos_train'])
-        self.ds_val = self._dataset(df_val, dcon_val, self.args['data_dir'], self.args['csv_deg'], False,
-                                    mos_column=self.args['csv_mos_val'])
+        # tr_ds_to_memory goes to both datasets, as in the reference (NISQA_model.py:885, :909); load_to_memory() acts on it
+        self.ds_train = self._dataset(df_train, dcon_train, self.args['data_dir'], self.args['csv_deg'],
+                                      self.args.get('tr_ds_to_memory', False), mos_column=self.args['csv_mos_train'])
+        self.ds_val = self._dataset(df_val, dcon_val, self.args['data_dir'], self.args['csv_deg'],
+                                    self.args.get('tr_ds_to_memory', False), mos_column=self.args['csv_mos_val'])
         self.runinfos['ds_train_len'] = len(self.ds_train)
         self.runinfos['ds_val_len'] = len(self.ds_val)
 

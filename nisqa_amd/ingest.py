@@ -212,6 +212,19 @@ class Staged(object):
         self.slot, self.groups = slot, groups
 
 
+def rate_groups(srs):
+    """The groups one staged batch falls into: one per sample rate, in order of first appearance, batch order inside a group ->
+    [(rate, positions)].  Ingest._stage_once lays a batch out by it and the resident training loop (melstore) draws its batches by
+    it, so both enter the step in the same clip order."""
+    srs = np.asarray(srs)
+    return [(int(sr), np.flatnonzero(srs == sr)) for sr in dict.fromkeys(srs.tolist())]
+
+
+def step_order(srs):
+    """Positions of a batch's clips in the order the training step sees them: rate_groups, group after group."""
+    return np.concatenate([pos for _, pos in rate_groups(srs)]) if len(srs) else np.zeros(0, dtype=np.int64)
+
+
 class LengthAware(object):
     """Batching policy of the predict loop: the producer probes the RIFF headers of a
     window of items (headers only, native threads), sorts the window by (sample rate, length) and cuts batches by WORK,
@@ -466,8 +479,7 @@ class Ingest(object):
         dst_off = np.full(n, -1, dtype=np.int64)
         region_off, table_off = np.full(n, -1, dtype=np.int64), np.zeros(n, dtype=np.int64)
         clip_id = np.zeros(n, dtype=np.int32)
-        for sr in dict.fromkeys(srs.tolist()):
-            sel = np.flatnonzero(srs == sr)
+        for sr, sel in rate_groups(srs):
             is_i16 = bool(fast[sel].all())
             fl = dev_flac[sel]
             if fl.any():                                            # flac group: a raw group + frame regions + their frame rows
@@ -690,7 +702,8 @@ class Ingest(object):
                 raise val
             yield val
 
-    def close(self):
+    def close(self, keep_ring=True):
+        """keep_ring=False: the page-locked ring is freed instead of being kept for the next loop."""
         if self.ring is None:                      # already closed
             return
         self.stop.set()
@@ -704,7 +717,7 @@ class Ingest(object):
         helper = self._helper
         if helper is not None:                     # a probe of the next window still running: it sees self.stop, or finishes
             helper.join(timeout=30)
-        if not self.thread.is_alive():
+        if keep_ring and not self.thread.is_alive():
             _give_ring(self.ring)                  # the consumer's release events are still attached: reset() waits for them
         self.ring = None
 

@@ -53,6 +53,7 @@ class FlacFrame(ctypes.Structure):
 
 FLAC_BAD_MD5, FLAC_BAD_TABLE = 0x80, 0x100              # NISQA_FLAC_BAD_*; 1 << k below them: the frame check k that failed
 WAVENC_PCM, WAVENC_FLOAT, WAVENC_ALAW, WAVENC_MULAW, WAVENC_BIG_ENDIAN = 1, 3, 6, 7, 0x10000      # NISQA_WAVENC_*
+MEL_GATHER_LDS_CLIPS = 1024                               # NISQA_MEL_GATHER_LDS_CLIPS (nisqa_train.h)
 WAV_DECODE_MAX_BLOCK, WAV_DECODE_MAX_MEAN = 1024, 32     # nisqa_wav_decode's limits: channels * container, channels of a mean
 
 # name -> (restype, argtypes); every symbol include/nisqa_hip.h declares
@@ -182,6 +183,7 @@ TRAIN_SYMBOLS = {
     'nisqa_adam_step': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_f, c_i32, c_p]),
     'nisqa_de_align_fuse_packed': (ctypes.c_int, [c_p] * 6 + [c_i32] * 5 + [c_p] * 3),
     'nisqa_de_align_fuse_bwd': (ctypes.c_int, [c_p, c_i32] + [c_p] * 5 + [c_i32] * 3 + [c_p] * 3),
+    'nisqa_mel_gather': (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_i32, c_p, c_p, c_i32, c_i32, c_p, c_p, c_p]),
 }
 
 _lib = None

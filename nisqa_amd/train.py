@@ -279,6 +279,12 @@ class _FlatTrainer(object):
         d = plan.to(self.device)
         return self._step(mel, d['frame_off'], plan.n_wins, floor, y, masks, bias)
 
+    def step_mel(self, mel, frame_off, n_wins, floor, y, masks=None, bias=None):
+        """One step on spectrograms that already exist: mel [frames][48] dB (not clamped), frame_off int32 [B + 1] on the device,
+        n_wins [B] on the host, floor [B] the clips' top_db floors on the device -- what _mel_groups returns and what
+        melstore.MelStore.batch serves from the resident store (tr_ds_to_memory)."""
+        return self._step(mel, frame_off, n_wins, floor, y, masks, bias)
+
     def step_groups(self, groups, y, masks=None, bias=None):
         """One step on a batch staged as several groups, [(pcm, plan, sr), ...] (the ingest stages one group per sample rate;
         train-mode BatchNorm spans the batch, so it is not split): the mel front end runs per group at that group's rate, the

@@ -154,6 +154,12 @@ class HipTrainerDE(_AttTrainer):
         """deg / ref: (pcm, plan, sr) of the degraded and of the reference clips (float32 device tensor, clips back to back)."""
         return self.step_groups([deg], [ref], y, masks, bias)
 
+    def step_mel(self, deg, ref, y, masks=None, bias=None):
+        """deg / ref: (mel [frames][48], frame offsets on the device, n_wins, clip floors) of the degraded and of the reference
+        clips, row k of one the pair of row k of the other -- what _mel_groups returns per side and what melstore.MelStore.batch
+        serves from the two resident stores."""
+        return self._step(tuple(deg), tuple(ref), y, masks, bias)
+
     def step_groups(self, groups_deg, groups_ref, y, masks=None, bias=None):
         """One step on pairs whose clips are staged as groups, [(pcm, plan, sr), ...] per side -- one group per run of one
         sample rate, as train.concat_groups lays them out.  The two sides are grouped independently (a pair's files may differ in

@@ -15,6 +15,10 @@ BatchNorm spans the batch): every group is copied, resampled (``ms_sr``) and con
 group's spectrogram at that group's rate and runs the rest once (``step_groups``).  Labels, bias rows and predictions follow
 the step's clip order, group after group.
 
+Resident spectrograms (``tr_ds_to_memory: True``): the batches come out of melstore.MelStore instead of the files -- one
+``store.batch`` per side and one ``step_mel`` per batch, the clips in the order the file-fed loop gives the same batch
+(ingest.step_order / pair_order, the functions the file-fed paths themselves lay their batches out by).
+
 One loop serves both model types: ``targets`` is ['mos'] (well: csv_mos_train) for NISQA and
 ['mos', 'noi', 'dis', 'col', 'loud'] for NISQA_DIM, with the reference's key suffixes ('', '_noi', ...) in the result
 dicts, its printed lines and its checkpoint dictionary (so ``run_predict.py`` loads what this writes, here and in the
@@ -149,6 +153,14 @@ def make_trainer(args, state_dict, device, lr):
 _DIM = ['mos', 'noi', 'dis', 'col', 'loud']
 
 
+def pair_order(kinds_deg, kinds_ref):
+    """Positions of a double-ended batch's rows in the order the step sees them: a stable sort by the (sample rate, sample type) of
+    the degraded file, then of the reference file, so that each side falls into runs of one kind while ties keep the batch's order.
+    kinds_*: [(rate, numpy dtype string of the host readers' samples)] per row -- from the files (stage_pairs) or from the resident
+    stores' metadata (melstore.MelStore.kinds); both loops draw their batches by this one function."""
+    return sorted(range(len(kinds_deg)), key=lambda k: tuple(kinds_deg[k]) + tuple(kinds_ref[k]))
+
+
 def stage_pairs(tr, ds, ids):
     """One batch of a double-ended training set -> (row ids in the step's clip order, degraded groups, reference groups) for
     HipTrainerDE.step_groups.  Both files of every row are read on the host with the dataset's readers, as NISQA_lib._predict_de
@@ -158,7 +170,7 @@ def stage_pairs(tr, ds, ids):
     refs = ds.ref_view()
     items = [(ds.load_audio(i), refs.load_audio(i)) for i in ids]
     kind = lambda it: (int(it[1]), it[0].dtype.str)
-    order = sorted(range(len(ids)), key=lambda k: kind(items[k][0]) + kind(items[k][1]))      # stable: ties keep the batch's order
+    order = pair_order([kind(d) for d, _ in items], [kind(r) for _, r in items])
     eng = tr.eng
     sides = []
     for side, view in ((0, ds), (1, refs)):
@@ -177,6 +189,27 @@ def stage_pairs(tr, ds, ids):
                 run = []
         sides.append(groups)
     return np.asarray([ids[k] for k in order]), sides[0], sides[1]
+
+
+def stage_groups(tr, ds, ing, staged):
+    """One staged batch of a single-ended training set -> (row ids in the step's clip order, [(pcm, plan, sr), ...]) for
+    step_groups: one group per sample rate in the batch (the reference loads every file at its own rate, NISQA_lib.py:2299-2310).
+    Train-mode BatchNorm spans the batch, so the groups stay ONE step -- only the spectrogram is per group."""
+    raw = ing.ring.buf[staged.slot]
+    pcms = [_ingest.group_pcm(raw, g, tr.eng, getattr(ds, 'ms_channel', None))
+            for g in staged.groups]                                  # (a raw group: copy + nisqa_wav_decode; a flac group: + nisqa_flac_decode)
+    ev = torch.cuda.Event()
+    ev.record()                                                      # behind the last group's copy
+    ing.ring.release_after(staged.slot, ev)
+    groups = []
+    for g, pcm in zip(staged.groups, pcms):
+        plan = tr.eng.audio_plan(g.lengths, g.sr, names=g.names)     # (at ms_sr when the run sets it: lb.load resamples)
+        pcm = tr.eng.resample(pcm, g.lengths, g.sr)                  # a no-op unless ms_sr is set and differs from the files' rate
+        if pcm.dtype == torch.int16:
+            pcm = tr.eng.pcm16_to_f32(pcm)
+        groups.append((pcm, plan, tr.eng.rate(g.sr)))
+    ids = np.concatenate([np.asarray(g.ids) for g in staged.groups])     # the clip order of the step: group after group
+    return ids, groups
 
 
 def _targets(nm):
@@ -216,6 +249,12 @@ def train(nm):
     y_train = np.stack([nm.ds_train.df[t].to_numpy(dtype=np.float64) for t in targets], 1)
     rng = np.random.default_rng(int(torch.initial_seed()) & 0xffffffff)      # the same permutation on every rank
     rank, world = _dist.world()
+    # tr_ds_to_memory: the spectrograms of the training set are resident (nisqaModel.load_to_memory, melstore.MelStore); a
+    # double-ended set has a second store over its reference files
+    store = getattr(nm.ds_train, 'store', None)
+    ref_store = getattr(nm.ds_train, 'ref_store', None) if store is not None and a['double_ended'] else None
+    if store is not None and a['double_ended'] and ref_store is None:
+        raise RuntimeError('a resident double-ended training set needs both stores (nisqaModel.load_to_memory)')
 
     print('--> start training')
     for epoch in range(a['tr_epochs']):
@@ -243,31 +282,26 @@ def train(nm):
             loss = step(y_train[ids].astype(np.float32), bias)
             pending = (ids, tr.last['y_hat'], loss)
 
-        ing = None if a['double_ended'] else _ingest.Ingest(
+        for b in (batches if store is not None else ()):                # resident spectrograms: no file, no Ingest, no stage_pairs
+            b = np.asarray(b, dtype=np.int64)
+            if ref_store is not None:
+                ids = b[pair_order(store.kinds(b), ref_store.kinds(b))]
+                deg, ref = store.batch(ids), ref_store.batch(ids)
+                run_step(ids, lambda y, bias: tr.step_mel(deg, ref, y, bias=bias))
+            else:
+                ids = b[_ingest.step_order(store.sr[b])]
+                step_in = store.batch(ids)
+                run_step(ids, lambda y, bias: tr.step_mel(*step_in, y, bias=bias))
+        ing = None if a['double_ended'] or store is not None else _ingest.Ingest(
             nm.ds_train, batches, pin=True, num_workers=a['tr_num_workers'],
             device_decode=_ingest.device_decode_default(),                # (NISQA_HOST_DECODE=1: decode on the staging thread)
             device_flac=_ingest.device_flac_default())                    # (NISQA_HOST_FLAC=1: FLAC on the reader threads)
         try:
-            for b in (batches if ing is None else ()):                   # pairs: both files of every row, the two sides in row order
+            for b in (batches if ing is None and store is None else ()):     # pairs: both files of every row, the two sides in row order
                 ids, g_deg, g_ref = stage_pairs(tr, nm.ds_train, b)
                 run_step(ids, lambda y, bias: tr.step_groups(g_deg, g_ref, y, bias=bias))
             for staged in (() if ing is None else ing):
-                # one group per sample rate in the batch (the reference loads every file at its own rate, NISQA_lib.py:2299-2310):
-                # train-mode BatchNorm spans the batch, so the groups stay ONE step -- only the spectrogram is per group
-                raw = ing.ring.buf[staged.slot]
-                pcms = [_ingest.group_pcm(raw, g, tr.eng, getattr(nm.ds_train, 'ms_channel', None))
-                        for g in staged.groups]                          # (a raw group: copy + nisqa_wav_decode; a flac group: + nisqa_flac_decode)
-                ev = torch.cuda.Event()
-                ev.record()                                              # behind the last group's copy
-                ing.ring.release_after(staged.slot, ev)
-                groups = []
-                for g, pcm in zip(staged.groups, pcms):
-                    plan = tr.eng.audio_plan(g.lengths, g.sr, names=g.names)     # (at ms_sr when the run sets it: lb.load resamples)
-                    pcm = tr.eng.resample(pcm, g.lengths, g.sr)          # a no-op unless ms_sr is set and differs from the files' rate
-                    if pcm.dtype == torch.int16:
-                        pcm = tr.eng.pcm16_to_f32(pcm)
-                    groups.append((pcm, plan, tr.eng.rate(g.sr)))
-                ids = np.concatenate([np.asarray(g.ids) for g in staged.groups])     # the clip order of the step: group after group
+                ids, groups = stage_groups(tr, nm.ds_train, ing, staged)
                 run_step(ids, lambda y, bias: tr.step_groups(groups, y, bias=bias))
             if pending is not None:
                 y_hat_train[pending[0]] = pending[1].cpu().numpy()
