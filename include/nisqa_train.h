@@ -402,6 +402,37 @@ int nisqa_mel_gather(const float* store, int64_t store_rows, const int64_t* clip
                      const int32_t* ids, const int32_t* out_frame_off, int32_t n, int32_t out_frames, float* out_mel,
                      float* out_floor, void* stream);
 
+/* ---- the gradient of model(x, n_wins) with respect to x: the eval-mode AdaptCNN with its activations kept (csrc/input_grad.hip) ----
+ * After model.eval() the reference's NISQA / NISQA_DIM are differentiable functions of the segment tensor x [B, L, 1, 48, 15]
+ * (nisqa/NISQA_lib.py:137-142, 260-268, 688-710): BatchNorm normalises by the RUNNING statistics and there is no dropout, so
+ * neither the forward nor the backward of the training step's layers applies (no statistics terms), and conv1 needs an input
+ * gradient.  Activations and arg as above: [S][H*W][C] over the S VALID segments packed clip after clip (seg_off [n_clips + 1]);
+ * valid segment seg_off[b] + k is row b * l_max + k of x.  The attention half of the backward runs on the training operators.
+ *
+ *   nisqa_bn_eval_act_pool_fwd  y[S][ho*wo][c] = adaptive_max_pool(relu(scale z + shift)), scale = gamma / sqrt(running_var + 1e-5),
+ *                               shift = beta - running_mean scale; arg = the pixel (y * w + x) of each maximum, the first one in
+ *                               (y, x) order on a tie -- NOT written (and may be NULL) when ho == h and wo == w, as in
+ *                               nisqa_bn_act_pool_fwd.  The running statistics are read only.
+ *   nisqa_bn_eval_act_pool_bwd  dz[S][h*w][c] = scale * (sum of dy over the cells whose maximum the pixel is) where the
+ *                               pre-activation scale z + shift is positive, 0 elsewhere.  Every element of dz is written (no
+ *                               clearing pass); a gather per pixel in a fixed order, no atomics.
+ *   nisqa_conv1_segments_fwd    z[S][720][16] = conv1(x rows) + bias, w [16][9] with tap = dy * 3 + dx, pixel = band * 15 + frame.
+ *   nisqa_conv1_segments_dgrad  dx [n_clips][l_max][48][15] (the layout of x): row (b, l) = sum_co sum_tap dz[seg_off[b] + l]
+ *                               [pixel - tap offset][co] w[co][tap] for l < the clip's segment count, zeros for the padding
+ *                               rows.  Every element of dx is written; a gather per pixel in a fixed order, no atomics: two
+ *                               runs give the same bits.
+ * c % 4 == 0, c <= 256, 16-byte aligned buffers.  NULL pointers and non-positive sizes return NISQA_ERR_ARG before any launch. */
+int nisqa_bn_eval_act_pool_fwd(const float* z, const float* gamma, const float* beta, const float* running_mean,
+                               const float* running_var, int32_t n_segments, int32_t h, int32_t w, int32_t c, int32_t ho, int32_t wo,
+                               float* y, int32_t* arg, void* stream);
+int nisqa_bn_eval_act_pool_bwd(const float* dy, const int32_t* arg, const float* z, const float* gamma, const float* beta,
+                               const float* running_mean, const float* running_var, int32_t n_segments, int32_t h, int32_t w,
+                               int32_t c, int32_t ho, int32_t wo, float* dz, void* stream);
+int nisqa_conv1_segments_fwd(const float* x, int32_t l_max, const int32_t* seg_off, int32_t n_clips, int32_t n_segments,
+                             const float* w, const float* bias, float* z, void* stream);
+int nisqa_conv1_segments_dgrad(const float* dz, const int32_t* seg_off, int32_t n_clips, int32_t l_max, const float* w, float* dx,
+                               void* stream);
+
 #ifdef __cplusplus
 }
 #endif

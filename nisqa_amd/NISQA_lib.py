@@ -184,11 +184,40 @@ class _NisqaBase(nn.Module):
         return self._engine
 
     def forward(self, x, n_wins):
-        """Reference inner operator model(x[B,L,1,48,15], n_wins[B]) -> [B, heads] (NL:137-142, NL:260-268)."""
-        from .engine import check_segments
-        check_segments(x, n_wins, 1)                               # malformed arguments raise before the engine is built
+        """Reference inner operator model(x[B,L,1,48,15], n_wins[B]) -> [B, heads] (NL:137-142, NL:260-268).
+        CNN-SA-AP models: when gradients are enabled and x requires one, the result carries a grad_fn and backward delivers
+        d / d x as the reference's module does in eval mode (engine.HipNisqa.grad_segments; precisions 'f32' and 'bf16x6', any
+        other raises NotImplementedError here).  The values are those of the plain call, bit for bit.  The StandardCNN + BiLSTM
+        models return values without a grad_fn."""
+        from .engine import DEFAULT_PRECISION, check_segments
+        n = check_segments(x, n_wins, 1)                           # malformed arguments raise before the engine is built
         dev = x.device if x.is_cuda else None
-        return self.engine(dev).forward_segments(x, n_wins)
+        sa = isinstance(self.time_dependency.model, _SelfAttentionParams)
+        if not (sa and torch.is_grad_enabled() and x.requires_grad):
+            return self.engine(dev).forward_segments(x, n_wins)
+        from .input_grad import check_precision
+        check_precision(self._engine.precision if self._engine is not None
+                        else os.environ.get('NISQA_HIP_PRECISION') or DEFAULT_PRECISION)        # refused before any GPU work
+        eng = self.engine(dev)
+        # the Function sees the tensor the kernels read: torch supplies the adjoint of the device / dtype conversion
+        return _SegmentsFunction.apply(x.to(eng.device, dtype=torch.float32).contiguous(), eng, n)
+
+
+class _SegmentsFunction(torch.autograd.Function):
+    """HipNisqa.forward_segments with HipNisqa.grad_segments as its backward.  The forward is the inference path untouched;
+    only x and n_wins are kept, and the backward recomputes what it needs (it costs a second forward)."""
+
+    @staticmethod
+    def forward(ctx, x, eng, n_wins):
+        ctx.eng, ctx.n_wins = eng, n_wins
+        ctx.save_for_backward(x)
+        return eng.forward_segments(x, n_wins)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        x, = ctx.saved_tensors
+        return ctx.eng.grad_segments(x, ctx.n_wins, grad_out), None, None
 
 
 def init_parameters_(model):

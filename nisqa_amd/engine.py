@@ -281,6 +281,7 @@ class HipNisqa(object):
             self.td_wb = self.pool_wb = None
             return
         self.n_layers = int(a['td_sa_num_layers'])
+        self._state_dict, self._input_grad = state_dict, None     # grad_segments builds its operator chain from them on first use
         heads = ['pool_layers.%d.model.' % h for h in range(5)] if self.dim else ['pool.model.']
         self.n_heads = len(heads)
         self.cnn_w = up(_w.pack_adapt_cnn(state_dict))
@@ -539,6 +540,20 @@ class HipNisqa(object):
         if self.arch >= 1:
             return self.lstm(self.cnn_std_segments(x, plan), plan)[0]
         return self.td_pool(self.cnn_segments(x, plan), plan)
+
+    def grad_segments(self, x, n_wins, grad_out):
+        """The backward of forward_segments for the CNN-SA-AP models in precision 'f32' / 'bf16x6': grad_out [B, heads] ->
+        d (sum grad_out * model(x, n_wins)) / d x, float32 [B, L, 1, 48, 15] on the engine's device -- the reference's module in
+        eval mode (BatchNorm on the running statistics, no dropout, key mask over n_wins); rows l >= n_wins[b] are exactly zero.
+        forward_segments keeps no activation, so this call recomputes the network with its activations in HBM: it costs a
+        second forward (nisqa_amd/input_grad.py)."""
+        from . import input_grad
+        if self.arch != 0:
+            raise NotImplementedError('grad_segments is built for the CNN-SA-AP models (NISQA, NISQA_DIM)')
+        input_grad.check_precision(self.precision)
+        if self._input_grad is None:
+            self._input_grad = input_grad.InputGrad(self, self._state_dict)
+        return self._input_grad(x, n_wins, grad_out)
 
     # -- nisqa_tts.tar stages ------------------------------------------------------------------------
     def cnn_std(self, mel_tm, clip_floor, plan):
