@@ -432,6 +432,19 @@ int nisqa_conv1_segments_fwd(const float* x, int32_t l_max, const int32_t* seg_o
                              const float* w, const float* bias, float* z, void* stream);
 int nisqa_conv1_segments_dgrad(const float* dz, const int32_t* seg_off, int32_t n_clips, int32_t l_max, const float* w, float* dx,
                                void* stream);
+/* The same pair for the pooled layers of the StandardCNN (NISQA_lib.py:712-836: pool_first = MaxPool2d(2, stride 2, padding (0, 1))
+ * after conv1, MaxPool2d(2) after conv2 and conv4), which no adaptive window expresses: ho = h / 2, wo = (w + 2 pad_w - 2) / 2 + 1,
+ * cell (oy, ox) = rows 2 oy, 2 oy + 1 x columns 2 ox - pad_w, 2 ox - pad_w + 1 (48 x 15, pad_w 1 -> 24 x 8 with the column windows
+ * {0}, {1, 2}, ..., {13, 14}).  The padding column never wins; arg [S][ho*wo][c] is always written.  The windows do not overlap:
+ * the backward gathers nothing, dz[pixel] = scale * dy[its cell] where the pixel is the cell's maximum and scale z + shift > 0,
+ * 0 elsewhere (also for a last column that no window covers).  h even, pad_w 0 or 1, w + 2 pad_w >= 2, c as above; anything else
+ * returns NISQA_ERR_ARG.  The layers without a pool use nisqa_bn_eval_act_pool_fwd / _bwd with ho = h, wo = w. */
+int nisqa_bn_eval_act_maxpool2_fwd(const float* z, const float* gamma, const float* beta, const float* running_mean,
+                                   const float* running_var, int32_t n_segments, int32_t h, int32_t w, int32_t c, int32_t pad_w,
+                                   float* y, int32_t* arg, void* stream);
+int nisqa_bn_eval_act_maxpool2_bwd(const float* dy, const int32_t* arg, const float* z, const float* gamma, const float* beta,
+                                   const float* running_mean, const float* running_var, int32_t n_segments, int32_t h, int32_t w,
+                                   int32_t c, int32_t pad_w, float* dz, void* stream);
 
 #ifdef __cplusplus
 }

@@ -185,15 +185,14 @@ class _NisqaBase(nn.Module):
 
     def forward(self, x, n_wins):
         """Reference inner operator model(x[B,L,1,48,15], n_wins[B]) -> [B, heads] (NL:137-142, NL:260-268).
-        CNN-SA-AP models: when gradients are enabled and x requires one, the result carries a grad_fn and backward delivers
-        d / d x as the reference's module does in eval mode (engine.HipNisqa.grad_segments; precisions 'f32' and 'bf16x6', any
-        other raises NotImplementedError here).  The values are those of the plain call, bit for bit.  The StandardCNN + BiLSTM
-        models return values without a grad_fn."""
+        When gradients are enabled and x requires one, the result carries a grad_fn and backward delivers d / d x as the
+        reference's module does in eval mode (engine.HipNisqa.grad_segments; precisions 'f32' and 'bf16x6', any other raises
+        NotImplementedError here), for the CNN-SA-AP and the StandardCNN + BiLSTM models alike.  The values are those of the plain
+        call, bit for bit; there is no double backward, and the parameters get no gradient."""
         from .engine import DEFAULT_PRECISION, check_segments
         n = check_segments(x, n_wins, 1)                           # malformed arguments raise before the engine is built
         dev = x.device if x.is_cuda else None
-        sa = isinstance(self.time_dependency.model, _SelfAttentionParams)
-        if not (sa and torch.is_grad_enabled() and x.requires_grad):
+        if not (torch.is_grad_enabled() and x.requires_grad):
             return self.engine(dev).forward_segments(x, n_wins)
         from .input_grad import check_precision
         check_precision(self._engine.precision if self._engine is not None

@@ -2,6 +2,8 @@
 // d model(x, n_wins) / d x after model.eval() (BatchNorm on the running statistics, no dropout; nisqa/NISQA_lib.py:688-710).  The
 // training step cannot lend its kernels here: its BatchNorm normalises by batch statistics and its backward carries their terms,
 // and it has no input gradient of conv1 because a spectrogram never needed one.  Host side: nisqa_amd/input_grad.py.
+// The StandardCNN of the BiLSTM models (NISQA_lib.py:712-836) shares conv1 and the identity layers and has its own pools: the
+// bn_eval_act_maxpool2 pair below.
 //
 // Layouts are the training step's (include/nisqa_train.h): activations [S][H*W][C] with the channels contiguous, S = the VALID
 // segments of the batch packed clip after clip (seg_off), arg = pixel (y * W + x) of every pooled maximum.
@@ -166,6 +168,129 @@ extern "C" int nisqa_bn_eval_act_pool_bwd(const float* dy, const int32_t* arg, c
     NQ_LAUNCH_BEGIN();
     NQ_EVAL_POOL_DISPATCH(bn_eval_act_pool_bwd_kernel, dim3(grid_resident(total)), (hipStream_t)stream, dy, arg, z, gamma, beta,
                           running_mean, running_var, total, h, w, c, ho, wo, dz);
+    return NQ_LAUNCH_STATUS();
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// The StandardCNN's pools: MaxPool2d(2, stride 2, padding (0, pad_w)) behind the frozen BatchNorm + ReLU
+// ---------------------------------------------------------------------------------------------------------
+// Output cell (oy, ox) covers rows 2 oy, 2 oy + 1 and columns 2 ox - pad_w, 2 ox - pad_w + 1; a column outside [0, w) is padding
+// (-inf in PyTorch: it never wins, and every window holds at least one real column).  The windows do not overlap, and with an
+// odd w + 2 pad_w the last real column belongs to no window (floor mode).  pool_first of the StandardCNN is pad_w = 1 on 48 x 15:
+// 8 columns with the windows {0}, {1, 2}, ..., {13, 14} (NISQA_lib.py:712-836).
+NQ_DEV int mp2_wo(int w, int pad_w) { return (w + 2 * pad_w - 2) / 2 + 1; }
+
+// One thread = four consecutive channels of one OUTPUT cell, as bn_eval_act_pool_fwd_kernel.
+template <int H, int W, int C, int PAD>
+__global__ __launch_bounds__(256) void bn_eval_act_maxpool2_fwd_kernel(
+    const float* __restrict__ z, const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean,
+    const float* __restrict__ var, int64_t total4, int h_, int w_, int c_, int pad_, float* __restrict__ y,
+    int32_t* __restrict__ arg) {
+    const int h = H ? H : h_, w = H ? W : w_, c = H ? C : c_, pad = H ? PAD : pad_;
+    const int ho = h / 2, wo = mp2_wo(w, pad);
+    const int c4 = c / 4;
+    constexpr bool INV = H != 0 && 256 % ((C ? C : 4) / 4) == 0;
+    f32x4 sc, sh;
+    if (INV) bn_eval_affine4(gamma, beta, mean, var, 4 * ((int)threadIdx.x % c4), sc, sh);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+        const int ch = 4 * (int)(i % c4);
+        const int64_t op = i / c4;
+        const int64_t s = op / (ho * wo);
+        const int o = (int)(op - s * (ho * wo));
+        const int oy = o / wo, ox = o % wo;
+        if (!INV) bn_eval_affine4(gamma, beta, mean, var, ch, sc, sh);
+        f32x4 best = {-3.0e38f, -3.0e38f, -3.0e38f, -3.0e38f};
+        i32x4 bp = {0, 0, 0, 0};
+#pragma unroll
+        for (int dy = 0; dy < 2; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 2; ++dx) {
+                const int yy = 2 * oy + dy, xx = 2 * ox - pad + dx;
+                if ((unsigned)xx >= (unsigned)w) continue;                   // the padding column
+                const int p = yy * w + xx;
+                const f32x4 v = bn_apply(*(const f32x4*)(z + (s * (h * w) + p) * c + ch), sc, sh);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const float r = fmaxf(v[e], 0.f);
+                    if (r > best[e]) { best[e] = r; bp[e] = p; }         // the first maximum in (y, x) order, as PyTorch
+                }
+            }
+        ((f32x4*)y)[i] = best;
+        ((i32x4*)arg)[i] = bp;
+    }
+}
+
+// One thread = four consecutive channels of one INPUT pixel.  The pixel belongs to at most one cell, so there is nothing to
+// gather: dz = scale * dy of that cell where the pixel is its maximum and the pre-activation is positive, 0 elsewhere (and for
+// the column no window covers).  Every element of dz is written exactly once: no clearing pass, no atomics.
+template <int H, int W, int C, int PAD>
+__global__ __launch_bounds__(256) void bn_eval_act_maxpool2_bwd_kernel(
+    const float* __restrict__ dy, const int32_t* __restrict__ arg, const float* __restrict__ z, const float* __restrict__ gamma,
+    const float* __restrict__ beta, const float* __restrict__ mean, const float* __restrict__ var, int64_t total4, int h_, int w_,
+    int c_, int pad_, float* __restrict__ dz) {
+    const int h = H ? H : h_, w = H ? W : w_, c = H ? C : c_, pad = H ? PAD : pad_;
+    const int ho = h / 2, wo = mp2_wo(w, pad);
+    const int c4 = c / 4;
+    constexpr bool INV = H != 0 && 256 % ((C ? C : 4) / 4) == 0;
+    f32x4 sc, sh;
+    if (INV) bn_eval_affine4(gamma, beta, mean, var, 4 * ((int)threadIdx.x % c4), sc, sh);
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total4; i += (int64_t)gridDim.x * 256) {
+        const int ch = 4 * (int)(i % c4);
+        const int64_t pix = i / c4;
+        const int64_t s = pix / (h * w);
+        const int p = (int)(pix - s * (h * w));
+        const int oy = (p / w) / 2, ox = (p % w + pad) / 2;
+        if (!INV) bn_eval_affine4(gamma, beta, mean, var, ch, sc, sh);
+        const f32x4 yb = bn_apply(((const f32x4*)z)[i], sc, sh);
+        f32x4 out = {0.f, 0.f, 0.f, 0.f};
+        if (ox < wo && (yb[0] > 0.f || yb[1] > 0.f || yb[2] > 0.f || yb[3] > 0.f)) {
+            const int64_t o = (s * (ho * wo) + oy * wo + ox) * c + ch;
+            const i32x4 ag = *(const i32x4*)(arg + o);
+            const f32x4 d = *(const f32x4*)(dy + o);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) out[e] = (ag[e] == p && yb[e] > 0.f) ? sc[e] * d[e] : 0.f;
+        }
+        ((f32x4*)dz)[i] = out;
+    }
+}
+
+// the three pooled layers of the StandardCNN get their own instantiation, anything else the generic one
+#define NQ_EVAL_MAXPOOL2_DISPATCH(KERNEL, GRID, ST, ...)                                                          \
+    do {                                                                                                          \
+        if (h == 48 && w == 15 && c == 16 && pad_w == 1) hipLaunchKernelGGL((KERNEL<48, 15, 16, 1>), GRID, dim3(256), 0, ST, __VA_ARGS__);     \
+        else if (h == 24 && w == 8 && c == 32 && pad_w == 0) hipLaunchKernelGGL((KERNEL<24, 8, 32, 0>), GRID, dim3(256), 0, ST, __VA_ARGS__); \
+        else if (h == 12 && w == 4 && c == 64 && pad_w == 0) hipLaunchKernelGGL((KERNEL<12, 4, 64, 0>), GRID, dim3(256), 0, ST, __VA_ARGS__); \
+        else hipLaunchKernelGGL((KERNEL<0, 0, 0, 0>), GRID, dim3(256), 0, ST, __VA_ARGS__);                        \
+    } while (0)
+
+static bool maxpool2_shape_ok(int32_t n_segments, int32_t h, int32_t w, int32_t c, int32_t pad_w) {
+    return n_segments > 0 && h > 0 && !(h & 1) && w > 0 && c > 0 && c <= 256 && !(c & 3) && (pad_w == 0 || pad_w == 1) &&
+           w + 2 * pad_w >= 2;
+}
+
+extern "C" int nisqa_bn_eval_act_maxpool2_fwd(const float* z, const float* gamma, const float* beta, const float* running_mean,
+                                              const float* running_var, int32_t n_segments, int32_t h, int32_t w, int32_t c,
+                                              int32_t pad_w, float* y, int32_t* arg, void* stream) {
+    if (!z || !gamma || !beta || !running_mean || !running_var || !y || !arg || !maxpool2_shape_ok(n_segments, h, w, c, pad_w))
+        return NISQA_ERR_ARG;
+    const int64_t total = (int64_t)n_segments * (h / 2) * ((w + 2 * pad_w - 2) / 2 + 1) * c / 4;
+    NQ_LAUNCH_BEGIN();
+    NQ_EVAL_MAXPOOL2_DISPATCH(bn_eval_act_maxpool2_fwd_kernel, dim3(grid_resident(total)), (hipStream_t)stream, z, gamma, beta,
+                              running_mean, running_var, total, h, w, c, pad_w, y, arg);
+    return NQ_LAUNCH_STATUS();
+}
+
+extern "C" int nisqa_bn_eval_act_maxpool2_bwd(const float* dy, const int32_t* arg, const float* z, const float* gamma,
+                                              const float* beta, const float* running_mean, const float* running_var,
+                                              int32_t n_segments, int32_t h, int32_t w, int32_t c, int32_t pad_w, float* dz,
+                                              void* stream) {
+    if (!dy || !arg || !z || !gamma || !beta || !running_mean || !running_var || !dz ||
+        !maxpool2_shape_ok(n_segments, h, w, c, pad_w))
+        return NISQA_ERR_ARG;
+    const int64_t total = (int64_t)n_segments * h * w * c / 4;
+    NQ_LAUNCH_BEGIN();
+    NQ_EVAL_MAXPOOL2_DISPATCH(bn_eval_act_maxpool2_bwd_kernel, dim3(grid_resident(total)), (hipStream_t)stream, dy, arg, z, gamma,
+                              beta, running_mean, running_var, total, h, w, c, pad_w, dz);
     return NQ_LAUNCH_STATUS();
 }
 

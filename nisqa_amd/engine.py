@@ -272,6 +272,7 @@ class HipNisqa(object):
         self._mel = {}
         self._ws = {}                      # one workspace per stream (batches may be in flight on several)
         self._flac_ws = {}                 # the same for nisqa_flac_decode
+        self._state_dict, self._input_grad = state_dict, None     # grad_segments builds its operator chain from them on first use
         if self.arch >= 1:
             # StandardCNN (split 16-bit or exact-fp32 MFMA) + BiLSTM + last-step / average / max pooling (fp32 VALU in every mode)
             self.n_layers, self.n_heads = 0, 1
@@ -281,7 +282,6 @@ class HipNisqa(object):
             self.td_wb = self.pool_wb = None
             return
         self.n_layers = int(a['td_sa_num_layers'])
-        self._state_dict, self._input_grad = state_dict, None     # grad_segments builds its operator chain from them on first use
         heads = ['pool_layers.%d.model.' % h for h in range(5)] if self.dim else ['pool.model.']
         self.n_heads = len(heads)
         self.cnn_w = up(_w.pack_adapt_cnn(state_dict))
@@ -542,17 +542,16 @@ class HipNisqa(object):
         return self.td_pool(self.cnn_segments(x, plan), plan)
 
     def grad_segments(self, x, n_wins, grad_out):
-        """The backward of forward_segments for the CNN-SA-AP models in precision 'f32' / 'bf16x6': grad_out [B, heads] ->
-        d (sum grad_out * model(x, n_wins)) / d x, float32 [B, L, 1, 48, 15] on the engine's device -- the reference's module in
-        eval mode (BatchNorm on the running statistics, no dropout, key mask over n_wins); rows l >= n_wins[b] are exactly zero.
+        """The backward of forward_segments in precision 'f32' / 'bf16x6', for the CNN-SA-AP models (input_grad.InputGrad) and the
+        StandardCNN + BiLSTM ones (input_grad.InputGradLSTM): grad_out [B, heads] -> d (sum grad_out * model(x, n_wins)) / d x,
+        float32 [B, L, 1, 48, 15] on the engine's device -- the reference's module in eval mode (BatchNorm on the running
+        statistics, no dropout, the key mask / the packed sequence over n_wins); rows l >= n_wins[b] are exactly zero.
         forward_segments keeps no activation, so this call recomputes the network with its activations in HBM: it costs a
-        second forward (nisqa_amd/input_grad.py)."""
+        second forward (nisqa_amd/input_grad.py).  NISQA_DE has its own engine class, which has no grad_segments."""
         from . import input_grad
-        if self.arch != 0:
-            raise NotImplementedError('grad_segments is built for the CNN-SA-AP models (NISQA, NISQA_DIM)')
         input_grad.check_precision(self.precision)
         if self._input_grad is None:
-            self._input_grad = input_grad.InputGrad(self, self._state_dict)
+            self._input_grad = (input_grad.InputGrad if self.arch == 0 else input_grad.InputGradLSTM)(self, self._state_dict)
         return self._input_grad(x, n_wins, grad_out)
 
     # -- nisqa_tts.tar stages ------------------------------------------------------------------------

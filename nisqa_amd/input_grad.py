@@ -1,4 +1,4 @@
-"""d model(x, n_wins) / d x for the CNN-SA-AP checkpoints (NISQA / NISQA_DIM), on the GPU.
+"""d model(x, n_wins) / d x for the CNN-SA-AP checkpoints (NISQA / NISQA_DIM) and the StandardCNN + BiLSTM ones, on the GPU.
 
 After ``model.eval()`` the reference's modules are differentiable functions of the segment tensor x [B, L, 1, 48, 15]
 (nisqa/NISQA_lib.py:137-142, 260-268): people use NISQA as a perceptual loss, for saliency maps and for adversarial probing.
@@ -16,12 +16,22 @@ and walks back through it:
   heads      attention pooling forward and the input half of its backward, fed with the caller's grad_out.
 Parameters get no gradient here (that is the trainers' business): the weight-gradient GEMMs and column sums of the borrowed
 operators are not run.
+
+``InputGradLSTM`` is the same for the StandardCNN + BiLSTM models (nisqa_tts.tar, pool=last_step_bi; the CNN-LSTM-AVG recipe,
+pool=avg or max), whose grad_out is [B, 1]:
+  CNN        the same eval-mode layers, with the StandardCNN's pools -- pool_first = MaxPool2d(2, 2, padding (0, 1)), which no
+             adaptive window expresses, and the 2 x 2 pools after conv2 and conv4 -- by nisqa_bn_eval_act_maxpool2_fwd / _bwd, and
+             conv2..6 by the exact fp32 implicit GEMM (nisqa_conv3x3_gemm modes 0 and 1), whatever the engine's precision;
+  BiLSTM     fc_out, nisqa_lstm_train_fwd (gates and cell states kept) and nisqa_lstm_train_bptt without the bias sums, then
+             dx20 = dgates w_ih and dfeat = dx20 fc_out.weight;
+  pooling    PoolLastStepBi / PoolAvg / PoolMax inside the two LSTM entries; dpooled = grad_out pool.model.linear.weight.
 """
 import numpy as np
 import torch
 
-from .engine import check_segments
-from .train import _AttTrainer, _ClipSet, _CONV, _ptr, step_tables
+from .engine import check_segments, LSTM_POOL_MODE
+from .train import _AttTrainer, _ClipSet, _CONV, _FlatTrainer, _ptr, step_tables
+from .train_lstm import FC_W, GEO, HipTrainerLSTM, LSTM_KEYS, POOL_KEYS
 
 PRECISIONS = ('f32', 'bf16x6')          # the engine precisions whose operands are the reference's fp32 values
 
@@ -35,7 +45,76 @@ def check_precision(precision):
     return precision
 
 
-class InputGrad(_AttTrainer):
+class _EvalCNN(object):
+    """The eval-mode CNN with its activations kept and the walk back to x, for a trainer's parameter layout (self.P, self.bn,
+    self._geo): conv1 on the segment rows, six frozen-statistics BatchNorm + ReLU (+ pool) layers, conv2..6 through the subclass's
+    ``_conv_eval``.  MAXPOOL2[i] = the pad_w of a MaxPool2d(2, stride 2, padding (0, pad_w)) behind layer i (the StandardCNN);
+    every other layer pools by the adaptive windows of its geometry (the AdaptCNN), the identity among them."""
+    MAXPOOL2 = {}
+
+    def _bn_ptrs(self, i):
+        P = self.P
+        return (_ptr(P['cnn.model.bn%d.weight' % i]), _ptr(P['cnn.model.bn%d.bias' % i]), _ptr(self.bn[i]['mean']),
+                _ptr(self.bn[i]['var']))
+
+    def _cnn_fwd_eval(self, x, seg_off, B, S):
+        """x [B, L, 1, 48, 15] -> (per layer (z, arg), the features [S][pixels * 64] in (pixel, c) order)"""
+        L_, P, st = self.lib, self.P, self._st()
+        recs, act = [], None
+        for i in range(1, 7):
+            co = _CONV[i - 1][1]
+            h, w, (ho, wo) = self._geo[i - 1]
+            bias = P['cnn.model.conv%d.bias' % i]
+            z = self._new(S * h * w, co)
+            if i == 1:
+                self._ck(L_.nisqa_conv1_segments_fwd(_ptr(x), x.shape[1], _ptr(seg_off), B, S, _ptr(P['cnn.model.conv1.weight']),
+                                                     _ptr(bias), _ptr(z), st), 'nisqa_conv1_segments_fwd')
+            else:
+                self._conv_eval(0, i, act, z, S, bias)
+            arg = None if (h, w) == (ho, wo) else self._new(S, ho * wo, co, dtype=torch.int32)
+            act = self._new(S, ho * wo, co)
+            if i in self.MAXPOOL2:
+                self._ck(L_.nisqa_bn_eval_act_maxpool2_fwd(_ptr(z), *self._bn_ptrs(i), S, h, w, co, self.MAXPOOL2[i], _ptr(act),
+                                                           arg.data_ptr(), st), 'nisqa_bn_eval_act_maxpool2_fwd')
+            else:
+                self._ck(L_.nisqa_bn_eval_act_pool_fwd(_ptr(z), *self._bn_ptrs(i), S, h, w, co, ho, wo, _ptr(act),
+                                                       arg.data_ptr() if arg is not None else None, st), 'nisqa_bn_eval_act_pool_fwd')
+            recs.append((z, arg))
+        return recs, act.view(S, -1)
+
+    def _cnn_bwd_eval(self, recs, da, seg_off, B, S, L):
+        """d / d features [S][pixels * 64] -> d / d x [B, L, 1, 48, 15]; recs is emptied, layer by layer"""
+        L_, st = self.lib, self._st()
+        for i in range(6, 0, -1):
+            ci, co = _CONV[i - 1]
+            h, w, (ho, wo) = self._geo[i - 1]
+            z, arg = recs.pop()
+            dz = self._new(S * h * w, co)
+            if i in self.MAXPOOL2:
+                self._ck(L_.nisqa_bn_eval_act_maxpool2_bwd(_ptr(da), arg.data_ptr(), _ptr(z), *self._bn_ptrs(i), S, h, w, co,
+                                                           self.MAXPOOL2[i], _ptr(dz), st), 'nisqa_bn_eval_act_maxpool2_bwd')
+            else:
+                self._ck(L_.nisqa_bn_eval_act_pool_bwd(_ptr(da), arg.data_ptr() if arg is not None else None, _ptr(z),
+                                                       *self._bn_ptrs(i), S, h, w, co, ho, wo, _ptr(dz), st),
+                         'nisqa_bn_eval_act_pool_bwd')
+            if i == 1:
+                break
+            hi, wi = self._geo[i - 2][2]
+            da = self._new(S, hi * wi, ci)
+            self._conv_eval(1, i, dz, da, S)
+        dx = self._new(B, L, 1, 48, 15)
+        self._ck(L_.nisqa_conv1_segments_dgrad(_ptr(dz), _ptr(seg_off), B, L, _ptr(self.P['cnn.model.conv1.weight']), _ptr(dx), st),
+                 'nisqa_conv1_segments_dgrad')
+        return dx
+
+
+def _check_grad_out(grad_out, B, H):
+    if not torch.is_tensor(grad_out) or tuple(grad_out.shape) != (B, H):
+        raise ValueError('expected grad_out of shape [{}, {}], got {}'.format(
+            B, H, tuple(grad_out.shape) if torch.is_tensor(grad_out) else type(grad_out).__name__))
+
+
+class InputGrad(_EvalCNN, _AttTrainer):
     FEAT_W = 'time_dependency.model.linear.weight'
 
     def __init__(self, eng, state_dict):
@@ -78,61 +157,19 @@ class InputGrad(_AttTrainer):
             self._tab_key, self._tab = key, (host, buf, _ClipSet(n, tv, tiles))
         return self._tab[2]
 
-    def _cnn_fwd_eval(self, x, cs):
-        """x [B, L, 1, 48, 15] -> (per layer (z, arg), the features [S][384] in (y, c) order)"""
-        L_, P, S, st = self.lib, self.P, cs.S, self._st()
+    def _conv_eval(self, mode, i, src, dst, S, bias=None):
+        """conv i forward (mode 0) or its input gradient (mode 1): the segment-resident convolutions of the training step, their
+        weight fragments packed at the first call (the weights never change here)"""
         if not self._packed:
             self._pack_frags()
-            if any(self._convs[i][0] is None or self._convs[i][1] is None for i in range(2, 7)):
+            if any(self._convs[k][0] is None or self._convs[k][1] is None for k in range(2, 7)):
                 raise NotImplementedError('no segment-resident convolution for this CNN geometry')
             self._packed = True
-        recs, act = [], None
-        for i in range(1, 7):
-            ci, co = _CONV[i - 1]
-            h, w, (ho, wo) = self._geo[i - 1]
-            bk = 'cnn.model.conv%d.bias' % i
-            z = self._new(S * h * w, co)
-            if i == 1:
-                self._ck(L_.nisqa_conv1_segments_fwd(_ptr(x), x.shape[1], _ptr(cs.seg_off), cs.B, S, _ptr(P['cnn.model.conv1.weight']),
-                                                     _ptr(P[bk]), _ptr(z), st), 'nisqa_conv1_segments_fwd')
-            else:
-                hi, wi = self._geo[i - 2][2]
-                fwd = self._convs[i][0]
-                self._ck(fwd[0](0, _ptr(act), _ptr(fwd[1]), _ptr(z), S, hi, wi, ci, co, self._pad6 if i == 6 else 1, _ptr(P[bk]), None,
-                                st), fwd[0].__name__)
-            arg = None if (h, w) == (ho, wo) else self._new(S, ho * wo, co, dtype=torch.int32)
-            act = self._new(S, ho * wo, co)
-            self._ck(L_.nisqa_bn_eval_act_pool_fwd(_ptr(z), *self._bn_ptrs(i), S, h, w, co, ho, wo, _ptr(act),
-                                                   arg.data_ptr() if arg is not None else None, st), 'nisqa_bn_eval_act_pool_fwd')
-            recs.append((z, arg))
-        return recs, act.view(S, 384)
-
-    def _bn_ptrs(self, i):
-        P = self.P
-        return (_ptr(P['cnn.model.bn%d.weight' % i]), _ptr(P['cnn.model.bn%d.bias' % i]), _ptr(self.bn[i]['mean']),
-                _ptr(self.bn[i]['var']))
-
-    def _cnn_bwd_eval(self, recs, da, cs, B, L):
-        """d / d features [S][384] -> d / d x [B, L, 1, 48, 15]"""
-        L_, S, st = self.lib, cs.S, self._st()
-        for i in range(6, 0, -1):
-            ci, co = _CONV[i - 1]
-            h, w, (ho, wo) = self._geo[i - 1]
-            z, arg = recs.pop()
-            dz = self._new(S * h * w, co)
-            self._ck(L_.nisqa_bn_eval_act_pool_bwd(_ptr(da), arg.data_ptr() if arg is not None else None, _ptr(z), *self._bn_ptrs(i),
-                                                   S, h, w, co, ho, wo, _ptr(dz), st), 'nisqa_bn_eval_act_pool_bwd')
-            if i == 1:
-                break
-            hi, wi = self._geo[i - 2][2]
-            dgrad = self._convs[i][1]
-            da = self._new(S, hi * wi, ci)
-            self._ck(dgrad[0](1, _ptr(dz), _ptr(dgrad[1]), _ptr(da), S, hi, wi, ci, co, self._pad6 if i == 6 else 1, None, None, st),
-                     dgrad[0].__name__)
-        dx = self._new(B, L, 1, 48, 15)
-        self._ck(L_.nisqa_conv1_segments_dgrad(_ptr(dz), _ptr(cs.seg_off), B, L, _ptr(self.P['cnn.model.conv1.weight']), _ptr(dx), st),
-                 'nisqa_conv1_segments_dgrad')
-        return dx
+        ci, co = _CONV[i - 1]
+        hi, wi = self._geo[i - 2][2]
+        fn, frags = self._convs[i][mode]
+        self._ck(fn(mode, _ptr(src), _ptr(frags), _ptr(dst), S, hi, wi, ci, co, self._pad6 if i == 6 else 1,
+                    _ptr(bias) if bias is not None else None, None, self._st()), fn.__name__)
 
     def _heads_bwd(self, cs, x, g):
         """Attention pooling (NISQA_lib.py:1171-1183) on x [S][64], forward, then d (sum_bh g[b][h] y[b][h]) / d x: the input half
@@ -165,14 +202,87 @@ class InputGrad(_AttTrainer):
         engine's device, in x's shape."""
         n = check_segments(x, n_wins, 1)
         B, L, H = x.shape[0], x.shape[1], len(self.heads)
-        if not torch.is_tensor(grad_out) or tuple(grad_out.shape) != (B, H):
-            raise ValueError('expected grad_out of shape [{}, {}], got {}'.format(
-                B, H, tuple(grad_out.shape) if torch.is_tensor(grad_out) else type(grad_out).__name__))
+        _check_grad_out(grad_out, B, H)
         x = x.detach().to(self.device, dtype=torch.float32).contiguous()
         g = grad_out.detach().to(self.device, dtype=torch.float32).contiguous()
         cs = self._tables(np.asarray(n, dtype=np.int64))
-        recs, feat = self._cnn_fwd_eval(x, cs)
+        recs, feat = self._cnn_fwd_eval(x, cs.seg_off, cs.B, cs.S)
         xs, rec = self._sa_fwd(cs, feat, 384, 'time_dependency.model.', self.n_layers, None, 'td%d_%s', 0.0)
         dfeat = self._sa_bwd(rec, self._heads_bwd(cs, xs, g))
         del rec, xs, feat
-        return self._cnn_bwd_eval(recs, dfeat, cs, B, L)
+        return self._cnn_bwd_eval(recs, dfeat, cs.seg_off, B, cs.S, L)
+
+
+class InputGradLSTM(_EvalCNN, _FlatTrainer):
+    """The same for the StandardCNN + BiLSTM models (nisqa_tts.tar and the CNN-LSTM-AVG / -MAX recipe), on HipTrainerLSTM's
+    parameter layout and operators: the StandardCNN's 2 x 2 pools by nisqa_bn_eval_act_maxpool2_fwd / _bwd, conv2..6 by the exact
+    fp32 implicit GEMM (nisqa_conv3x3_gemm modes 0 and 1: what the LSTM trainer runs at these shapes), fc_out, the BiLSTM with
+    its gates kept and the backward through time, fed with grad_out through the pooling's linear layer.  The arithmetic is exact
+    fp32 under either accepted engine precision: this family has no split-bf16 training convolutions."""
+    FEAT_W = FC_W
+    MAXPOOL2 = {1: 1, 2: 0, 4: 0}                     # pool_first = MaxPool2d(2, 2, padding (0, 1)), MaxPool2d(2) after conv2 and conv4
+    _param_order = HipTrainerLSTM._param_order
+
+    def __init__(self, eng, state_dict):
+        if eng.arch not in LSTM_POOL_MODE:
+            raise NotImplementedError('InputGradLSTM is built for the StandardCNN + BiLSTM models')
+        self.precision = check_precision(eng.precision)
+        self.eng, self.lib, self.device, self.args = eng, eng.lib, eng.device, eng.args
+        self.pool_mode = LSTM_POOL_MODE[eng.arch]
+        state_dict = {k: v.detach().cpu() if torch.is_tensor(v) else v for k, v in state_dict.items()}
+        self._layout(state_dict)
+        self.load_state_dict(state_dict)
+        for a_, b_ in zip(LSTM_KEYS[0::2], LSTM_KEYS[1::2]):       # both directions back to back: one pointer per tensor kind
+            assert self.off[b_] == self.off[a_] + int(np.prod(self.kshape[a_])), 'LSTM directions must be adjacent'
+        self._geo, self._pad6 = GEO, 1
+        self._tab_key = None
+
+    def _tables(self, n):
+        """seg_off [B + 1] on the device, kept while the counts repeat"""
+        key = n.tobytes()
+        if key != self._tab_key:
+            seg_off = torch.from_numpy(np.concatenate(([0], np.cumsum(n))).astype(np.int32)).to(self.device)
+            self._tab_key, self._tab = key, seg_off
+        return self._tab
+
+    def _conv_eval(self, mode, i, src, dst, S, bias=None):
+        ci, co = _CONV[i - 1]
+        hi, wi = self._geo[i - 2][2]
+        self._ck(self.lib.nisqa_conv3x3_gemm(mode, _ptr(src), _ptr(self.P['cnn.model.conv%d.weight' % i]), _ptr(dst), S, hi, wi, ci,
+                                             co, self._pad6 if i == 6 else 1, _ptr(bias) if bias is not None else None, 1,
+                                             self._st()), 'nisqa_conv3x3_gemm mode %d' % mode)
+
+    def __call__(self, x, n_wins, grad_out):
+        """x [B, L, 1, 48, 15], n_wins [B], grad_out [B, 1] -> d (sum grad_out * model(x, n_wins)) / d x, float32 on the engine's
+        device, in x's shape."""
+        n = check_segments(x, n_wins, 1)
+        B, L, S = x.shape[0], x.shape[1], int(n.sum())
+        _check_grad_out(grad_out, B, 1)
+        x = x.detach().to(self.device, dtype=torch.float32).contiguous()
+        g = grad_out.detach().to(self.device, dtype=torch.float32).contiguous()
+        seg_off = self._tables(np.asarray(n, dtype=np.int64))
+        L_, P, st = self.lib, self.P, self._st()
+        # recompute, activations kept
+        recs, feat = self._cnn_fwd_eval(x, seg_off, B, S)                     # [S][12 pixels][64]
+        x20 = self._linear_fwd(feat, FC_W, 'cnn.model.fc_out.bias', S, 768, 20)
+        del feat
+        save, hprev = self._new(S, 2, 640), self._new(S, 2, 128)              # hprev: written by the entry, not read here
+        pooled, argmax = self._new(B, 256), self._new(B, 256, dtype=torch.int32)
+        wih, whh = P[LSTM_KEYS[0]], P[LSTM_KEYS[2]]
+        self._ck(L_.nisqa_lstm_train_fwd(_ptr(x20), _ptr(seg_off), B, _ptr(wih), _ptr(whh), _ptr(P[LSTM_KEYS[4]]),
+                                         _ptr(P[LSTM_KEYS[6]]), self.pool_mode, _ptr(save), _ptr(hprev), _ptr(pooled),
+                                         argmax.data_ptr(), st), 'nisqa_lstm_train_fwd')
+        del x20, hprev, pooled
+        # backward, input halves only
+        dpooled = self._new(B, 256)
+        self._gemm(g, P[POOL_KEYS[0]], dpooled, B, 256, 1, 1, 256, 256)
+        dgates = self._new(S, 1024)                                           # [token][direction][4 gates x 128]
+        self._ck(L_.nisqa_lstm_train_bptt(_ptr(seg_off), B, _ptr(whh), _ptr(save), self.pool_mode, _ptr(dpooled),
+                                          argmax.data_ptr(), _ptr(dgates), None, st), 'nisqa_lstm_train_bptt')
+        del save
+        dx20 = self._new(S, 20)                                               # sum over both directions: K = 1024
+        self._gemm(dgates, wih, dx20, S, 20, 1024, 1024, 20, 20)
+        dfeat = self._new(S, 768)
+        self._gemm(dx20, P[FC_W], dfeat, S, 768, 20, 20, 768, 768)
+        del dgates
+        return self._cnn_bwd_eval(recs, dfeat, seg_off, B, S, L)

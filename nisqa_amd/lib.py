@@ -188,6 +188,8 @@ TRAIN_SYMBOLS = {
     'nisqa_bn_eval_act_pool_bwd': (ctypes.c_int, [c_p] * 7 + [c_i32] * 6 + [c_p] * 2),
     'nisqa_conv1_segments_fwd': (ctypes.c_int, [c_p, c_i32, c_p, c_i32, c_i32, c_p, c_p, c_p, c_p]),
     'nisqa_conv1_segments_dgrad': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_p, c_p, c_p]),
+    'nisqa_bn_eval_act_maxpool2_fwd': (ctypes.c_int, [c_p] * 5 + [c_i32] * 5 + [c_p] * 3),
+    'nisqa_bn_eval_act_maxpool2_bwd': (ctypes.c_int, [c_p] * 7 + [c_i32] * 5 + [c_p] * 2),
 }
 
 _lib = None
