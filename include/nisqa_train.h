@@ -381,6 +381,40 @@ int nisqa_de_align_fuse_bwd(const float* d_fused, int32_t ld, const int32_t* idx
                             const int32_t* deg_n_wins, const int32_t* ref_tok_off, const int32_t* ref_n_wins, int32_t n_pairs,
                             int32_t max_n_wins, int32_t fuse, float* d_deg, float* d_ref, void* stream);
 
+/* ---- SOFT alignment at the packed layout, forward with kept statistics, and its backward (d model(x, n_wins) / d x of NISQA_DE
+ * checkpoints with de_align_apply = soft, nisqa_amd/input_grad.py) -------------------------------------------
+ * Layout and arguments as above.  lse [degraded rows] and aligned [degraded rows][64] are indexed like out / d_fused.
+ *
+ * nisqa_de_align_soft_packed: nisqa_de_align_fuse with apply = soft at packed offsets (the same kernel source, the same
+ *   arithmetic: the fused rows are bit for bit those of nisqa_de_align_fuse(apply = 1) on the same valid rows).  Per degraded
+ *   row i it also writes lse[i] = M_i + log L_i (the row's score maximum and its sum of exp(s_ij - M_i) over the pair's valid
+ *   reference tokens), so that the attention weights are p_ij = exp(s_ij - lse[i]), and aligned[i] = a_i = sum_j p_ij y_j, the
+ *   row the fusion combined with x_i.  Writes out, lse and aligned for every degraded row and nothing else.
+ *
+ * nisqa_de_align_soft_bwd: x, lse and aligned as the forward read / wrote them, d_fused = d loss / d fused ->
+ *     s_ij = q^_i . y^_j     p_ij = exp(s_ij - lse[i])     delta_i = ga_i . a_i     ds_ij = p_ij (ga_i . y_j - delta_i)
+ *     d_deg[deg row i] = gx_i + N'(q_i)[ sum_j ds_ij y^_j ]
+ *     d_ref[ref row j] = sum_i p_ij ga_i + N'(y_j)[ sum_i ds_ij q^_i ]
+ *   q_i / y_j: the pair's degraded / reference rows of x; q^, y^: the rows divided by max(||.||, 1e-8) for align 1 (cosine), the
+ *   rows themselves for align 0 (dot); gx_i / ga_i: d_deg and dya of nisqa_de_align_fuse_bwd; N'(v)[u] = (u - v^ (v^ . u)) / ||v||
+ *   for cosine (u / 1e-8 for a row whose norm is at or under the clamp), u for dot.  Sums over the pair's valid tokens only.
+ *   Contract:
+ *     - a score is recomputed with the forward's k-ordered fp32 fma chain on the forward's operands; everything is fp32;
+ *     - two launches (one workgroup per 64 degraded tokens of a pair, then one per 64 reference tokens), no floating-point
+ *       atomics, every sum in a fixed order: two runs give the same bits;
+ *     - every row of every token of both sides is written once (the caller does not pre-zero), no other row is touched;
+ *       d_deg and d_ref may be one buffer in x's layout;
+ *     - ld is a multiple of 4 and d_fused 16-byte aligned (rows are read as 16-byte vectors).
+ * Both return NISQA_ERR_ARG before any launch for a NULL pointer, n_pairs <= 0, align outside {0, 1}, fuse outside {0, 1, 2},
+ * ld_out / ld below the fused width or not a multiple of 4, n_tiles < n_pairs, max_n_wins <= 0 or n_pairs > 65535. */
+int nisqa_de_align_soft_packed(const float* x, const int32_t* deg_tok_off, const int32_t* deg_n_wins, const int32_t* ref_tok_off,
+                               const int32_t* ref_n_wins, const int32_t* tile_off, int32_t n_pairs, int32_t n_tiles, int32_t align,
+                               int32_t fuse, int32_t ld_out, float* out, float* lse, float* aligned, void* stream);
+int nisqa_de_align_soft_bwd(const float* x, const float* d_fused, int32_t ld, const float* lse, const float* aligned,
+                            const int32_t* deg_tok_off, const int32_t* deg_n_wins, const int32_t* ref_tok_off,
+                            const int32_t* ref_n_wins, int32_t n_pairs, int32_t max_n_wins, int32_t align, int32_t fuse,
+                            float* d_deg, float* d_ref, void* stream);
+
 /* ---- resident training spectrograms (tr_ds_to_memory): one batch out of the store --------------------------------------------
  * The store (nisqa_amd/melstore.py) keeps the dB spectrogram of every clip of a dataset in ONE device arena, store
  * [store_rows][48] float32, clip after clip: clip i's rows are clip_row[i] .. clip_row[i + 1] - 1 (clip_row [n_store + 1], int64,

@@ -203,7 +203,7 @@ class _NisqaBase(nn.Module):
 
 
 class _SegmentsFunction(torch.autograd.Function):
-    """HipNisqa.forward_segments with HipNisqa.grad_segments as its backward.  The forward is the inference path untouched;
+    """An engine's forward_segments (HipNisqa, HipNisqaDE) with its grad_segments as the backward.  The forward is the inference path untouched;
     only x and n_wins are kept, and the backward recomputes what it needs (it costs a second forward)."""
 
     @staticmethod
@@ -303,11 +303,21 @@ class NISQA_DE(nn.Module):
 
     def forward(self, x, n_wins):
         """Reference inner operator model(x[B,L,2,48,15], n_wins[B,2]) -> [B, 1] (NL:399-424): channel 0 of x holds the degraded
-        clip's segments, channel 1 the reference clip's.  Malformed arguments raise ValueError before any GPU work."""
-        from .engine import check_segments
-        check_segments(x, n_wins, 2)
+        clip's segments, channel 1 the reference clip's.  Malformed arguments raise ValueError before any GPU work.
+        When gradients are enabled and x requires one, the result carries a grad_fn and backward delivers d / d x as the
+        reference's module does in eval mode, for hard and soft alignment (engine.HipNisqaDE.grad_segments; precisions 'f32' and
+        'bf16x6', any other raises NotImplementedError here).  The values are those of the plain call, bit for bit; there is no
+        double backward, and the parameters get no gradient."""
+        from .engine import DEFAULT_PRECISION, check_segments
+        n = check_segments(x, n_wins, 2)
         dev = x.device if x.is_cuda else None
-        return self.engine(dev).forward_segments(x, n_wins)
+        if not (torch.is_grad_enabled() and x.requires_grad):
+            return self.engine(dev).forward_segments(x, n_wins)
+        from .input_grad import check_precision
+        check_precision(self._engine.precision if self._engine is not None
+                        else os.environ.get('NISQA_HIP_PRECISION') or DEFAULT_PRECISION)        # refused before any GPU work
+        eng = self.engine(dev)
+        return _SegmentsFunction.apply(x.to(eng.device, dtype=torch.float32).contiguous(), eng, n)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -547,7 +547,8 @@ class HipNisqa(object):
         float32 [B, L, 1, 48, 15] on the engine's device -- the reference's module in eval mode (BatchNorm on the running
         statistics, no dropout, the key mask / the packed sequence over n_wins); rows l >= n_wins[b] are exactly zero.
         forward_segments keeps no activation, so this call recomputes the network with its activations in HBM: it costs a
-        second forward (nisqa_amd/input_grad.py).  NISQA_DE has its own engine class, which has no grad_segments."""
+        second forward (nisqa_amd/input_grad.py).  NISQA_DE has its own engine class and its own grad_segments
+        (HipNisqaDE.grad_segments, input_grad.InputGradDE)."""
         from . import input_grad
         input_grad.check_precision(self.precision)
         if self._input_grad is None:
@@ -684,6 +685,7 @@ class HipNisqaDE(object):
         self.fuse = DE_FUSE[args.get('de_fuse', 'x/y/-')]
         self.fuse_width = DE_FUSE_WIDTH[args.get('de_fuse', 'x/y/-')]
         self.n_layers2 = int(args['td_2_sa_num_layers'])
+        self._input_grad = None                                       # grad_segments builds its operator chain on first use
         up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(self.device)
         pfx = 'time_dependency_2.model.'
         self.td2_w = up(_w.pack_self_att(state_dict, self.n_layers2, pfx, in_features=self.fuse_width))
@@ -743,6 +745,19 @@ class HipNisqaDE(object):
         x2 = torch.cat([x[:, :, 0:1], x[:, :, 1:2]], 0).contiguous()
         plan = BatchPlan.from_n_wins(np.concatenate([n[:, 0], n[:, 1]]))
         return self.forward_features(self.base.cnn_segments(x2, plan), plan)
+
+    def grad_segments(self, x, n_wins, grad_out):
+        """The backward of forward_segments in precision 'f32' / 'bf16x6' (input_grad.InputGradDE): x [B, L, 2, 48, 15], n_wins
+        [B, 2], grad_out [B, 1] -> d (sum grad_out * model(x, n_wins)) / d x, float32 [B, L, 2, 48, 15] on the engine's device --
+        the reference's module in eval mode, for hard and soft alignment alike (hard: the argmax carries no gradient); rows
+        l >= n_wins[b, c] of channel c are exactly zero.  forward_segments keeps no activation, so this call recomputes the
+        network operator by operator with its activations in HBM: it costs a second forward.  In hard mode the recomputation
+        takes its own argmax (InputGradDE.last_idx), which at a near-tie of two scores may differ from the fused chain's."""
+        from . import input_grad
+        input_grad.check_precision(self.precision)
+        if self._input_grad is None:
+            self._input_grad = input_grad.InputGradDE(self, self.base._state_dict)
+        return self._input_grad(x, n_wins, grad_out)
 
     def forward_pcm(self, pcm, plan, sr, want_idx=False):
         """pcm: device tensor of the plan's 2B clips back to back (degraded, then reference; float32 or int16 PCM) -> [B, 1]"""

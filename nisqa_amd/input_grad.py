@@ -1,4 +1,5 @@
-"""d model(x, n_wins) / d x for the CNN-SA-AP checkpoints (NISQA / NISQA_DIM) and the StandardCNN + BiLSTM ones, on the GPU.
+"""d model(x, n_wins) / d x for the CNN-SA-AP checkpoints (NISQA / NISQA_DIM), the StandardCNN + BiLSTM ones and the double-ended
+NISQA_DE ones, on the GPU.
 
 After ``model.eval()`` the reference's modules are differentiable functions of the segment tensor x [B, L, 1, 48, 15]
 (nisqa/NISQA_lib.py:137-142, 260-268): people use NISQA as a perceptual loss, for saliency maps and for adversarial probing.
@@ -25,6 +26,10 @@ pool=avg or max), whose grad_out is [B, 1]:
   BiLSTM     fc_out, nisqa_lstm_train_fwd (gates and cell states kept) and nisqa_lstm_train_bptt without the bias sums, then
              dx20 = dgates w_ih and dfeat = dx20 fc_out.weight;
   pooling    PoolLastStepBi / PoolAvg / PoolMax inside the two LSTM entries; dpooled = grad_out pool.model.linear.weight.
+
+``InputGradDE`` is the same for NISQA_DE (x [B, L, 2, 48, 15], n_wins [B, 2], grad_out [B, 1]): InputGrad's operators around the
+alignment + fusion kernels of csrc/de_align.hip, hard (nisqa_de_align_fuse_packed / _bwd) or soft (nisqa_de_align_soft_packed /
+nisqa_de_align_soft_bwd) -- DESIGN.md 4.8.2.
 """
 import numpy as np
 import torch
@@ -32,6 +37,8 @@ import torch
 from .engine import check_segments, LSTM_POOL_MODE
 from .train import _AttTrainer, _ClipSet, _CONV, _FlatTrainer, _ptr, step_tables
 from .train_lstm import FC_W, GEO, HipTrainerLSTM, LSTM_KEYS, POOL_KEYS
+
+_TD1, _TD2 = 'time_dependency.model.', 'time_dependency_2.model.'
 
 PRECISIONS = ('f32', 'bf16x6')          # the engine precisions whose operands are the reference's fp32 values
 
@@ -211,6 +218,92 @@ class InputGrad(_EvalCNN, _AttTrainer):
         dfeat = self._sa_bwd(rec, self._heads_bwd(cs, xs, g))
         del rec, xs, feat
         return self._cnn_bwd_eval(recs, dfeat, cs.seg_off, B, cs.S, L)
+
+
+class InputGradDE(InputGrad):
+    """The same for the double-ended NISQA_DE checkpoints (NISQA_lib.py:406-424 after model.eval()): x [B, L, 2, 48, 15] with the
+    degraded clip's segments in channel 0 and the reference clip's in channel 1, n_wins [B, 2], grad_out [B, 1].  The channels
+    are copied into one [2B, L, 1, 48, 15] tensor, degraded clips first, and the chain is HipTrainerDE's on the eval-mode
+    operators: ONE _cnn_fwd_eval over the 2B clips (BatchNorm on the running statistics couples nothing, so one pass is the
+    reference's two calls), time_dependency over the 2B clips, alignment + fusion, time_dependency_2 and the pooling head over
+    the B degraded clips -- and back: _heads_bwd, _sa_bwd, the alignment's backward, _sa_bwd, _cnn_bwd_eval, and the two halves
+    of the result side by side again.
+      hard  nisqa_de_align_fuse_packed / nisqa_de_align_fuse_bwd, as the training step runs them.  ``last_idx`` keeps the indices
+            the recomputation chose: the argmax over the RAW scores of the recomputed first self-attention (operator by operator,
+            fp32).  At a near-tie of two scores it may differ from the choice of the fused inference chain that produced y
+            (DESIGN.md 4.8 "argmax deviation"); the gradient is then that of the recomputed choice.
+      soft  nisqa_de_align_soft_packed, which keeps lse and the aligned rows, and nisqa_de_align_soft_bwd (csrc/de_align.hip)."""
+
+    def __init__(self, eng, state_dict):
+        InputGrad.__init__(self, eng.base, state_dict)          # eng: engine.HipNisqaDE; its base runs the CNN-SA-AP half
+        self.eng, self.args = eng, eng.args
+        self.n_layers2 = eng.n_layers2
+        self.align, self.soft, self.fuse, self.fuse_width = eng.align, eng.apply, eng.fuse, eng.fuse_width
+        w2 = state_dict[_TD2 + 'linear.weight']
+        if tuple(w2.shape) != (64, self.fuse_width):
+            raise ValueError('{}linear.weight is {}, de_fuse={} needs [64, {}]'.format(_TD2, tuple(w2.shape), self.args.get('de_fuse'),
+                                                                                    self.fuse_width))
+        self.last_idx = None
+
+    def _tables(self, n):
+        """The tables of HipTrainerDE._prepare for pairs of n[b] = (degraded, reference) segments, kept while the counts repeat:
+        -> ({name: device view}, the clip set of the 2B clips, the clip set of the B degraded clips)"""
+        Lx, Ly = n[:, 0], n[:, 1]
+        L12 = np.concatenate([Lx, Ly])
+        key = L12.tobytes()
+        if key != self._tab_key:
+            pa, tiles_a = step_tables(L12)
+            pd, tiles_d = step_tables(Lx)
+            parts = [('a_' + k, v) for k, v in pa] + pd
+            parts += [('n_wins', L12.astype(np.int32)), ('tile_off', np.concatenate(([0], np.cumsum((Lx + 63) // 64))).astype(np.int32))]
+            host, buf, tv = self._upload_tables(parts)
+            self._tab_key, self._tab = key, (host, buf, tv, _ClipSet(L12, tv, tiles_a, 'a_'), _ClipSet(Lx, tv, tiles_d))
+        return self._tab[2:]
+
+    def __call__(self, x, n_wins, grad_out):
+        """x [B, L, 2, 48, 15], n_wins [B, 2], grad_out [B, 1] -> d (sum grad_out * model(x, n_wins)) / d x, float32 on the
+        engine's device, in x's shape; rows l >= n_wins[b, c] of channel c exactly zero."""
+        n = check_segments(x, n_wins, 2)
+        B, L, F = x.shape[0], x.shape[1], self.fuse_width
+        _check_grad_out(grad_out, B, 1)
+        x = x.detach().to(self.device, dtype=torch.float32)
+        x2 = torch.cat([x[:, :, 0:1], x[:, :, 1:2]], 0).contiguous()             # [2B, L, 1, 48, 15], degraded clips first
+        g = grad_out.detach().to(self.device, dtype=torch.float32).contiguous()
+        n = np.asarray(n, dtype=np.int64)
+        tv, cs_all, cs_deg = self._tables(n)
+        L_, st, Sx = self.lib, self._st(), cs_deg.S
+        off, nw = tv['a_seg_off'], tv['n_wins']
+        pair = (_ptr(off), _ptr(nw), _ptr(off, B), _ptr(nw, B))                  # offsets and counts: degraded side, reference side
+        n_tiles, n_max = int(((n[:, 0] + 63) // 64).sum()), int(n.max())
+        # recompute, activations kept
+        recs, feat = self._cnn_fwd_eval(x2, cs_all.seg_off, 2 * B, cs_all.S)
+        del x2
+        x1, rec1 = self._sa_fwd(cs_all, feat, 384, _TD1, self.n_layers, None, 'td%d_%s', 0.0)
+        fused = self._new(Sx, F)
+        if self.soft:
+            lse, aligned = self._new(Sx), self._new(Sx, 64)
+            self._ck(L_.nisqa_de_align_soft_packed(_ptr(x1), *pair, _ptr(tv['tile_off']), B, n_tiles, self.align, self.fuse, F,
+                                                   _ptr(fused), _ptr(lse), _ptr(aligned), st), 'nisqa_de_align_soft_packed')
+        else:
+            idx = self._new(Sx, dtype=torch.int32)
+            self._ck(L_.nisqa_de_align_fuse_packed(_ptr(x1), *pair, _ptr(tv['tile_off']), B, n_tiles, self.align, self.fuse, F,
+                                                   _ptr(fused), _ptr(idx), st), 'nisqa_de_align_fuse_packed')
+            self.last_idx = idx
+        xs, rec2 = self._sa_fwd(cs_deg, fused, F, _TD2, self.n_layers2, None, 'td2_%d_%s', 0.0)
+        # backward, input halves only
+        dfused = self._sa_bwd(rec2, self._heads_bwd(cs_deg, xs, g))              # [Sx][F]
+        del rec2, xs, fused
+        dx1 = self._new(cs_all.S, 64)                                            # every row is written: no clearing
+        if self.soft:
+            self._ck(L_.nisqa_de_align_soft_bwd(_ptr(x1), _ptr(dfused), F, _ptr(lse), _ptr(aligned), *pair, B, n_max, self.align,
+                                                self.fuse, _ptr(dx1), _ptr(dx1), st), 'nisqa_de_align_soft_bwd')
+        else:
+            self._ck(L_.nisqa_de_align_fuse_bwd(_ptr(dfused), F, _ptr(idx), *pair, B, n_max, self.fuse, _ptr(dx1), _ptr(dx1), st),
+                     'nisqa_de_align_fuse_bwd')
+        dfeat = self._sa_bwd(rec1, dx1)                                          # [Sx + Sy][384]
+        del rec1, x1, feat, dfused, dx1
+        dx = self._cnn_bwd_eval(recs, dfeat, cs_all.seg_off, 2 * B, cs_all.S, L)  # [2B, L, 1, 48, 15]
+        return torch.cat([dx[:B], dx[B:]], 2)
 
 
 class InputGradLSTM(_EvalCNN, _FlatTrainer):

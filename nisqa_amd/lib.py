@@ -183,6 +183,8 @@ TRAIN_SYMBOLS = {
     'nisqa_adam_step': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i64, c_f, c_i32, c_p]),
     'nisqa_de_align_fuse_packed': (ctypes.c_int, [c_p] * 6 + [c_i32] * 5 + [c_p] * 3),
     'nisqa_de_align_fuse_bwd': (ctypes.c_int, [c_p, c_i32] + [c_p] * 5 + [c_i32] * 3 + [c_p] * 3),
+    'nisqa_de_align_soft_packed': (ctypes.c_int, [c_p] * 6 + [c_i32] * 5 + [c_p] * 4),
+    'nisqa_de_align_soft_bwd': (ctypes.c_int, [c_p, c_p, c_i32] + [c_p] * 6 + [c_i32] * 4 + [c_p] * 3),
     'nisqa_mel_gather': (ctypes.c_int, [c_p, c_i64, c_p, c_p, c_i32, c_p, c_p, c_i32, c_i32, c_p, c_p, c_p]),
     'nisqa_bn_eval_act_pool_fwd': (ctypes.c_int, [c_p] * 5 + [c_i32] * 6 + [c_p] * 3),
     'nisqa_bn_eval_act_pool_bwd': (ctypes.c_int, [c_p] * 7 + [c_i32] * 6 + [c_p] * 2),
