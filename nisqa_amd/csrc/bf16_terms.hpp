@@ -81,3 +81,17 @@ NQ_DEV void mma16_terms(f32x4 (&acc)[MT], const f32x4 (&a)[MT][T], const f32x4 (
 #pragma unroll
             for (int m = 0; m < MT; ++m) acc[m] = mfma_bf16x16(a[m][i], b[order - i], acc[m]);
 }
+// acc[m][nt] += a[m] x b[nt] (16x16x32)
+template <int T, int MT, int NT>
+NQ_DEV void mma16_terms(f32x4 (&acc)[MT][NT], const f32x4 (&a)[MT][T], const f32x4 (&b)[NT][T]) {
+#pragma unroll
+    for (int order = T - 1; order >= 0; --order)
+#pragma unroll
+        for (int i = order; i >= 0; --i) {
+            const int j = order - i;
+#pragma unroll
+            for (int m = 0; m < MT; ++m)
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt) acc[m][nt] = mfma_bf16x16(a[m][i], b[nt][j], acc[m][nt]);
+        }
+}

@@ -32,7 +32,11 @@
 //   * T = 2: 79 KB of LDS per workgroup, two workgroups (two waves per SIMD) per CU.  T = 3: 117 KB, ONE workgroup per CU, one
 //     wave per SIMD on the 512-register budget -- the K loops keep the A rows of the next step and two steps of weight fragments
 //     in flight themselves and are opened a phase ahead (conv_k_terms_ring; tools/micro/klx6.hip: 96 % matrix-pipe duty at
-//     1.79 GHz in the conv3 + conv4 loops, the chip's power envelope).
+//     1.79 GHz in the conv3 + conv4 loops, the chip's power envelope).  That envelope is why conv3 and conv4 of the three-term
+//     form run TRANSPOSED on 16x16x32 tiles (conv_kt_terms_ring: output channels on the D rows, pixels on the D columns): the chip
+//     holds a higher clock on that shape, and a lane then owns four consecutive channels of a pixel, so its three terms leave as
+//     three 8-byte stores instead of twelve 16-bit ones; conv4's pixel <-> column map keeps the 12 x 5 -> 6 x 3 pool in-lane but
+//     for two DPP row shifts (profiles/r13_cnn_t16_ab.txt: kernel -4.1 %, clock64 ticks +1.4 %, shader clock +4.1 %).
 // What bounds it (tools/micro/issue2.hip): a wave hides <= 5 other instructions behind a 32x32x16 MFMA
 // (<= 2 behind a 16x16x32) and a VALU-only stream issues one instruction per ~5 cycles, so every instruction outside the
 // MFMA shadows counts.  Hence: LDS by 32-bit addresses (no 64-bit pointer arithmetic), lane-static tap masks instead of
@@ -124,6 +128,7 @@ NQ_DEV void cnn_front_split_body(
     extern __shared__ __attribute__((aligned(16))) char smem[];
     constexpr bool X6 = FMT == NQ_FMT_BF16X6, F16 = FMT == NQ_FMT_F16X3 || FMT == NQ_FMT_F16X4;
     constexpr int T = X6 ? 3 : 2;                         // terms per operand = planes per tensor
+    constexpr bool T16_3 = X6 && (NQ_T16 & 1), T16_4 = X6 && (NQ_T16 & 2);
     static_assert(!P3 || FMT == NQ_FMT_BF16X3, "the fp32 copy of the pooled conv4 tensor is a bf16x3 debug output");
     // fragment blob of the term count: CNNB_ (two terms, also the CNNH_ blob of the f16 formats) or CNNX_ (three)
     constexpr int W1_ = X6 ? CNNX_W1 : CNNB_W1, W2_ = X6 ? CNNX_W2 : CNNB_W2, W3_ = X6 ? CNNX_W3 : CNNB_W3, W4_ = X6 ? CNNX_W4 : CNNB_W4,
@@ -311,6 +316,10 @@ NQ_DEV void cnn_front_split_body(
     NQ_STAMP(2);
     // ---- conv2 16->32 on 24x7, pool -> 12x5 (row maps as in cnn.hip)
     conv_k_ring<T, 2, 3> ring34;                          // X6: conv3's, then conv4's first fragments
+    conv_kt_ring<T, 4, NQ_RINGT> ringt;                   // the same for a layer in the transposed form
+    const unsigned lanew = conv_kt_lane<T, 4>(lane);
+    const int c16 = lane & 15, q4 = lane >> 4;            // transposed form: D column (pixel) and row group (channels 4 q4 .. 4 q4 + 3 of a tile)
+    f32x4 tnt[4];                                         // its shifts, by row
     {
         f32x16 acc[6][1];
         unsigned base[6], m9[6];
@@ -325,7 +334,12 @@ NQ_DEV void cnn_front_split_body(
         }
         fb_conv_k<FMT, 16, 6, 1, 7, FB_RS1, FB_P1, false, NQ_RING2>(acc, wrs, W2_ * 2, lane16, base, m9, ring2);
         NQ_STAMP(3);
-        if constexpr (X6) {
+        if constexpr (T16_3) {
+            conv_kt_preload(ringt, wrs, W3_ * 2, lanew);
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) tnt[mt] = *(const f32x4*)(cw + CNN_T3 + 16 * mt + 4 * q4);
+            __builtin_amdgcn_sched_barrier(0);
+        } else if constexpr (X6) {
             conv_k_preload(ring34, wrs, W3_ * 2, lane16);
             __builtin_amdgcn_sched_barrier(0);            // (hipcc would sink the requests below the epilogue, to their use)
         }
@@ -370,7 +384,41 @@ NQ_DEV void cnn_front_split_body(
     }
 
     // ---- conv3 32->64 on 12x5
-    {
+    if constexpr (T16_3) {
+        // transposed: four N tiles of 16 consecutive pixels (60 of 64), four M tiles of 16 channels; one K32 step per tap
+        f32x4 acc[4][4];
+        unsigned base[4], m9[4];
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            const int pix = 16 * nt + c16, py = pix / 5, px = pix - 5 * py;
+            m9[nt] = tap_mask(pix < 60, py, px, 12, 5);
+            base[nt] = R + (pix - 6) * FB_RS2 + (q4 << 4);       // tap (-1, -1) is 5 + 1 pixels back
+        }
+        conv_kt_terms_ring<3, 32, 4, 4, 5, FB_RS2, FB_P2, FB_ZADDR, NQ_RINGT>(acc, wrs, W3_ * 2, lanew, base, m9, ringt);
+        NQ_STAMP(5);
+        const f32x4 tn[4] = {tnt[0], tnt[1], tnt[2], tnt[3]};
+        if constexpr (T16_4) {
+            conv_kt_preload(ringt, wrs, W4_ * 2, lanew);
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) tnt[mt] = *(const f32x4*)(cw + CNN_T4 + 16 * mt + 4 * q4);
+        } else conv_k_preload(ring34, wrs, W4_ * 2, lane16);
+        __builtin_amdgcn_sched_barrier(0);
+        // a lane holds channels 16 mt + 4 q4 + r of pixel 16 nt + c16: one 8-byte store per term plane
+        const unsigned wr = R + c16 * FB_RS3 + q4 * 8;
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt)
+            if (nt < 3 || c16 < 12) {
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt) {
+                    f32x4 v;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) v[r] = fmaxf(acc[mt][nt][r] + tn[mt][r], 0.f);
+                    lds_store_terms4<3>(wr + 16 * nt * FB_RS3 + 32 * mt, FB_P3, v);
+                }
+            }
+    } else {
         f32x16 acc[2][2];
         unsigned base[2];
 #pragma unroll
@@ -381,7 +429,12 @@ NQ_DEV void cnn_front_split_body(
         }
         fb_conv_k<FMT, 32, 2, 2, 5, FB_RS2, FB_P2, true, NQ_RING34>(acc, wrs, W3_ * 2, lane16, base, m34, ring34);
         NQ_STAMP(5);
-        if constexpr (X6) {
+        if constexpr (T16_4) {
+            conv_kt_preload(ringt, wrs, W4_ * 2, lanew);
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) tnt[mt] = *(const f32x4*)(cw + CNN_T4 + 16 * mt + 4 * q4);
+            __builtin_amdgcn_sched_barrier(0);
+        } else if constexpr (X6) {
             conv_k_preload(ring34, wrs, W4_ * 2, lane16);
             __builtin_amdgcn_sched_barrier(0);
         }
@@ -419,7 +472,60 @@ NQ_DEV void cnn_front_split_body(
     const int w5b = __builtin_amdgcn_readfirstlane((W5_ + wave * (18 * T * 512)) * 2);
     const int w6b = __builtin_amdgcn_readfirstlane((W6_ + wave * (18 * T * 512)) * 2);
     f32x4 b5[4][T], b6[8][T];
-    {
+    if constexpr (T16_4) {
+        // transposed, with the pixel <-> (N tile, column) map chosen for the pool: columns 5 j .. 5 j + 4 serve the row pairs gl = 2 j
+        // and 2 j + 1 (image rows 2 gl, 2 gl + 1 = N tile parity) as
+        //     role 0: gl = 2 j,     x = 0 | 1        role 3: gl = 2 j + 1, x = 1 | 0        (N tiles 0, 1 | 2, 3)
+        //     role 1: gl = 2 j,     x = 3 | 4        role 4: gl = 2 j + 1, x = 3 | 4
+        //     role 2: x = 2 of gl = 2 j | 2 j + 1
+        // (15 of 16 columns).  Pooled windows x = {0, 1} and {3, 4} are then the maximum of a column's four tiles; window {1, 2, 3}
+        // is finalised in columns 5 j + 1 and 5 j + 3 from their own tiles 0, 1, the left neighbour's tiles 2, 3 and the right
+        // neighbour's tiles 0, 1: two DPP row shifts, no LDS, no selects.
+        f32x4 acc[4][4];
+        unsigned base[4], m9[4];
+        const int j5 = c16 / 5, role = c16 - 5 * j5;
+        const int glc = 2 * j5 + (role >= 3 ? 1 : 0);     // (roles 0, 1, 3, 4; role 2 holds both)
+#pragma unroll
+        for (int nt = 0; nt < 4; ++nt) {
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) acc[mt][nt] = f32x4{0.f, 0.f, 0.f, 0.f};
+            const int yy = nt & 1, hi = nt >> 1;
+            const int gl = role == 2 ? 2 * j5 + hi : glc;
+            const int px = role == 2 ? 2 : role == 0 ? hi : role == 3 ? 1 - hi : 3 + hi, py = 2 * gl + yy;
+            m9[nt] = tap_mask(c16 < 15, py, px, 12, 5);
+            base[nt] = R + (py * 5 + px - 6) * FB_RS3 + (q4 << 4);
+        }
+        conv_kt_terms_ring<3, 64, 4, 4, 5, FB_RS3, FB_P3, FB_ZADDR, NQ_RINGT>(acc, wrs, W4_ * 2, lanew, base, m9, ringt);
+        NQ_STAMP(7);
+#pragma unroll
+        for (int g = 0; g < 3; ++g)
+#pragma unroll
+            for (int q = 0; q < T; ++q) b5[g][q] = wfrag_load(wrs, lane16, w5b + (g * T + q) * 1024);
+        f32x4 w02[4], w1[4];                              // relu(max + shift) of windows 0 / 2 (by role) and of window 1
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                // (v_maximum3_f32: fmaxf would first canonicalise every accumulator with a v_max of its own)
+                const float m01 = __builtin_elementwise_maximum(acc[mt][0][r], acc[mt][1][r]), m23 = __builtin_elementwise_maximum(acc[mt][2][r], acc[mt][3][r]);
+                const int i01 = (int)__float_as_uint(m01), i23 = (int)__float_as_uint(m23);
+                const float lf = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(i23, i23, 0x111, 0xf, 0xf, false));   // row_shr:1: lane c - 1
+                const float rt = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(i01, i01, 0x101, 0xf, 0xf, false));   // row_shl:1: lane c + 1
+                w02[mt][r] = fmaxf(__builtin_elementwise_maximum(m01, m23) + tnt[mt][r], 0.f);
+                w1[mt][r] = fmaxf(__builtin_elementwise_maximum(__builtin_elementwise_maximum(m01, lf), rt) + tnt[mt][r], 0.f);
+            }
+        __syncthreads();                  // every wave has consumed its A3: the regions may be re-used
+        const unsigned wr = S4 + (18 * wave + 3 * glc) * FB_RS3 + q4 * 8;
+        if (c16 < 15 && role != 2) {
+            const unsigned a = wr + (role == 1 || role == 4 ? 2 * FB_RS3 : 0);
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) lds_store_terms4<3>(a + 32 * mt, FB_PS, w02[mt]);
+        }
+        if (c16 < 15 && (role == 1 || role == 3)) {
+#pragma unroll
+            for (int mt = 0; mt < 4; ++mt) lds_store_terms4<3>(wr + FB_RS3 + 32 * mt, FB_PS, w1[mt]);
+        }
+    } else {
         f32x16 acc[2][2];
         unsigned base[2];
 #pragma unroll

@@ -121,6 +121,7 @@ NQ_DEV f32x4 lds_ld128(unsigned a) { return *(NQ_AS3 const f32x4*)(a); }
 NQ_DEV unsigned lds_ld32(unsigned a) { return *(NQ_AS3 const unsigned*)(a); }
 NQ_DEV void lds_st16(unsigned a, unsigned v) { *(NQ_AS3 unsigned short*)(a) = (unsigned short)v; }
 NQ_DEV void lds_st32(unsigned a, unsigned v) { *(NQ_AS3 unsigned*)(a) = v; }
+NQ_DEV void lds_st64(unsigned a, u32x2 v) { *(NQ_AS3 u32x2*)(a) = v; }
 NQ_DEV void lds_st128(unsigned a, f32x4 v) { *(NQ_AS3 f32x4*)(a) = v; }
 // v = hi + lo into the two bf16 planes (lo plane `plane` bytes behind the hi plane)
 NQ_DEV void lds_store_split(unsigned a, int plane, float v) {
@@ -275,6 +276,15 @@ NQ_DEV void lds_store_terms(unsigned a, int plane, float v) {
         if (t + 1 < T) r -= __uint_as_float(pk << 16);
     }
 }
+// four consecutive channels of one pixel -> T terms each, ONE 8-byte store per plane (the epilogue of the transposed form below)
+template <int T>
+NQ_DEV void lds_store_terms4(unsigned a, int plane, f32x4 v) {
+    unsigned lo[T], hi[T];
+    split2t<T>(v[0], v[1], lo);
+    split2t<T>(v[2], v[3], hi);
+#pragma unroll
+    for (int t = 0; t < T; ++t) lds_st64(a + t * plane, u32x2{lo[t], hi[t]});
+}
 // conv_k_bf16 for T terms: fragments [step][NT][T][64 lanes][8 bf16], activation planes PLANE bytes apart; A rows always
 // one step ahead (this form runs one wave per SIMD on the 512-register budget).  FENCE: a sched_barrier behind the step's
 // requests -- hipcc's scheduler otherwise sinks them to just before their use, and with ONE wave per SIMD nobody fills the
@@ -334,6 +344,109 @@ NQ_DEV void conv_k_terms_ring(f32x16 (&acc)[MT][NT], __amdgpu_buffer_rsrc_t rsrc
         if (g + 1 < TOTAL) load_a(g + 1, (g + 1) & 1);
         if (FENCE) __builtin_amdgcn_sched_barrier(0);
         mma_terms<T, MT, NT>(acc, a[g & 1], ring.b[g % RING]);
+    }
+}
+// ---- the transposed form on 16x16x32 tiles: output CHANNELS on the D rows (A operand = weights, MT tiles of 16 channels), PIXELS
+// on the D columns (B operand = activations, NT tiles of 16 pixels); a K step is 32 input channels of one tap.  Same fragment blob
+// as conv_k_terms_ring ([K16 step g][32-channel tile][T][64 lanes][8 bf16], the B operand of a 32x32x16): the 16 bytes of output
+// channel n, K chunk q = lane >> 4 of K32 step G sit in K16 step 2 G + (q >> 1) at lane n % 32 + 32 (q & 1) of tile n / 32 -- one
+// lane-dependent offset (conv_kt_lane) plus immediates.  A lane reads its column's pixel row at byte 16 q of the step's 32-channel
+// block.  Prefetch distances as in conv_k_terms_ring (weights RING - 1 steps, activations one step ahead).
+//   base[nt] : LDS address of chunk q of the pixel at tap (-1, -1) of tile nt's column, first plane;  m9[nt] : its tap_mask
+// NQ_KT_SGB: where a step's requests go.  0: in a block ahead of the step's MFMAs behind a fence, as conv_k_terms_ring does -- but a
+// 16x16x32 hides two other instructions, not five, and hipcc emitted the 12 ds_read_b128 back to back and parked addresses in AGPRs
+// (586 v_accvgpr_read): 93 % matrix-pipe duty.  1: a sched_group_barrier pipeline deals them out between the step's MFMAs, at most
+// two in a row: no AGPR copies, 246 + 96 registers instead of 256 + 108, and the conv3 + conv4 loops 7 % shorter in clock64 ticks
+// (profiles/r13_cnn_t16_ab.txt).
+#ifndef NQ_KT_SGB
+#define NQ_KT_SGB 1
+#endif
+// Which layers of cnn_front_bf16x6_kernel run in this form -- conv3 (bit 0), conv4 (bit 1) -- and the depth of the weight-fragment
+// ring in K32 steps.  Measured per layer against the 32x32x16 form at the same output tile per wave (tools/ab_build.sh, same box,
+// alternating, profiles/r13_cnn_t16_ab.txt): conv3 alone -1.6 %, both -2.7 % (ring 2; ring 3 -1.4 %: more registers, AGPR traffic),
+// both with NQ_KT_SGB -4.1 % of the kernel's time.
+#ifndef NQ_T16
+#define NQ_T16 3
+#endif
+#ifndef NQ_RINGT
+#define NQ_RINGT 2
+#endif
+template <int T, int MT, int RING = 3>
+struct conv_kt_ring { f32x4 a[RING][MT][T]; };
+template <int T, int MT>
+NQ_DEV unsigned conv_kt_lane(int lane) {
+    const int q = lane >> 4;
+    return (unsigned)((q >> 1) * ((MT / 2) * T * 1024) + ((lane & 15) + 32 * (q & 1)) * 16);
+}
+template <int T, int MT>
+NQ_DEV f32x4 conv_kt_wfrag(__amdgpu_buffer_rsrc_t rsrc, unsigned lanew, int wbyte, int G, int mt, int t) {
+    return wfrag_load(rsrc, lanew, wbyte + ((2 * G * (MT / 2) + (mt >> 1)) * T + t) * 1024 + (mt & 1) * 256);
+}
+template <int T, int MT, int RING>
+NQ_DEV void conv_kt_preload(conv_kt_ring<T, MT, RING>& r, __amdgpu_buffer_rsrc_t rsrc, int wbyte, unsigned lanew) {
+#pragma unroll
+    for (int G = 0; G < RING - 1; ++G)
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int t = 0; t < T; ++t) r.a[G][mt][t] = conv_kt_wfrag<T, MT>(rsrc, lanew, wbyte, G, mt, t);
+}
+// PRE: `ring` already holds the first RING - 1 steps (conv_kt_preload)
+template <int T, int CIN, int MT, int NT, int W, int RS, int PLANE, unsigned ZADDR, int RING>
+NQ_DEV void conv_kt_terms_ring(f32x4 (&acc)[MT][NT], __amdgpu_buffer_rsrc_t rsrc, int wbyte, unsigned lanew,
+                               const unsigned (&base)[NT], const unsigned (&m9)[NT], conv_kt_ring<T, MT, RING>& ring) {
+    constexpr int S32 = CIN / 32, TOTAL = 9 * S32;
+    static_assert(MT % 2 == 0 && CIN % 32 == 0, "whole 32-channel fragment tiles");
+    static_assert(ZADDR >= (2 * W + 2) * RS + 64 * S32, "zero block must sit above the largest tap offset");
+    f32x4 b[2][NT][T];
+    unsigned b_ad[NT][T];
+    auto load_a = [&](int G, int slot) {
+#pragma unroll
+        for (int mt = 0; mt < MT; ++mt)
+#pragma unroll
+            for (int t = 0; t < T; ++t) ring.a[slot][mt][t] = conv_kt_wfrag<T, MT>(rsrc, lanew, wbyte, G, mt, t);
+    };
+    auto load_b = [&](int G, int slot) {
+        const int tap = G / S32, s = G - tap * S32;
+        const int tapoff = ((tap / 3) * W + tap % 3) * RS;
+        if (s == 0) {
+#pragma unroll
+            for (int nt = 0; nt < NT; ++nt) {
+                const bool ok = (m9[nt] >> tap) & 1u;
+#pragma unroll
+                for (int t = 0; t < T; ++t) b_ad[nt][t] = ok ? base[nt] + t * PLANE : ZADDR - tapoff;
+            }
+        }
+#pragma unroll
+        for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+            for (int t = 0; t < T; ++t) b[slot][nt][t] = lds_ld128(b_ad[nt][t] + tapoff + 64 * s);
+    };
+    load_b(0, 0);
+#pragma unroll
+    for (int G = 0; G < TOTAL; ++G) {
+#if NQ_KT_SGB
+        // the next steps' requests ride between this step's MFMAs, never more than two in a row (a 16x16x32 hides two)
+        __builtin_amdgcn_sched_barrier(0);
+        mma16_terms<T, MT, NT>(acc, ring.a[G % RING], b[G & 1]);
+        if (G + RING - 1 < TOTAL) load_a(G + RING - 1, (G + RING - 1) % RING);
+        if (G + 1 < TOTAL) load_b(G + 1, (G + 1) & 1);
+#pragma unroll
+        for (int i = 0; i < MT * T; ++i) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
+            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
+            __builtin_amdgcn_sched_group_barrier(0x008, MT * NT * T * (T + 1) / 2 / (MT * T) - 6, 0);
+        }
+#else
+        if (G + RING - 1 < TOTAL) load_a(G + RING - 1, (G + RING - 1) % RING);
+        if (G + 1 < TOTAL) load_b(G + 1, (G + 1) & 1);
+        __builtin_amdgcn_sched_barrier(0);
+        mma16_terms<T, MT, NT>(acc, ring.a[G % RING], b[G & 1]);
+#endif
     }
 }
 template <int T, int CIN, int MT, int NT, int W, int RS, int PLANE, unsigned ZADDR, int RING = 3, bool FENCE = true>
