@@ -14,6 +14,7 @@
 #define NISQA_TRAIN_H
 
 #include <stdint.h>
+#include "nisqa_hip.h"        /* nisqa_mel_cfg, NISQA_ERR_* */
 
 #ifdef __cplusplus
 extern "C" {
@@ -479,6 +480,46 @@ int nisqa_bn_eval_act_maxpool2_fwd(const float* z, const float* gamma, const flo
 int nisqa_bn_eval_act_maxpool2_bwd(const float* dy, const int32_t* arg, const float* z, const float* gamma, const float* beta,
                                    const float* running_mean, const float* running_var, int32_t n_segments, int32_t h, int32_t w,
                                    int32_t c, int32_t pad_w, float* dz, void* stream);
+
+/* ---- the gradient with respect to the AUDIO: backward of the mel front end and of the segmenting (csrc/mel_bwd.hip) ----
+ * Carries d L / d x of model(x, n_wins) back to the samples: segments -> clamped dB rows -> top_db floor -> dB -> filter bank ->
+ * |STFT| -> window -> reflect padding.  The function differentiated is the forward's (nisqa_mel_db + nisqa_mel_finalize), per clip
+ * of L samples: frame f, tap n < win reads sample refl(f hop + start0 + n), start0 = -n_fft / 2 + (n_fft - win) / 2, refl: i -> -i
+ * below 0, i -> 2 (L - 1) - i from L on; X_k = sum_n w_n x_n e^(-2 pi i k n / 4096), k = 0 .. 2048; M_m = sum_k fb[m][k] |X_k|;
+ * db = 10 log10(max(amin_sq, M_m^2)); out = max(db, max_clip(db) - top_db).  cfg and the tables are the forward's.
+ *
+ *   nisqa_segments_to_mel_bwd      dmel[TT][48]: element (t, m) of clip b = sum over the segments k < n_wins[b] with seg_hop k <= t <=
+ *                                  seg_hop k + 14 of dx[b][k][0][m][t - seg_hop k], k ascending; 0 for a frame no segment holds.
+ *                                  dx is [n_clips][l_max][1][48][15]; its rows k >= n_wins[b] are never read.
+ *   nisqa_mel_db_bwd_gate          dmel_amp[TT][48] = d L / d M from g = d L / d out, the forward's UNCLAMPED dB rows and its clip_floor:
+ *                                  an element passes g where db > clip_floor; the g of every other element of the clip goes to the
+ *                                  clip's maximum (the derivative of max(db) - top_db), on a tie the FIRST maximum in (frame, band)
+ *                                  order; d db / d M = 20 / (ln 10 M) where db is above the forward's value of 10 log10(amin_sq), else
+ *                                  0.  Both gates are taken on the forward's own bits; M is recovered from the stored dB.
+ *   nisqa_mel_bwd_workspace_bytes  total_frames * win floats (0 for sizes the entries refuse)
+ *   nisqa_mel_frame_bwd            ws[TT][win]: per frame the gradient of its win windowed samples.  X is recomputed (4096-point FFT
+ *                                  in LDS), d L / d |X_k| = sum_m fb[m][k] dmel_amp[m], d L / d x_n = w_n Re sum_{k = 0}^{2048}
+ *                                  (d L / d |X_k| X_k / |X_k|) e^(+2 pi i k n / 4096) -- one-sided, not doubled; a term is 0 where
+ *                                  |X_k| = 0.  A frame whose 48 gradients are all 0 writes exact zeros.  A clip's frames read that
+ *                                  clip's samples only.  The sparse bank must be triangular: bands m and m + 2 share no bin with a
+ *                                  non-zero weight.
+ *   nisqa_mel_overlap_add_bwd      dpcm[total_samples]: per sample the taps of every frame over every padded position that reflects
+ *                                  onto it (itself, the left and the right reflection), in a fixed order.  Exact for clips whose
+ *                                  padding reflects once (L > win / 2 + hop, as every clip of >= 15 frames).
+ * No atomics: every output element is written once, two calls give the same bits.  float PCM only (int16 PCM has no gradient).
+ * NULL pointers, non-positive or impossible sizes (n_clips > total_frames, win outside [2, 4096], n_fft != 4096, ...) return
+ * NISQA_ERR_ARG before any launch; a workspace smaller than nisqa_mel_bwd_workspace_bytes returns NISQA_ERR_WORKSPACE. */
+int nisqa_segments_to_mel_bwd(const float* dx, int32_t l_max, const int32_t* n_wins, const int32_t* frame_off, int32_t n_clips,
+                              int32_t total_frames, int32_t seg_hop, float* dmel, void* stream);
+int nisqa_mel_db_bwd_gate(const float* g, const float* mel_db, const float* clip_floor, const int32_t* frame_off, int32_t n_clips,
+                          int32_t total_frames, const nisqa_mel_cfg* cfg, float* dmel_amp, void* stream);
+int64_t nisqa_mel_bwd_workspace_bytes(int32_t total_frames, int32_t win);
+int nisqa_mel_frame_bwd(const float* pcm, const int64_t* clip_off, const int32_t* frame_off, int32_t n_clips, int32_t total_frames,
+                        const nisqa_mel_cfg* cfg, const float* window, const float* twiddle, const int32_t* band_start,
+                        const int32_t* band_len, const int32_t* band_woff, const float* band_w, const float* dmel_amp, float* ws,
+                        int64_t ws_bytes, void* stream);
+int nisqa_mel_overlap_add_bwd(const float* ws, const int64_t* clip_off, const int32_t* frame_off, int32_t n_clips,
+                              int32_t total_frames, int64_t total_samples, const nisqa_mel_cfg* cfg, float* dpcm, void* stream);
 
 #ifdef __cplusplus
 }

@@ -201,6 +201,97 @@ class _NisqaBase(nn.Module):
         # the Function sees the tensor the kernels read: torch supplies the adjoint of the device / dtype conversion
         return _SegmentsFunction.apply(x.to(eng.device, dtype=torch.float32).contiguous(), eng, n)
 
+    def forward_audio(self, y, sr, lengths=None):
+        """Scores of in-memory audio: y a floating tensor on any device, [N] for one clip or [B, N] for a padded batch of clips at
+        one integer rate ``sr``, lengths [B] whole numbers in [1, N] (default: N for every clip) -> [B, heads] on the engine's
+        device.  Samples at n >= lengths[b] are never read.  The clips are packed back to back and go through the engine's
+        forward_pcm (through its resampler first when the checkpoint sets ms_sr): the result is forward_pcm's, bit for bit, in
+        every engine precision.
+        When gradients are enabled and y requires one, the result carries a grad_fn and backward delivers d / d y in y's shape,
+        dtype and device, exact zeros at n >= lengths[b] whatever y holds there (engine.HipNisqa.grad_audio: the backward of the
+        mel front end and of the segmenting behind grad_segments; precisions 'f32' and 'bf16x6').  The values are the plain
+        call's, bit for bit; there is no double backward and the parameters get no gradient.
+        Refused before any GPU work: a y that is not floating or not of rank 1 or 2, an empty batch, lengths out of range
+        (ValueError); a clip too short for one segment or with more than ms_max_segments segments (engine.BatchPlan's
+        ValueErrors); a gradient in a fast precision, or while the checkpoint's ms_sr differs from sr -- the resampler has no
+        backward -- (NotImplementedError; the plain call still works)."""
+        from .engine import DEFAULT_PRECISION, BatchPlan
+        from .melbank import resampled_lengths
+        if not torch.is_tensor(y) or not y.is_floating_point() or y.dim() not in (1, 2):
+            raise ValueError('expected y as a floating tensor of shape [N] or [B, N], got {}'.format(
+                '{} {}'.format(y.dtype, tuple(y.shape)) if torch.is_tensor(y) else type(y).__name__))
+        y2 = y if y.dim() == 2 else y.unsqueeze(0)
+        B, N = y2.shape
+        if B == 0 or N == 0:
+            raise ValueError('empty batch')
+        if lengths is None:
+            n = np.full(B, N, dtype=np.int64)
+        else:
+            n = np.asarray(lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else lengths).reshape(-1)
+            if n.size != B or not (np.issubdtype(n.dtype, np.integer) or (np.isfinite(n).all() and (n == np.floor(n)).all())):
+                raise ValueError('lengths must hold one whole number in [1, N] per clip')
+            n = n.astype(np.int64)
+            if (n < 1).any() or (n > N).any():
+                raise ValueError('lengths must hold one whole number in [1, N] per clip')
+        if int(sr) != sr or int(sr) < 1:
+            raise ValueError('sr must be one positive integer rate for the batch, got {}'.format(sr))
+        sr, args = int(sr), self._engine_args
+        if args is None:
+            raise RuntimeError('bind_args(checkpoint_args) must be called before the HIP engine is built')
+        rate = sr if args.get('ms_sr') is None else int(args['ms_sr'])
+        # the engine's audio_plan(n, sr), on the host: too short a clip and too many segments raise here
+        plan = BatchPlan(n if rate == sr else resampled_lengths(n, sr, rate)[0], int(rate * args['ms_hop_length']),
+                         int(args['ms_seg_hop_length']), args['ms_max_segments'])
+        dev = y.device if y.is_cuda else None
+        if not (torch.is_grad_enabled() and y.requires_grad):
+            eng = self.engine(dev)
+            return _score_audio(eng, y2.detach().to(eng.device, dtype=torch.float32), n, sr, plan)
+        from .input_grad import check_precision
+        check_precision(self._engine.precision if self._engine is not None
+                        else os.environ.get('NISQA_HIP_PRECISION') or DEFAULT_PRECISION)
+        if rate != sr:
+            raise NotImplementedError('the gradient with respect to the audio needs sr == ms_sr ({} != {}): the resampler has no '
+                                      'backward; the plain call works'.format(sr, rate))
+        eng = self.engine(dev)
+        # the Function sees the samples the kernels read: torch supplies the adjoint of the device / dtype / rank conversion
+        return _AudioFunction.apply(y2.to(eng.device, dtype=torch.float32), eng, n, sr, plan)
+
+
+def _pack_clips(y, lengths):
+    """y [B, N] on the device, lengths [B] -> the clips back to back [sum lengths] (no sample at n >= lengths[b] is read)"""
+    if (lengths == y.shape[1]).all():
+        return y.contiguous().reshape(-1)
+    return torch.cat([y[b, :int(n)] for b, n in enumerate(lengths)])
+
+
+def _score_audio(eng, y, lengths, sr, plan):
+    return eng.forward_audio(_pack_clips(y, lengths), lengths, sr, plan)
+
+
+class _AudioFunction(torch.autograd.Function):
+    """HipNisqa.forward_audio on the packed clips with grad_audio as the backward.  The forward is the inference path untouched; only
+    y and the lengths are kept, and the backward recomputes what it needs (the dB rows and the network)."""
+
+    @staticmethod
+    def forward(ctx, y, eng, lengths, sr, plan):
+        ctx.eng, ctx.lengths, ctx.sr = eng, lengths, sr
+        ctx.save_for_backward(y)
+        return _score_audio(eng, y, lengths, sr, plan)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        y, = ctx.saved_tensors
+        eng, lengths, sr = ctx.eng, ctx.lengths, ctx.sr
+        d = eng.grad_audio(_pack_clips(y, lengths), eng.plan(lengths, sr), sr, grad_out)
+        if (lengths == y.shape[1]).all():
+            return d.view_as(y), None, None, None, None
+        dy, o = torch.zeros_like(y), 0                       # exact zeros beyond lengths[b], whatever y holds there
+        for b, n in enumerate(lengths):
+            dy[b, :int(n)] = d[o:o + int(n)]
+            o += int(n)
+        return dy, None, None, None, None
+
 
 class _SegmentsFunction(torch.autograd.Function):
     """An engine's forward_segments (HipNisqa, HipNisqaDE) with its grad_segments as the backward.  The forward is the inference path untouched;

@@ -555,6 +555,77 @@ class HipNisqa(object):
             self._input_grad = (input_grad.InputGrad if self.arch == 0 else input_grad.InputGradLSTM)(self, self._state_dict)
         return self._input_grad(x, n_wins, grad_out)
 
+    # -- the gradient with respect to the audio samples (csrc/mel_bwd.hip) ----------------------------------
+    def segments_from_mel(self, mel_clamped, plan):
+        """clamped dB rows [TT, 48] -> the segment tensor x [B, L, 1, 48, 15] the segment-fed CNN reads, L = the largest n_wins:
+        segment k of clip b = frames seg_hop k .. seg_hop k + 14 (NISQA_lib.py:2266-2280); rows k >= n_wins[b] are zero.  Device
+        indexing, no arithmetic: the values are mel_clamped's bits."""
+        L = int(plan.n_wins.max())
+        k, j = np.arange(L)[None, :, None], np.arange(SEG_LEN)[None, None, :]
+        valid = k < plan.n_wins[:, None, None]
+        idx = np.where(valid, plan.frame_off[:-1, None, None].astype(np.int64) + self.seg_hop * k + j, 0)
+        rows = mel_clamped[torch.from_numpy(idx).to(self.device)]                           # [B, L, 15, 48]
+        rows = rows.masked_fill(~torch.from_numpy(valid[:, :, :1]).to(self.device)[..., None], 0.0)
+        return rows.permute(0, 1, 3, 2).unsqueeze(2).contiguous()
+
+    def segments_to_mel_bwd(self, dx, plan):
+        """The adjoint of segments_from_mel: dx [B, L, 1, 48, 15] (float32, contiguous; rows k >= n_wins[b] are never read)
+        -> d / d mel_clamped [TT, 48]; frames no segment holds get 0 (nisqa_segments_to_mel_bwd)."""
+        assert dx.dtype == torch.float32 and dx.is_cuda and dx.is_contiguous() and dx.shape[0] == plan.n_clips \
+            and tuple(dx.shape[2:]) == (1, 48, SEG_LEN) and dx.shape[1] >= int(plan.n_wins.max())
+        d = plan.to(self.device)
+        dmel = torch.empty((plan.total_frames, 48), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.nisqa_segments_to_mel_bwd(_ptr(dx), dx.shape[1], _ptr(d['n_wins']), _ptr(d['frame_off']), plan.n_clips,
+                                                      plan.total_frames, self.seg_hop, _ptr(dmel), self._stream()),
+                   'nisqa_segments_to_mel_bwd')
+        return dmel
+
+    def mel_bwd(self, pcm, plan, sr, g, mel_db, clip_floor):
+        """The backward of mel(pcm, plan, sr, clamp=True): g [TT, 48] = d L / d (clamped dB rows), mel_db / clip_floor what
+        mel(..., clamp=False) returned for the same pcm -> d L / d pcm, float32 [plan.total_samples].  Three launches
+        (nisqa_mel_db_bwd_gate, nisqa_mel_frame_bwd, nisqa_mel_overlap_add_bwd) around a workspace of total_frames * win floats;
+        the spectra are recomputed, nothing of the forward but its dB rows is read.  float32 samples only."""
+        assert pcm.dtype == torch.float32 and pcm.is_cuda and pcm.is_contiguous() and pcm.numel() == plan.total_samples
+        for t in (g, mel_db):
+            assert t.dtype == torch.float32 and t.is_cuda and t.is_contiguous() and tuple(t.shape) == (plan.total_frames, 48)
+        assert clip_floor.dtype == torch.float32 and clip_floor.numel() == plan.n_clips
+        mt = self.mel_tables(sr)
+        d = plan.to(self.device)
+        cfg, st = ctypes.byref(mt['cfg']), self._stream()
+        dm = torch.empty_like(mel_db)
+        _lib.check(self.lib.nisqa_mel_db_bwd_gate(_ptr(g), _ptr(mel_db), _ptr(clip_floor), _ptr(d['frame_off']), plan.n_clips,
+                                                  plan.total_frames, cfg, _ptr(dm), st), 'nisqa_mel_db_bwd_gate')
+        ws = torch.empty(int(self.lib.nisqa_mel_bwd_workspace_bytes(plan.total_frames, mt['cfg'].win)), dtype=torch.uint8,
+                         device=self.device)
+        _lib.check(self.lib.nisqa_mel_frame_bwd(_ptr(pcm), _ptr(d['clip_off']), _ptr(d['frame_off']), plan.n_clips, plan.total_frames,
+                                                cfg, _ptr(mt['window']), _ptr(mt['twiddle']), _ptr(mt['band_start']),
+                                                _ptr(mt['band_len']), _ptr(mt['band_woff']), _ptr(mt['band_w']), _ptr(dm), _ptr(ws),
+                                                ws.numel(), st), 'nisqa_mel_frame_bwd')
+        dpcm = torch.empty(plan.total_samples, dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.nisqa_mel_overlap_add_bwd(_ptr(ws), _ptr(d['clip_off']), _ptr(d['frame_off']), plan.n_clips,
+                                                      plan.total_frames, plan.total_samples, cfg, _ptr(dpcm), st),
+                   'nisqa_mel_overlap_add_bwd')
+        return dpcm
+
+    def grad_audio(self, pcm, plan, sr, grad_out):
+        """The backward of forward_pcm in precision 'f32' / 'bf16x6': pcm float32 [plan.total_samples] at rate ``sr`` (the rate the
+        spectrogram is computed at: the resampler of ms_sr has no backward), grad_out [B, heads]
+        -> d (sum grad_out * forward_pcm(pcm, plan, sr)) / d pcm, float32 [plan.total_samples].
+        Nothing is kept from the forward: the dB rows are recomputed (mel, unclamped, with clip_floor), the clamped segment tensor
+        is cut from them on the device, grad_segments (a recomputation of the network) gives d / d x, and the
+        segment adjoint and the mel backward carry it to the samples.  The segment-fed and the frame-fed CNN give the same bits
+        for the same window, so the gradient belongs to the values forward_pcm returned."""
+        from . import input_grad
+        input_grad.check_precision(self.precision)
+        assert pcm.dtype == torch.float32, 'int16 PCM has no gradient'
+        pcm = pcm.detach().contiguous()
+        mel_db, floor = self.mel(pcm, plan, sr, clamp=False)
+        clip_of_frame = torch.from_numpy(np.repeat(np.arange(plan.n_clips), plan.T)).to(self.device)
+        x = self.segments_from_mel(torch.maximum(mel_db, floor[clip_of_frame][:, None]), plan)
+        dx = self.grad_segments(x, plan.n_wins, grad_out)
+        del x
+        return self.mel_bwd(pcm, plan, sr, self.segments_to_mel_bwd(dx, plan), mel_db, floor)
+
     # -- nisqa_tts.tar stages ------------------------------------------------------------------------
     def cnn_std(self, mel_tm, clip_floor, plan):
         """StandardCNN + fc_out -> feat20 [NP, 20]"""

@@ -192,6 +192,11 @@ TRAIN_SYMBOLS = {
     'nisqa_conv1_segments_dgrad': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_p, c_p, c_p]),
     'nisqa_bn_eval_act_maxpool2_fwd': (ctypes.c_int, [c_p] * 5 + [c_i32] * 5 + [c_p] * 3),
     'nisqa_bn_eval_act_maxpool2_bwd': (ctypes.c_int, [c_p] * 7 + [c_i32] * 5 + [c_p] * 2),
+    'nisqa_segments_to_mel_bwd': (ctypes.c_int, [c_p, c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p]),
+    'nisqa_mel_db_bwd_gate': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_i32, c_i32, ctypes.POINTER(MelCfg), c_p, c_p]),
+    'nisqa_mel_bwd_workspace_bytes': (ctypes.c_int64, [c_i32, c_i32]),
+    'nisqa_mel_frame_bwd': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, ctypes.POINTER(MelCfg)] + [c_p] * 8 + [c_i64, c_p]),
+    'nisqa_mel_overlap_add_bwd': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, c_i64, ctypes.POINTER(MelCfg), c_p, c_p]),
 }
 
 _lib = None
