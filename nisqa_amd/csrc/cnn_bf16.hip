@@ -37,6 +37,11 @@
 //     holds a higher clock on that shape, and a lane then owns four consecutive channels of a pixel, so its three terms leave as
 //     three 8-byte stores instead of twelve 16-bit ones; conv4's pixel <-> column map keeps the 12 x 5 -> 6 x 3 pool in-lane but
 //     for two DPP row shifts (profiles/r13_cnn_t16_ab.txt: kernel -4.1 %, clock64 ticks +1.4 %, shader clock +4.1 %).
+//     With one wave per SIMD nothing hides what stands outside a K loop either, so the three-term form also (profiles/
+//     r14_cnn_epilogue_ab.txt) runs conv1 + pool as a software pipeline, the MFMAs of the next iteration between the VALU instructions
+//     of this one's pooling epilogue (NQ_C1_PIPE), and stores the A1 and A2 term planes as 32-bit words of a channel pair after one
+//     quad_perm exchange with lane n ^ 1 (NQ_CPAIR, lds_store_terms2_cpair): 63 + 45 word stores where there were 126 + 90 half-word
+//     ones.  Same values, same splits: the features carry the bits of the half-word form.
 // What bounds it (tools/micro/issue2.hip): a wave hides <= 5 other instructions behind a 32x32x16 MFMA
 // (<= 2 behind a 16x16x32) and a VALU-only stream issues one instruction per ~5 cycles, so every instruction outside the
 // MFMA shadows counts.  Hence: LDS by 32-bit addresses (no 64-bit pointer arithmetic), lane-static tap masks instead of
@@ -129,6 +134,7 @@ NQ_DEV void cnn_front_split_body(
     constexpr bool X6 = FMT == NQ_FMT_BF16X6, F16 = FMT == NQ_FMT_F16X3 || FMT == NQ_FMT_F16X4;
     constexpr int T = X6 ? 3 : 2;                         // terms per operand = planes per tensor
     constexpr bool T16_3 = X6 && (NQ_T16 & 1), T16_4 = X6 && (NQ_T16 & 2);
+    constexpr bool CP1 = X6 && (NQ_CPAIR & 1), CP2 = X6 && (NQ_CPAIR & 2);   // A1 / A2 stored as words of a channel pair
     static_assert(!P3 || FMT == NQ_FMT_BF16X3, "the fp32 copy of the pooled conv4 tensor is a bf16x3 debug output");
     // fragment blob of the term count: CNNB_ (two terms, also the CNNH_ blob of the f16 formats) or CNNX_ (three)
     constexpr int W1_ = X6 ? CNNX_W1 : CNNB_W1, W2_ = X6 ? CNNX_W2 : CNNB_W2, W3_ = X6 ? CNNX_W3 : CNNB_W3, W4_ = X6 ? CNNX_W4 : CNNB_W4,
@@ -227,6 +233,7 @@ NQ_DEV void cnn_front_split_body(
 
     const int i = lane & 31, hfi = (i >> 2) & 1, qi = (i & 3) + 4 * (i >> 3);
     const int n = lane & 31, hf = lane >> 5, h = lane >> 5;
+    const bool odd = (lane & 1) != 0;                     // CP1 / CP2: the lane of the odd channel of a pair
 
     // ---- conv1 1->16 + pool 48x15 -> 24x7 on the matrix pipe, two output pixels per row.  A row = the mel pair
     //      (m0, m0 + 1) of one frame x; N = 32 = (channel c, pair member dm); K = 12 of 16 = (frame tap kx, mel m0 - 1 +
@@ -260,14 +267,19 @@ NQ_DEV void cnn_front_split_body(
         const bool is_b = (n & 16) != 0;
         const unsigned mb = is_b ? ~0u : 0u;             // bit select (v_bfi_b32): a ternary on r[] becomes an indexed stack array
         unsigned wr = R + (12 * hf * 7) * FB_RS1 + (n & 15) * 2 + (is_b ? FB_RS1 : 0);
-        for (int g2 = 0; g2 < 6; ++g2) {
-            f32x16 acc[2][1];
+        // CP1 (lds_store_terms2_cpair): the lane's 7 values of an iteration are the pixels 2 kk (+ 1 in lane group dm = 1) of its channel;
+        // values (kk, kk + 1) pair up within the iteration, value 6 of an even iteration waits for value 6 of the next one (14 pixels on)
+        const unsigned wrc = R + (12 * hf * 7) * FB_RS1 + (n & 14) * 2 + (is_b ? FB_RS1 : 0);
+        const unsigned wrp = wrc + (odd ? 2 * FB_RS1 : 0), wrq = wrc + (odd ? 14 * FB_RS1 : 0);
+        float fin6 = 0.f;
+        // an iteration's operand reads and MFMAs: acc = the conv1 output of its two mel pairs
+        auto c1_mma = [&](f32x16 (&acc)[2][1], unsigned ra, unsigned rb) {
             f32x4 xa[2][T];
 #pragma unroll
             for (int tt = 0; tt < 2; ++tt)
 #pragma unroll
                 for (int t = 0; t < T; ++t) {              // dword reads (ds_read2_b32): the pairs are only 4-byte aligned
-                    const unsigned pa = rd_a + 4 * tt + t * FB_PPLANE, pq = rd_b + 4 * tt + t * FB_PPLANE;
+                    const unsigned pa = ra + 4 * tt + t * FB_PPLANE, pq = rb + 4 * tt + t * FB_PPLANE;
                     xa[tt][t] = f32x4{__uint_as_float(lds_ld32(pa)), __uint_as_float(lds_ld32(pa + 4)),
                                       __uint_as_float(lds_ld32(pq)), __uint_as_float(lds_ld32(pq + 4))};
                 }
@@ -285,6 +297,9 @@ NQ_DEV void cnn_front_split_body(
                 acc[0][0] = mfma32_fmt<FMT>(xa[0][0], w[1], acc[0][0]); acc[1][0] = mfma32_fmt<FMT>(xa[1][0], w[1], acc[1][0]);
                 acc[0][0] = mfma32_fmt<FMT>(xa[0][0], w[0], acc[0][0]); acc[1][0] = mfma32_fmt<FMT>(xa[1][0], w[0], acc[1][0]);
             }
+        };
+        // its pooling epilogue: the 14 pooled values of iteration g2 into A1 at w (the lane's first pixel of the iteration)
+        auto c1_pool = [&](const f32x16 (&acc)[2][1], unsigned w, int g2) {
             // ReLU(. + shift) is monotone, so it is applied before the pair maximum, which is then taken on non-negative
             // floats -- as unsigned integers
             unsigned r[14];
@@ -304,11 +319,44 @@ NQ_DEV void cnn_front_split_body(
                 const unsigned own = (r[2 * kk + 1] & mb) | (r[2 * kk] & ~mb);
                 fin[kk] = __uint_as_float(max(own, got[kk]));
             }
+            if constexpr (CP1) {
 #pragma unroll
-            for (int kk = 0; kk < 6; kk += 2) lds_store_pair_fmt<FMT>(wr + 2 * kk * FB_RS1, wr + 2 * (kk + 1) * FB_RS1, FB_P1, fin[kk], fin[kk + 1], ms1);
-            lds_store_one_fmt<FMT>(wr + 12 * FB_RS1, FB_P1, fin[6], ms1);
-            rd_a += 8; rd_b += 8;                          // mel m0 = 2 gl, gl = 12 hfi + 2 g2 + tt
-            wr += 14 * FB_RS1;
+                for (int kk = 0; kk < 6; kk += 2) lds_store_terms2_cpair<T>(wrp + (14 * g2 + 2 * kk) * FB_RS1, FB_P1, fin[kk], fin[kk + 1], odd);
+                if (g2 & 1) lds_store_terms2_cpair<T>(wrq + (14 * (g2 - 1) + 12) * FB_RS1, FB_P1, fin6, fin[6], odd);
+                else fin6 = fin[6];
+            } else {
+#pragma unroll
+                for (int kk = 0; kk < 6; kk += 2) lds_store_pair_fmt<FMT>(w + 2 * kk * FB_RS1, w + 2 * (kk + 1) * FB_RS1, FB_P1, fin[kk], fin[kk + 1], ms1);
+                lds_store_one_fmt<FMT>(w + 12 * FB_RS1, FB_P1, fin[6], ms1);
+            }
+        };
+        if constexpr (X6 && NQ_C1_PIPE) {
+            // software pipeline (one wave per SIMD: nobody else fills the matrix pipe's latency): the reads and the 12 MFMAs of iteration
+            // g2 + 1 ride between the VALU instructions of iteration g2's epilogue, one MFMA per NQ_C1_PIPE of them
+            f32x16 acc[2][2][1];
+            c1_mma(acc[0], rd_a, rd_b);
+#pragma unroll
+            for (int g2 = 0; g2 < 6; ++g2) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (g2 + 1 < 6) c1_mma(acc[(g2 + 1) & 1], rd_a + 8 * (g2 + 1), rd_b + 8 * (g2 + 1));
+                c1_pool(acc[g2 & 1], wr + 14 * g2 * FB_RS1, g2);
+                if (g2 + 1 < 6) {
+#pragma unroll
+                    for (int i = 0; i < 12; ++i) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        __builtin_amdgcn_sched_group_barrier(0x002, NQ_C1_PIPE, 0);
+                    }
+                }
+            }
+        } else {
+#pragma unroll
+            for (int g2 = 0; g2 < 6; ++g2) {
+                f32x16 acc[2][1];
+                c1_mma(acc, rd_a, rd_b);
+                c1_pool(acc, wr, g2);
+                rd_a += 8; rd_b += 8;                      // mel m0 = 2 gl, gl = 12 hfi + 2 g2 + tt
+                wr += 14 * FB_RS1;
+            }
         }
         if (F16) { m_in = wave_max_nonneg(ms1) * pow2_f32(-e1); e_in = e1; }
     }
@@ -351,6 +399,7 @@ NQ_DEV void cnn_front_split_body(
             tn = tn2 * pow2_f32(e2);
         }
         const unsigned wr = R + (6 * hf * 5) * FB_RS2 + n * 2;
+        const unsigned wrp = R + (6 * hf * 5) * FB_RS2 + (n & 30) * 2 + (odd ? FB_RS2 : 0);   // CP2: the lane's word of the channel pair
 #pragma unroll
         for (int k2 = 0; k2 < 30; k2 += 2) {              // pooled pixel k = gl * 5 + bb, two per packed split
             float pv[2];
@@ -367,7 +416,8 @@ NQ_DEV void cnn_front_split_body(
                     }
                 pv[e] = epi_fmt<FMT>(mx, c2, tn);
             }
-            lds_store_pair_fmt<FMT>(wr + k2 * FB_RS2, wr + (k2 + 1) * FB_RS2, FB_P2, pv[0], pv[1], ms2);
+            if constexpr (CP2) lds_store_terms2_cpair<T>(wrp + k2 * FB_RS2, FB_P2, pv[0], pv[1], odd);
+            else lds_store_pair_fmt<FMT>(wr + k2 * FB_RS2, wr + (k2 + 1) * FB_RS2, FB_P2, pv[0], pv[1], ms2);
         }
         if (F16) { m_in = wave_max_nonneg(ms2) * pow2_f32(-e2); e_in = e2; }
     }

@@ -285,6 +285,33 @@ NQ_DEV void lds_store_terms4(unsigned a, int plane, f32x4 v) {
 #pragma unroll
     for (int t = 0; t < T; ++t) lds_st64(a + t * plane, u32x2{lo[t], hi[t]});
 }
+// NQ_CPAIR: which pooling epilogues of cnn_front_bf16x6_kernel store their term planes as 32-bit words of a channel pair -- conv1's
+// A1 (bit 0), conv2's A2 (bit 1) -- instead of 16-bit halves of a pixel pair (lds_store_terms2).  0: the half-word form.
+#ifndef NQ_CPAIR
+#define NQ_CPAIR 3
+#endif
+// NQ_C1_PIPE: conv1 + pool of cnn_front_bf16x6_kernel as a software pipeline -- the operand reads and the 12 MFMAs of iteration g + 1
+// are issued between the VALU instructions of iteration g's pooling epilogue, one MFMA per NQ_C1_PIPE of them (sched_group_barrier;
+// hipcc keeps MFMAs and epilogue apart on its own), on a second pair of accumulator tiles.  0: one iteration after the other.
+// profiles/r14_cnn_epilogue_ab.txt: conv1 + pool 9 374 -> 8 040 clock64 ticks per wave; spacings 6 / 8 / 10 / 14 within 2 % of each other.
+#ifndef NQ_C1_PIPE
+#define NQ_C1_PIPE 8
+#endif
+// lds_store_terms2 where lanes n and n ^ 1 hold ADJACENT CHANNELS (even lane = even channel) of the same two pixels: one quad_perm
+// exchange per value and the even lane holds pixel 0 of both channels, the odd lane pixel 1 of both -- ONE 4-byte store per plane and
+// lane instead of two 2-byte ones, and no two lanes write the halves of one word.  `a`: the lane's own word, channel c & ~1 of pixel
+// 0 (even lane) or pixel 1 (odd lane).  The split is elementwise: the stored bits are those of lds_store_terms2.  All lanes active.
+template <int T>
+NQ_DEV void lds_store_terms2_cpair(unsigned a, int plane, float v0, float v1, bool odd) {
+    const int i0 = (int)__float_as_uint(v0), i1 = (int)__float_as_uint(v1);
+    // quad_perm [1, 0, 3, 2]: lane n ^ 1 (every lane has a source: no old value to keep, so no copy ahead of the DPP move)
+    const float g0 = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, i0, 0xB1, 0xf, 0xf, true));
+    const float g1 = __uint_as_float((unsigned)__builtin_amdgcn_update_dpp(0, i1, 0xB1, 0xf, 0xf, true));
+    unsigned t[T];
+    split2t<T>(odd ? g1 : v0, odd ? v1 : g0, t);
+#pragma unroll
+    for (int q = 0; q < T; ++q) lds_st32(a + q * plane, t[q]);
+}
 // conv_k_bf16 for T terms: fragments [step][NT][T][64 lanes][8 bf16], activation planes PLANE bytes apart; A rows always
 // one step ahead (this form runs one wave per SIMD on the 512-register budget).  FENCE: a sched_barrier behind the step's
 // requests -- hipcc's scheduler otherwise sinks them to just before their use, and with ONE wave per SIMD nobody fills the
