@@ -520,6 +520,19 @@ int nisqa_mel_frame_bwd(const float* pcm, const int64_t* clip_off, const int32_t
                         int64_t ws_bytes, void* stream);
 int nisqa_mel_overlap_add_bwd(const float* ws, const int64_t* clip_off, const int32_t* frame_off, int32_t n_clips,
                               int32_t total_frames, int64_t total_samples, const nisqa_mel_cfg* cfg, float* dpcm, void* stream);
+/* The forward counterpart of nisqa_segments_to_mel_bwd: the clamped segment tensor the segment-fed CNN reads, cut on the device
+ * from the UNCLAMPED dB rows and the clip floors of nisqa_mel_db + nisqa_mel_finalize(clamp = 0).
+ *   x[b][k][0][m][j] = fmaxf(mel_db[frame_off[b] + seg_hop k + j][m], clip_floor[b])   for k < n_wins[b], m < 48, j < 15
+ *   x[b][k][0][m][j] = 0                                                               for n_wins[b] <= k < L
+ * x is [n_clips][L][1][48][15] and may be uninitialised: every element is written once, by one thread (no atomics: two calls
+ * give the same bits); nothing behind it is touched.  No arithmetic but the clamp: the values are mel_db's or clip_floor's bits.
+ * The caller keeps L >= the largest n_wins[b] (a smaller L cuts the first L segments of a clip) and the plan's invariant
+ * seg_hop (n_wins[b] - 1) + 15 <= frame_off[b + 1] - frame_off[b]; a segment that would read past its clip's frames is written
+ * as zeros instead.  Offsets into x are 64-bit.  mel_db and x must be 16-byte aligned (the rows move as 128-bit words).
+ * NULL pointers, n_clips <= 0, total_frames <= 0, n_clips > total_frames, seg_hop < 1, L < 1, n_clips * L >= 2^31 or a misaligned
+ * mel_db / x return NISQA_ERR_ARG before any launch. */
+int nisqa_mel_segments_fwd(const float* mel_db, const float* clip_floor, const int32_t* frame_off, const int32_t* n_wins,
+                           int32_t n_clips, int32_t total_frames, int32_t seg_hop, int32_t L, float* x, void* stream);
 
 #ifdef __cplusplus
 }

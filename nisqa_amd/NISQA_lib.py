@@ -217,22 +217,7 @@ class _NisqaBase(nn.Module):
         backward -- (NotImplementedError; the plain call still works)."""
         from .engine import DEFAULT_PRECISION, BatchPlan
         from .melbank import resampled_lengths
-        if not torch.is_tensor(y) or not y.is_floating_point() or y.dim() not in (1, 2):
-            raise ValueError('expected y as a floating tensor of shape [N] or [B, N], got {}'.format(
-                '{} {}'.format(y.dtype, tuple(y.shape)) if torch.is_tensor(y) else type(y).__name__))
-        y2 = y if y.dim() == 2 else y.unsqueeze(0)
-        B, N = y2.shape
-        if B == 0 or N == 0:
-            raise ValueError('empty batch')
-        if lengths is None:
-            n = np.full(B, N, dtype=np.int64)
-        else:
-            n = np.asarray(lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else lengths).reshape(-1)
-            if n.size != B or not (np.issubdtype(n.dtype, np.integer) or (np.isfinite(n).all() and (n == np.floor(n)).all())):
-                raise ValueError('lengths must hold one whole number in [1, N] per clip')
-            n = n.astype(np.int64)
-            if (n < 1).any() or (n > N).any():
-                raise ValueError('lengths must hold one whole number in [1, N] per clip')
+        y2, n = _audio_args(y, lengths)
         if int(sr) != sr or int(sr) < 1:
             raise ValueError('sr must be one positive integer rate for the batch, got {}'.format(sr))
         sr, args = int(sr), self._engine_args
@@ -257,11 +242,43 @@ class _NisqaBase(nn.Module):
         return _AudioFunction.apply(y2.to(eng.device, dtype=torch.float32), eng, n, sr, plan)
 
 
+def _audio_args(y, lengths, name='y', size='N'):
+    """The checks of forward_audio on one batch of clips: y [N] or [B, N] floating, lengths [B] whole numbers in [1, N] or None
+    -> (y as [B, N], the lengths as int64 [B]).  Raises ValueError; no device is touched beyond reading lengths."""
+    if not torch.is_tensor(y) or not y.is_floating_point() or y.dim() not in (1, 2):
+        raise ValueError('expected {} as a floating tensor of shape [{}] or [B, {}], got {}'.format(
+            name, size, size, '{} {}'.format(y.dtype, tuple(y.shape)) if torch.is_tensor(y) else type(y).__name__))
+    y2 = y if y.dim() == 2 else y.unsqueeze(0)
+    B, N = y2.shape
+    if B == 0 or N == 0:
+        raise ValueError('empty batch')
+    if lengths is None:
+        return y2, np.full(B, N, dtype=np.int64)
+    n = np.asarray(lengths.detach().cpu().numpy() if torch.is_tensor(lengths) else lengths).reshape(-1)
+    if n.size != B or not (np.issubdtype(n.dtype, np.integer) or (np.isfinite(n).all() and (n == np.floor(n)).all())):
+        raise ValueError('lengths must hold one whole number in [1, {}] per clip'.format(size))
+    n = n.astype(np.int64)
+    if (n < 1).any() or (n > N).any():
+        raise ValueError('lengths must hold one whole number in [1, {}] per clip'.format(size))
+    return y2, n
+
+
 def _pack_clips(y, lengths):
     """y [B, N] on the device, lengths [B] -> the clips back to back [sum lengths] (no sample at n >= lengths[b] is read)"""
     if (lengths == y.shape[1]).all():
         return y.contiguous().reshape(-1)
     return torch.cat([y[b, :int(n)] for b, n in enumerate(lengths)])
+
+
+def _unpack_clips(d, y, lengths):
+    """The adjoint of _pack_clips: d [sum lengths] -> [B, N] in y's shape, exact zeros at n >= lengths[b] whatever y holds there"""
+    if (lengths == y.shape[1]).all():
+        return d.view_as(y)
+    dy, o = torch.zeros_like(y), 0
+    for b, n in enumerate(lengths):
+        dy[b, :int(n)] = d[o:o + int(n)]
+        o += int(n)
+    return dy
 
 
 def _score_audio(eng, y, lengths, sr, plan):
@@ -284,13 +301,32 @@ class _AudioFunction(torch.autograd.Function):
         y, = ctx.saved_tensors
         eng, lengths, sr = ctx.eng, ctx.lengths, ctx.sr
         d = eng.grad_audio(_pack_clips(y, lengths), eng.plan(lengths, sr), sr, grad_out)
-        if (lengths == y.shape[1]).all():
-            return d.view_as(y), None, None, None, None
-        dy, o = torch.zeros_like(y), 0                       # exact zeros beyond lengths[b], whatever y holds there
-        for b, n in enumerate(lengths):
-            dy[b, :int(n)] = d[o:o + int(n)]
-            o += int(n)
-        return dy, None, None, None, None
+        return _unpack_clips(d, y, lengths), None, None, None, None
+
+
+class _AudioFunctionDE(torch.autograd.Function):
+    """HipNisqaDE.forward_audio on the 2B packed clips (degraded, then reference) with its grad_audio as the backward.  The forward
+    is the inference path untouched; only the two sample tensors are kept (the lengths and the plan, host metadata, ride on
+    ctx), and the backward recomputes what it needs.  A side that needs no gradient gets None, and its mel backward is not run."""
+
+    @staticmethod
+    def forward(ctx, y_deg, y_ref, eng, n_deg, n_ref, sr, plan):
+        ctx.eng, ctx.n_deg, ctx.n_ref, ctx.sr, ctx.plan = eng, n_deg, n_ref, sr, plan
+        ctx.save_for_backward(y_deg, y_ref)
+        return _score_audio_de(eng, y_deg, y_ref, n_deg, n_ref, sr, plan)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        y_deg, y_ref = ctx.saved_tensors
+        pcm = torch.cat([_pack_clips(y_deg, ctx.n_deg), _pack_clips(y_ref, ctx.n_ref)])
+        d = ctx.eng.grad_audio(pcm, ctx.plan, ctx.sr, grad_out, ctx.needs_input_grad[:2])
+        return tuple(_unpack_clips(dk, y, n) if dk is not None else None
+                     for dk, y, n in zip(d, (y_deg, y_ref), (ctx.n_deg, ctx.n_ref))) + (None,) * 5
+
+
+def _score_audio_de(eng, y_deg, y_ref, n_deg, n_ref, sr, plan):
+    return eng.forward_audio(torch.cat([_pack_clips(y_deg, n_deg), _pack_clips(y_ref, n_ref)]), n_deg, n_ref, sr, plan)
 
 
 class _SegmentsFunction(torch.autograd.Function):
@@ -409,6 +445,63 @@ class NISQA_DE(nn.Module):
                         else os.environ.get('NISQA_HIP_PRECISION') or DEFAULT_PRECISION)        # refused before any GPU work
         eng = self.engine(dev)
         return _SegmentsFunction.apply(x.to(eng.device, dtype=torch.float32).contiguous(), eng, n)
+
+    def forward_audio(self, y_deg, y_ref, sr, lengths_deg=None, lengths_ref=None):
+        """Full-reference scores of in-memory audio: y_deg [N] or [B, N] the degraded clips, y_ref [M] or [B, M] their clean
+        references -- floating tensors of the same rank and the same B on any device (both on one GPU if both are on a GPU), N and
+        M independent -- at one integer rate ``sr``; lengths_deg / lengths_ref [B] whole numbers in [1, N] / [1, M] (default: the
+        full row) -> [B, 1] on the engine's device.  Samples at n >= lengths[b] are never read.  Both sides are packed back to
+        back, the degraded clips first, and go through the engine's forward_pcm (through its resampler first when the checkpoint
+        sets ms_sr): the result is HipNisqaDE.forward_pcm's, bit for bit, in every engine precision.
+        When gradients are enabled and y_deg or y_ref requires one, the result carries a grad_fn and backward delivers d / d y_deg
+        and d / d y_ref, each in its input's shape, dtype and device, exact zeros at n >= lengths[b] whatever the input holds
+        there (engine.HipNisqaDE.grad_audio: the mel backward and the segment adjoint behind InputGradDE, in the 2B-clip layout
+        end to end; precisions 'f32' and 'bf16x6').  A side that requires no gradient gets none, and its mel backward and CNN
+        backward are not run.  The values are the plain call's, bit for bit; there is no double backward and the parameters get
+        no gradient.
+        Hard alignment (de_align_apply=hard): the argmax carries no gradient.  The backward recomputes the network and takes the
+        recomputation's own argmax (InputGradDE.last_idx); at a near-tie of two scores that may differ from the choice of the
+        fused inference chain that produced the score (DESIGN.md 4.8 "argmax deviation"), and the gradient is then that of the
+        recomputed choice.
+        Refused before any GPU work: a side that is not floating or not of rank 1 or 2, sides of different rank or B, on different
+        GPUs, an empty batch, lengths out of range (ValueError); a clip of either side too short for one segment or with more
+        than ms_max_segments segments (engine.BatchPlan's ValueErrors); a gradient in a fast precision, or while the
+        checkpoint's ms_sr differs from sr -- the resampler has no backward -- (NotImplementedError; the plain call still
+        works)."""
+        from .engine import DEFAULT_PRECISION, BatchPlan
+        from .melbank import resampled_lengths
+        d2, n_deg = _audio_args(y_deg, lengths_deg, 'y_deg', 'N')
+        r2, n_ref = _audio_args(y_ref, lengths_ref, 'y_ref', 'M')
+        if y_deg.dim() != y_ref.dim() or d2.shape[0] != r2.shape[0]:
+            raise ValueError('y_deg and y_ref must have the same rank and the same number of clips, got {} and {}'.format(
+                tuple(y_deg.shape), tuple(y_ref.shape)))
+        if y_deg.is_cuda and y_ref.is_cuda and y_deg.device != y_ref.device:
+            raise ValueError('y_deg and y_ref are on different GPUs: {} and {}'.format(y_deg.device, y_ref.device))
+        if int(sr) != sr or int(sr) < 1:
+            raise ValueError('sr must be one positive integer rate for both sides, got {}'.format(sr))
+        sr, args = int(sr), self._engine_args
+        if args is None:
+            raise RuntimeError('bind_args(checkpoint_args) must be called before the HIP engine is built')
+        rate = sr if args.get('ms_sr') is None else int(args['ms_sr'])
+        # the engine's audio_plan(n_deg, n_ref, sr), on the host: too short a clip and too many segments raise here, on either side
+        n2 = np.concatenate([n_deg, n_ref])
+        plan = BatchPlan(n2 if rate == sr else resampled_lengths(n2, sr, rate)[0], int(rate * args['ms_hop_length']),
+                         int(args['ms_seg_hop_length']), args['ms_max_segments'])
+        dev = y_deg.device if y_deg.is_cuda else (y_ref.device if y_ref.is_cuda else None)
+        if not (torch.is_grad_enabled() and (y_deg.requires_grad or y_ref.requires_grad)):
+            eng = self.engine(dev)
+            to = lambda y: y.detach().to(eng.device, dtype=torch.float32)
+            return _score_audio_de(eng, to(d2), to(r2), n_deg, n_ref, sr, plan)
+        from .input_grad import check_precision
+        check_precision(self._engine.precision if self._engine is not None
+                        else os.environ.get('NISQA_HIP_PRECISION') or DEFAULT_PRECISION)
+        if rate != sr:
+            raise NotImplementedError('the gradient with respect to the audio needs sr == ms_sr ({} != {}): the resampler has no '
+                                      'backward; the plain call works'.format(sr, rate))
+        eng = self.engine(dev)
+        # the Function sees the samples the kernels read: torch supplies the adjoint of the device / dtype / rank conversion
+        to = lambda y: y.to(eng.device, dtype=torch.float32)
+        return _AudioFunctionDE.apply(to(d2), to(r2), eng, n_deg, n_ref, sr, plan)
 
 
 # ---------------------------------------------------------------------------------------------

@@ -14,6 +14,7 @@
 //                              d L / d x_n = w_n Re sum_{k <= 2048} (d L / d |X_k| X_k / |X_k|) e^(+2 pi i k n / 4096) -> ws [TT][win]
 //   nisqa_mel_overlap_add_bwd  per sample: the frames over each padded position that reflects onto it, gathered from ws
 //   nisqa_segments_to_mel_bwd  d L / d out [TT][48] from d L / d x [B][L][1][48][15]
+// and, for the way there, nisqa_mel_segments_fwd: the clamped segment tensor x [B][L][1][48][15] from the unclamped dB rows.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "common.hpp"
@@ -278,6 +279,55 @@ __global__ __launch_bounds__(256) void segments_to_mel_bwd_kernel(
     dmel[i] = acc;
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// unclamped dB rows [TT][48] + clip_floor -> x [n_clips][L][1][48][15]: clamp and cut segments (the forward of the kernel above)
+// ---------------------------------------------------------------------------------------------------------
+// One wave per row (b, k) of x, four rows per workgroup.  A segment's source is 15 consecutive rows of mel_db: 720 contiguous
+// floats, read as 180 128-bit words, lane after lane (three wave loads), clamped at the clip's floor and written to LDS at their
+// place in the destination [48][15]; the 720 floats of the destination are contiguous too and leave as 180 128-bit words, lane
+// after lane.  (The transposing LDS write is 32-bit: element (frame j, band m) goes to 15 m + j, at most two lanes of a group on
+// one bank.)  Rows k >= n_wins[b] -- and a segment that would read past its clip's frames, which a consistent plan never has --
+// are written as zeros.  Every element of x is written once, by one lane.
+#define MS_SEG (NISQA_N_MELS * 15)           // floats of one segment: 720
+#define MS_WORDS (MS_SEG / 4)                // 128-bit words of one segment: 180
+__global__ __launch_bounds__(256) void mel_segments_fwd_kernel(
+    const float* __restrict__ mel_db, const float* __restrict__ clip_floor, const int32_t* __restrict__ frame_off,
+    const int32_t* __restrict__ n_wins, int n_rows, int total_frames, int seg_hop, int L, float* __restrict__ x) {
+    __shared__ __attribute__((aligned(16))) float tile[4][MS_SEG];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + wave;                      // wave-uniform: row b * L + k of x
+    const bool in_x = r < n_rows;
+    bool cut = false;
+    if (in_x) {
+        const int b = r / L, k = r - b * L;
+        const int64_t f0 = frame_off[b] + (int64_t)seg_hop * k;
+        cut = k < n_wins[b] && frame_off[b] >= 0 && f0 + 15 <= frame_off[b + 1] && f0 + 15 <= total_frames;
+        if (cut) {
+            const float fl = clip_floor[b];
+            const f32x4* src = (const f32x4*)(mel_db + (int64_t)f0 * NISQA_N_MELS);
+#pragma unroll
+            for (int it = 0; it < 3; ++it) {
+                const int i = lane + 64 * it;
+                if (i < MS_WORDS) {
+                    const f32x4 v = src[i];
+                    const int j = i / 12, m = 4 * (i - 12 * j);
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) tile[wave][(m + e) * 15 + j] = fmaxf(v[e], fl);
+                }
+            }
+        }
+    }
+    __syncthreads();
+    if (!in_x) return;
+    f32x4* dst = (f32x4*)(x + (int64_t)r * MS_SEG);
+    const f32x4* t4 = (const f32x4*)tile[wave];
+#pragma unroll
+    for (int it = 0; it < 3; ++it) {
+        const int i = lane + 64 * it;
+        if (i < MS_WORDS) dst[i] = cut ? t4[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+}
+
 static bool mel_bwd_cfg_ok(const nisqa_mel_cfg* cfg) {
     return cfg && cfg->n_fft == MB_N && cfg->n_mels == NISQA_N_MELS && cfg->win >= 2 && cfg->win <= MB_N && cfg->hop >= 1 &&
            cfg->w_floats >= 1 && cfg->w_floats <= 8192 && cfg->amin_sq > 0.f;
@@ -335,5 +385,18 @@ extern "C" int nisqa_segments_to_mel_bwd(const float* dx, int32_t l_max, const i
     NQ_LAUNCH_BEGIN();
     hipLaunchKernelGGL(segments_to_mel_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, dx, l_max,
                        n_wins, frame_off, n_clips, total, seg_hop, dmel);
+    return NQ_LAUNCH_STATUS();
+}
+
+extern "C" int nisqa_mel_segments_fwd(const float* mel_db, const float* clip_floor, const int32_t* frame_off, const int32_t* n_wins,
+                                      int32_t n_clips, int32_t total_frames, int32_t seg_hop, int32_t L, float* x, void* stream) {
+    if (!mel_db || !clip_floor || !frame_off || !n_wins || !x || n_clips <= 0 || total_frames <= 0 || n_clips > total_frames ||
+        seg_hop < 1 || L < 1 || (int64_t)n_clips * L > 0x7fffffffLL - 3 || (int64_t)total_frames * NISQA_N_MELS > 0x7fffffffLL ||
+        ((uintptr_t)mel_db & 15) || ((uintptr_t)x & 15))
+        return NISQA_ERR_ARG;
+    const int n_rows = n_clips * L;
+    NQ_LAUNCH_BEGIN();
+    hipLaunchKernelGGL(mel_segments_fwd_kernel, dim3((unsigned)((n_rows + 3) / 4)), dim3(256), 0, (hipStream_t)stream, mel_db, clip_floor,
+                       frame_off, n_wins, n_rows, total_frames, seg_hop, L, x);
     return NQ_LAUNCH_STATUS();
 }

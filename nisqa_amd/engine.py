@@ -568,6 +568,26 @@ class HipNisqa(object):
         rows = rows.masked_fill(~torch.from_numpy(valid[:, :, :1]).to(self.device)[..., None], 0.0)
         return rows.permute(0, 1, 3, 2).unsqueeze(2).contiguous()
 
+    def segments_from_mel_db(self, mel_db, clip_floor, plan, L=None):
+        """segments_from_mel(torch.maximum(mel_db, floor of each frame's clip), plan) in one launch (nisqa_mel_segments_fwd): the
+        UNCLAMPED dB rows [TT, 48] and clip_floor [B] of mel(..., clamp=False) -> x [B, L, 1, 48, 15], L >= the largest n_wins
+        (default: that count); rows k >= n_wins[b] are exact zeros.  The same bits as the indexing path, without its index
+        upload, gather, mask and transposing copy."""
+        n_max = int(plan.n_wins.max())
+        L = n_max if L is None else int(L)
+        if L < n_max:
+            raise ValueError('L = {} is smaller than the largest segment count {}'.format(L, n_max))
+        assert mel_db.dtype == torch.float32 and mel_db.is_cuda and mel_db.is_contiguous() \
+            and tuple(mel_db.shape) == (plan.total_frames, 48)
+        assert clip_floor.dtype == torch.float32 and clip_floor.is_cuda and clip_floor.is_contiguous() \
+            and clip_floor.numel() == plan.n_clips
+        d = plan.to(self.device)
+        x = torch.empty((plan.n_clips, L, 1, 48, SEG_LEN), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.nisqa_mel_segments_fwd(_ptr(mel_db), _ptr(clip_floor), _ptr(d['frame_off']), _ptr(d['n_wins']),
+                                                   plan.n_clips, plan.total_frames, self.seg_hop, L, _ptr(x), self._stream()),
+                   'nisqa_mel_segments_fwd')
+        return x
+
     def segments_to_mel_bwd(self, dx, plan):
         """The adjoint of segments_from_mel: dx [B, L, 1, 48, 15] (float32, contiguous; rows k >= n_wins[b] are never read)
         -> d / d mel_clamped [TT, 48]; frames no segment holds get 0 (nisqa_segments_to_mel_bwd)."""
@@ -824,16 +844,73 @@ class HipNisqaDE(object):
         l >= n_wins[b, c] of channel c are exactly zero.  forward_segments keeps no activation, so this call recomputes the
         network operator by operator with its activations in HBM: it costs a second forward.  In hard mode the recomputation
         takes its own argmax (InputGradDE.last_idx), which at a near-tie of two scores may differ from the fused chain's."""
+        return self._grad()(x, n_wins, grad_out)
+
+    def _grad(self):
         from . import input_grad
         input_grad.check_precision(self.precision)
         if self._input_grad is None:
             self._input_grad = input_grad.InputGradDE(self, self.base._state_dict)
-        return self._input_grad(x, n_wins, grad_out)
+        return self._input_grad
 
     def forward_pcm(self, pcm, plan, sr, want_idx=False):
         """pcm: device tensor of the plan's 2B clips back to back (degraded, then reference; float32 or int16 PCM) -> [B, 1]"""
         assert pcm.is_cuda and pcm.numel() == plan.total_samples
         return self.forward_features(self.features(pcm, plan, sr), plan, want_idx)
+
+    def audio_plan(self, lengths_deg, lengths_ref, sr, names=None):
+        """plan() of 2B clips of rate ``sr`` as the network sees them (resampled to ms_sr when the checkpoint sets it)."""
+        return self.base.audio_plan(list(lengths_deg) + list(lengths_ref), sr, names)
+
+    def forward_audio(self, pcm, lengths_deg, lengths_ref, sr, plan):
+        """forward_pcm for 2B clips as the caller holds them, degraded clips first: resampled to ms_sr first when the checkpoint
+        asks for that, as forward_items does (``plan`` from audio_plan(lengths_deg, lengths_ref, sr))."""
+        b = self.base
+        return self.forward_pcm(b.resample(pcm, list(lengths_deg) + list(lengths_ref), sr), plan, b.rate(sr))
+
+    # -- the gradient with respect to both audio signals (DESIGN.md 4.8.3) -------------------------------------------------------
+    def grad_audio(self, pcm, plan, sr, grad_out, need=(True, True)):
+        """The backward of forward_pcm in precision 'f32' / 'bf16x6': pcm float32 [plan.total_samples], the plan's 2B clips back to
+        back (degraded, then reference) at the rate ``sr`` the spectrogram is computed at, grad_out [B, 1]
+        -> (d_deg, d_ref) = d (sum grad_out * forward_pcm(pcm, plan, sr)) / d pcm split at the first reference sample: float32
+        [sum lengths_deg] and [sum lengths_ref]; None for a side that ``need`` = (degraded, reference) does not name.
+        The 2B-clip layout is kept end to end: base.mel (unclamped rows + floors), the clamped segment tensor cut on the device
+        (nisqa_mel_segments_fwd), InputGradDE.packed -- no channel split, no concatenation --, the segment adjoint and the mel
+        backward.  The degraded clips are a prefix of pcm, of the dB rows, of the floors and of d / d mel, the reference clips
+        the suffix: with one side named, the CNN backward, the segment adjoint and the mel backward run on that side's view
+        under its own plan.  Hard alignment: the argmax carries no gradient, and the backward takes the recomputation's own
+        argmax (InputGradDE.last_idx), which at a near-tie of two scores may differ from the choice of the fused inference chain
+        that produced the score (DESIGN.md 4.8 "argmax deviation")."""
+        ig = self._grad()
+        need = (bool(need[0]), bool(need[1]))
+        B, b = plan.n_clips // 2, self.base
+        assert plan.n_clips == 2 * B and any(need) and pcm.dtype == torch.float32, 'int16 PCM has no gradient'
+        from .input_grad import _check_grad_out
+        _check_grad_out(grad_out, B, 1)
+        pcm = pcm.detach().contiguous()
+        g = grad_out.detach().to(self.device, dtype=torch.float32).contiguous()
+        mel_db, floor = b.mel(pcm, plan, sr, clamp=False)
+        x2 = b.segments_from_mel_db(mel_db, floor, plan)
+        n = np.stack([plan.n_wins[:B], plan.n_wins[B:]], 1).astype(np.int64)
+        dx2 = ig.packed(x2, n, g, need)
+        del x2
+        if all(need):
+            d = b.mel_bwd(pcm, plan, sr, b.segments_to_mel_bwd(dx2, plan), mel_db, floor)
+            return d[:int(plan.clip_off[B])], d[int(plan.clip_off[B]):]
+        side = 0 if need[0] else 1
+        sub = self._side_plan(plan, sr, side)
+        c, s, f = slice(side * B, side * B + B), int(plan.clip_off[B]), int(plan.frame_off[B])
+        rows, smp = (slice(0, f), slice(0, s)) if side == 0 else (slice(f, None), slice(s, None))
+        d = b.mel_bwd(pcm[smp], sub, sr, b.segments_to_mel_bwd(dx2[c], sub), mel_db[rows], floor[c].contiguous())
+        return (d, None) if side == 0 else (None, d)
+
+    def _side_plan(self, plan, sr, side):
+        """The plan of the B degraded (side 0) or reference (side 1) clips of a 2B-clip plan, built once per plan."""
+        subs = plan.__dict__.setdefault('_de_sides', {})
+        if side not in subs:
+            B = plan.n_clips // 2
+            subs[side] = self.base.plan(plan.lengths[side * B:side * B + B], sr)
+        return subs[side]
 
     def forward_items(self, items, names=None):
         """items: 2B host clips (samples int16 / float32, sr) -- the degraded clips, then the reference clips -> [B, 1] on the device.

@@ -29,7 +29,8 @@ pool=avg or max), whose grad_out is [B, 1]:
 
 ``InputGradDE`` is the same for NISQA_DE (x [B, L, 2, 48, 15], n_wins [B, 2], grad_out [B, 1]): InputGrad's operators around the
 alignment + fusion kernels of csrc/de_align.hip, hard (nisqa_de_align_fuse_packed / _bwd) or soft (nisqa_de_align_soft_packed /
-nisqa_de_align_soft_bwd) -- DESIGN.md 4.8.2.
+nisqa_de_align_soft_bwd) -- DESIGN.md 4.8.2.  Its ``packed`` entry takes and returns the 2B-clip layout the engine's audio path
+holds (degraded clips, then reference clips) and can leave out one side's CNN backward -- DESIGN.md 4.8.3.
 """
 import numpy as np
 import torch
@@ -89,8 +90,9 @@ class _EvalCNN(object):
             recs.append((z, arg))
         return recs, act.view(S, -1)
 
-    def _cnn_bwd_eval(self, recs, da, seg_off, B, S, L):
-        """d / d features [S][pixels * 64] -> d / d x [B, L, 1, 48, 15]; recs is emptied, layer by layer"""
+    def _cnn_bwd_eval(self, recs, da, seg_off, B, S, L, dx=None):
+        """d / d features [S][pixels * 64] -> d / d x [B, L, 1, 48, 15] (written into ``dx`` where one is given); recs is emptied,
+        layer by layer"""
         L_, st = self.lib, self._st()
         for i in range(6, 0, -1):
             ci, co = _CONV[i - 1]
@@ -109,7 +111,7 @@ class _EvalCNN(object):
             hi, wi = self._geo[i - 2][2]
             da = self._new(S, hi * wi, ci)
             self._conv_eval(1, i, dz, da, S)
-        dx = self._new(B, L, 1, 48, 15)
+        dx = self._new(B, L, 1, 48, 15) if dx is None else dx
         self._ck(L_.nisqa_conv1_segments_dgrad(_ptr(dz), _ptr(seg_off), B, L, _ptr(self.P['cnn.model.conv1.weight']), _ptr(dx), st),
                  'nisqa_conv1_segments_dgrad')
         return dx
@@ -255,21 +257,34 @@ class InputGradDE(InputGrad):
             pa, tiles_a = step_tables(L12)
             pd, tiles_d = step_tables(Lx)
             parts = [('a_' + k, v) for k, v in pa] + pd
-            parts += [('n_wins', L12.astype(np.int32)), ('tile_off', np.concatenate(([0], np.cumsum((Lx + 63) // 64))).astype(np.int32))]
+            parts += [('n_wins', L12.astype(np.int32)), ('tile_off', np.concatenate(([0], np.cumsum((Lx + 63) // 64))).astype(np.int32)),
+                      ('r_seg_off', np.concatenate(([0], np.cumsum(Ly))).astype(np.int32))]
             host, buf, tv = self._upload_tables(parts)
             self._tab_key, self._tab = key, (host, buf, tv, _ClipSet(L12, tv, tiles_a, 'a_'), _ClipSet(Lx, tv, tiles_d))
         return self._tab[2:]
 
     def __call__(self, x, n_wins, grad_out):
         """x [B, L, 2, 48, 15], n_wins [B, 2], grad_out [B, 1] -> d (sum grad_out * model(x, n_wins)) / d x, float32 on the
-        engine's device, in x's shape; rows l >= n_wins[b, c] of channel c exactly zero."""
+        engine's device, in x's shape; rows l >= n_wins[b, c] of channel c exactly zero.  The channels are copied into the
+        2B-clip layout, ``packed`` does the work, and the two halves of its result go side by side again."""
         n = check_segments(x, n_wins, 2)
-        B, L, F = x.shape[0], x.shape[1], self.fuse_width
+        B = x.shape[0]
         _check_grad_out(grad_out, B, 1)
         x = x.detach().to(self.device, dtype=torch.float32)
         x2 = torch.cat([x[:, :, 0:1], x[:, :, 1:2]], 0).contiguous()             # [2B, L, 1, 48, 15], degraded clips first
         g = grad_out.detach().to(self.device, dtype=torch.float32).contiguous()
-        n = np.asarray(n, dtype=np.int64)
+        dx = self.packed(x2, np.asarray(n, dtype=np.int64), g)
+        return torch.cat([dx[:B], dx[B:]], 2)
+
+    def packed(self, x2, n, g, need=(True, True)):
+        """The same in the 2B-clip layout, for callers that hold it (engine.HipNisqaDE.grad_audio): x2 [2B, L, 1, 48, 15] float32,
+        contiguous, on the engine's device, the B degraded clips first, then their B reference clips; n int64 [B, 2] (checked by
+        the caller); g [B, 1] float32 on the device -> dx2 in x2's layout.  need = (degraded, reference): the CNN backward runs
+        over the segments of the sides named -- the degraded segments are the leading Sx rows of every kept activation, the
+        reference segments the rest, so one side is a view -- and the half of dx2 of a side not named is exact zeros.  The
+        recomputation and the self-attention backward over both sides stay whole: either side's gradient needs them."""
+        B, L, F = n.shape[0], x2.shape[1], self.fuse_width
+        assert tuple(x2.shape) == (2 * B, L, 1, 48, 15) and x2.dtype == torch.float32 and x2.is_contiguous() and any(need)
         tv, cs_all, cs_deg = self._tables(n)
         L_, st, Sx = self.lib, self._st(), cs_deg.S
         off, nw = tv['a_seg_off'], tv['n_wins']
@@ -302,8 +317,14 @@ class InputGradDE(InputGrad):
                      'nisqa_de_align_fuse_bwd')
         dfeat = self._sa_bwd(rec1, dx1)                                          # [Sx + Sy][384]
         del rec1, x1, feat, dfused, dx1
-        dx = self._cnn_bwd_eval(recs, dfeat, cs_all.seg_off, 2 * B, cs_all.S, L)  # [2B, L, 1, 48, 15]
-        return torch.cat([dx[:B], dx[B:]], 2)
+        if all(need):
+            return self._cnn_bwd_eval(recs, dfeat, cs_all.seg_off, 2 * B, cs_all.S, L)   # [2B, L, 1, 48, 15]
+        # one side: its segments' rows of every activation, its clips' offsets counted from its first segment
+        lo, hi, c0, seg_off = (0, Sx, 0, cs_deg.seg_off) if need[0] else (Sx, cs_all.S, B, tv['r_seg_off'])
+        recs = [(z.view(cs_all.S, -1)[lo:hi], arg[lo:hi] if arg is not None else None) for z, arg in recs]
+        dx2 = torch.zeros((2 * B, L, 1, 48, 15), dtype=torch.float32, device=self.device)
+        self._cnn_bwd_eval(recs, dfeat[lo:hi], seg_off, B, hi - lo, L, dx=dx2[c0:c0 + B])
+        return dx2
 
 
 class InputGradLSTM(_EvalCNN, _FlatTrainer):

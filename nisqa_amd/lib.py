@@ -197,6 +197,7 @@ TRAIN_SYMBOLS = {
     'nisqa_mel_bwd_workspace_bytes': (ctypes.c_int64, [c_i32, c_i32]),
     'nisqa_mel_frame_bwd': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, ctypes.POINTER(MelCfg)] + [c_p] * 8 + [c_i64, c_p]),
     'nisqa_mel_overlap_add_bwd': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, c_i64, ctypes.POINTER(MelCfg), c_p, c_p]),
+    'nisqa_mel_segments_fwd': (ctypes.c_int, [c_p] * 4 + [c_i32] * 4 + [c_p, c_p]),
 }
 
 _lib = None
