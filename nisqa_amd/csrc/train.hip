@@ -89,8 +89,11 @@ struct tile_loader {
 // grouped GEMM: 256 threads = 4 waves, one 32 x 32 MFMA block each (2 x 2 waves on a 64 x 64 tile, or 4 x 1 on a
 // 128 x 32 tile for narrow outputs); the next K-tile travels global -> registers while the current one is multiplied
 // ---------------------------------------------------------------------------------------------------------
+template <int BM, int BN, int MT, int NT>
+constexpr int gemm_threads = (BM / (32 * MT)) * (BN / (32 * NT)) * 64;    // 4 or 8 waves; each owns MT x NT blocks of 32 x 32
+
 template <int BM, int BN, int MT, int NT, bool TA, bool TB>
-__global__ __launch_bounds__((BM / (32 * MT)) * (BN / (32 * NT)) * 64) void gemm_f32_kernel(const float* __restrict__ A, const float* __restrict__ B,
+__global__ __launch_bounds__((gemm_threads<BM, BN, MT, NT>)) void gemm_f32_kernel(const float* __restrict__ A, const float* __restrict__ B,
                                                        float* __restrict__ C, const int64_t* __restrict__ desc,
                                                        gemm_one one, int n_groups, int ksplit, float alpha,
                                                        const float* __restrict__ bias, int relu) {
@@ -117,8 +120,8 @@ __global__ __launch_bounds__((BM / (32 * MT)) * (BN / (32 * NT)) * 64) void gemm
     if (k_begin >= k_end) return;
     const bool va = ((((uintptr_t)Ag) & 15) == 0) && ((lda & 3) == 0);
     const bool vb = ((((uintptr_t)Bg) & 15) == 0) && ((ldb & 3) == 0);
-    constexpr int WN = BN / (32 * NT);                     // waves along N; each wave owns MT x NT blocks of 32 x 32
-    constexpr int NTH = (BM / (32 * MT)) * WN * 64;        // 4 or 8 waves
+    constexpr int WN = BN / (32 * NT);                     // waves along N
+    constexpr int NTH = gemm_threads<BM, BN, MT, NT>;
     const int wm = (wave / WN) * 32 * MT, wn = (wave % WN) * 32 * NT;
     tile_loader<BM, !TA, NTH> la;
     tile_loader<BN, TB, NTH> lb;
@@ -181,10 +184,9 @@ __global__ __launch_bounds__((BM / (32 * MT)) * (BN / (32 * NT)) * 64) void gemm
 template <int BM, int BN, int MT, int NT>
 static void gemm_launch(dim3 grid, hipStream_t st, const float* a, const float* b, float* c, const int64_t* desc, gemm_one one,
                         int n_groups, int ta, int tb, int ksplit, float alpha, const float* bias = nullptr, int relu = 0) {
-    if (!ta && !tb) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, MT, NT, false, false>), grid, dim3((BM / (32 * MT)) * (BN / (32 * NT)) * 64), 0, st, a, b, c, desc, one, n_groups, ksplit, alpha, bias, relu);
-    else if (!ta && tb) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, MT, NT, false, true>), grid, dim3((BM / (32 * MT)) * (BN / (32 * NT)) * 64), 0, st, a, b, c, desc, one, n_groups, ksplit, alpha, bias, relu);
-    else if (ta && !tb) hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, MT, NT, true, false>), grid, dim3((BM / (32 * MT)) * (BN / (32 * NT)) * 64), 0, st, a, b, c, desc, one, n_groups, ksplit, alpha, bias, relu);
-    else hipLaunchKernelGGL((gemm_f32_kernel<BM, BN, MT, NT, true, true>), grid, dim3((BM / (32 * MT)) * (BN / (32 * NT)) * 64), 0, st, a, b, c, desc, one, n_groups, ksplit, alpha, bias, relu);
+    const auto kernel = ta ? (tb ? gemm_f32_kernel<BM, BN, MT, NT, true, true> : gemm_f32_kernel<BM, BN, MT, NT, true, false>)
+                           : (tb ? gemm_f32_kernel<BM, BN, MT, NT, false, true> : gemm_f32_kernel<BM, BN, MT, NT, false, false>);
+    hipLaunchKernelGGL(kernel, grid, dim3(gemm_threads<BM, BN, MT, NT>), 0, st, a, b, c, desc, one, n_groups, ksplit, alpha, bias, relu);
 }
 
 extern "C" int nisqa_gemm_f32(const float* a, const float* b, float* c, const int64_t* desc, int32_t n_groups,
@@ -235,7 +237,7 @@ extern "C" int nisqa_gemm_f32_one(const float* a, const float* b, float* c, int6
 // ---------------------------------------------------------------------------------------------------------
 // 3 x 3 convolutions as IMPLICIT GEMMs: the patch matrix of im2col is never written -- the operand loaders gather it
 // from the activation tensor ([S][H*W][C], channels contiguous: a group of four k's is one 128-bit load inside one
-// tap).  Same tiles, LDS staging and MFMA core as gemm_f32_kernel.
+// tap).  Same tiles and K loop as gemm_f32_kernel, on either arithmetic core.
 //   MODE 0 forward : z[(s,yo,xo)][co]   = sum_{tap,ci} x[s][(yo+dy-1, xo+dx-pad)][ci] * w[co][tap*CI+ci] (+ bias)
 //   MODE 1 dgrad   : dx[(s,y,x)][ci]    = sum_{tap,co} dz[s][(y-dy+1, x-dx+pad)][co]   * w[co][tap*CI+ci]
 //   MODE 2 wgrad   : dw[co][tap*CI+ci] += sum_{(s,yo,xo)} dz[(s,yo,xo)][co] * x[s][(yo+dy-1, xo+dx-pad)][ci]   (split-K, atomics)
@@ -273,15 +275,150 @@ NQ_DEV f32x4 conv_gather(const float* __restrict__ src, const conv_geom& g, int 
     return v;
 }
 
-template <int BM, int BN, int MT, int NT, int MODE>
-__global__ __launch_bounds__((BM / (32 * MT)) * (BN / (32 * NT)) * 64) void conv_gemm_kernel(
+// ---------------------------------------------------------------------------------------------------------
+// The arithmetic of one workgroup tile comes in two forms with one interface.  A core owns the LDS image of an A and a B
+// tile (declared in its constructor, so each kernel gets the arrays of the core it is built on); stage() lays the registers
+// of the two tile_loaders into it; multiply() adds one GB_K tile to the wave's MT x NT blocks of 32 x 32.
+// core_f32: exact fp32 on v_mfma_f32_32x32x2_f32, k ascending, two k's per MFMA, operands as T[k][r] (tile_loader::store) --
+// the arithmetic of gemm_f32_kernel, which keeps its own copy of this loop: built on the core, some of its instantiations
+// need a few registers more and fall from five waves per SIMD to four.
+// ---------------------------------------------------------------------------------------------------------
+template <int BM, int BN, int MT, int NT>
+struct core_f32 {
+    float (*a)[BM + 4];
+    float (*b)[BN + 4];
+    const NQ_AS3 float *fa, *fb;                           // this lane's element of k-pair 0 in the wave's first A and B block
+    __device__ __forceinline__ core_f32(int wm, int wn, int lane) {
+        __shared__ __attribute__((aligned(16))) float As[GB_K][BM + 4];
+        __shared__ __attribute__((aligned(16))) float Bs[GB_K][BN + 4];
+        a = As;
+        b = Bs;
+        fa = (const NQ_AS3 float*)&As[lane >> 5][wm + (lane & 31)];
+        fb = (const NQ_AS3 float*)&Bs[lane >> 5][wn + (lane & 31)];
+    }
+    template <class LA, class LB>
+    __device__ __forceinline__ void stage(const LA& la, const LB& lb, int tid) const {
+        la.store(a, tid);
+        lb.store(b, tid);
+    }
+    __device__ __forceinline__ void multiply(f32x16 (&acc)[MT][NT]) const {
+#pragma unroll
+        for (int s = 0; s < GB_K / 2; ++s) {
+            float av[MT], bv[NT];
+#pragma unroll
+            for (int i = 0; i < MT; ++i) av[i] = fa[2 * s * (BM + 4) + 32 * i];
+#pragma unroll
+            for (int j = 0; j < NT; ++j) bv[j] = fb[2 * s * (BN + 4) + 32 * j];
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int j = 0; j < NT; ++j) acc[i][j] = mfma32(av[i], bv[j], acc[i][j]);
+        }
+    }
+};
+
+// ---------------------------------------------------------------------------------------------------------
+// core_bf16x3: the same products on split-bf16 MFMA (v_mfma_f32_32x32x16_bf16; hi * hi + hi * lo + lo * hi, fp32 accumulate:
+// 16 operand bits like the inference path, 5.3x the fp32-MFMA rate).  Loaders and tiling as for core_f32; what changes is
+// the LDS image and how fragments come out of it.  A tile is two bf16 planes (hi, lo) written by the loader threads, which
+// split their four fp32 values on the way (v_cvt_pk_bf16_f32):
+//   * operand whose CONTIGUOUS index in memory is k (forward / dgrad patches, forward weights): image [row][32 k] with
+//     80-byte rows; a lane's fragment (row lane & 31, k = 8 * (lane >> 5) .. + 7) is one ds_read_b128;
+//   * operand whose contiguous index is the row (dgrad weights; dz and the patches of wgrad, where k is the pixel row of
+//     the batch): image [32 k][rows] as loaded (row stride 2 * rows + 64 bytes: the four k-rows of a transpose read land
+//     in different bank quarters), and the fragment comes out of ds_read_b64_tr_b16, gfx950's transposing LDS read:
+//     within a 16-lane group lane s points at row (s >> 2), columns 4 * (s & 3) .. + 3 of a [4 k][16 rows] block and
+//     lane i receives column i of that block (tools/micro/trread.hip prints the mapping from the hardware).
+// ---------------------------------------------------------------------------------------------------------
+typedef short nq_s16x4 __attribute__((ext_vector_type(4)));
+
+template <int R, bool KC>
+struct bf_tile {
+    static constexpr int RS = KC ? 80 : 2 * R + ((R / 32) % 2 ? 128 : 64);   // row stride in bytes: an odd multiple of 64
+    static constexpr int PLANE = KC ? R * 80 : GB_K * RS;     // one bf16 plane
+    static constexpr int BYTES = 2 * PLANE;
+    // the loader thread's groups of four values -> both planes
+    template <int NTH>
+    static __device__ __forceinline__ void store(const tile_loader<R, KC, NTH>& l, unsigned base, int tid) {
+        const auto& v = l.v;
+#pragma unroll
+        for (int j = 0; j < tile_loader<R, KC, NTH>::NV; ++j) {
+            const int i = tid + NTH * j;
+            unsigned a;
+            if (KC) a = base + (i / (GB_K / 4)) * RS + 8 * (i % (GB_K / 4));
+            else a = base + (i / (R / 4)) * RS + 8 * (i % (R / 4));
+            unsigned h0, l0, h1, l1;
+            split2(v[j][0], v[j][1], h0, l0);
+            split2(v[j][2], v[j][3], h1, l1);
+            *(NQ_AS3 u32x2*)(a) = u32x2{h0, h1};
+            *(NQ_AS3 u32x2*)(a + PLANE) = u32x2{l0, l1};
+        }
+    }
+    // lane-dependent part of a fragment address for the 32 rows starting at row0
+    static __device__ __forceinline__ unsigned lane_base(unsigned base, int row0, int lane) {
+        if (KC) return base + (row0 + (lane & 31)) * RS + 16 * (lane >> 5);
+        return base + (8 * (lane >> 5) + ((lane & 15) >> 2)) * RS + 2 * (row0 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3));
+    }
+    // fragment of k-substep s (k = 16 s .. 16 s + 15) of one plane
+    static __device__ __forceinline__ f32x4 frag(unsigned lb, int s) {
+        if (KC) return lds_ld128(lb + 32 * s);
+        const unsigned a = lb + 16 * s * RS;
+        const nq_s16x4 x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((NQ_AS3 nq_s16x4*)(a));
+        const nq_s16x4 x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((NQ_AS3 nq_s16x4*)(a + 4 * RS));
+        struct { nq_s16x4 a, b; } both = {x0, x1};
+        return __builtin_bit_cast(f32x4, both);
+    }
+};
+
+// product order per k-substep of 16: hi * hi, hi * lo, lo * hi
+template <int BM, int BN, int MT, int NT, bool A_KC, bool B_KC>
+struct core_bf16x3 {
+    typedef bf_tile<BM, A_KC> TA;
+    typedef bf_tile<BN, B_KC> TB;
+    unsigned sa, sb, fa[MT], fb[NT];                       // LDS addresses: the two tiles, this lane's fragment bases
+    __device__ __forceinline__ core_bf16x3(int wm, int wn, int lane) {
+        __shared__ __attribute__((aligned(16))) unsigned char smem[TA::BYTES + TB::BYTES];
+        sa = (unsigned)(size_t)(NQ_AS3 unsigned char*)smem;
+        sb = sa + TA::BYTES;
+        smem[TA::BYTES + TB::BYTES - 1] = 0;                // a pad byte: the kernel must be seen to use its LDS through the symbol
+#pragma unroll
+        for (int i = 0; i < MT; ++i) fa[i] = TA::lane_base(sa, wm + 32 * i, lane);
+#pragma unroll
+        for (int j = 0; j < NT; ++j) fb[j] = TB::lane_base(sb, wn + 32 * j, lane);
+    }
+    template <class LA, class LB>
+    __device__ __forceinline__ void stage(const LA& la, const LB& lb, int tid) const {
+        TA::store(la, sa, tid);
+        TB::store(lb, sb, tid);
+    }
+    __device__ __forceinline__ void multiply(f32x16 (&acc)[MT][NT]) const {
+#pragma unroll
+        for (int s = 0; s < GB_K / 16; ++s) {
+            f32x4 ah[MT], al[MT], bh[NT], bl[NT];
+#pragma unroll
+            for (int i = 0; i < MT; ++i) { ah[i] = TA::frag(fa[i], s); al[i] = TA::frag(fa[i] + TA::PLANE, s); }
+#pragma unroll
+            for (int j = 0; j < NT; ++j) { bh[j] = TB::frag(fb[j], s); bl[j] = TB::frag(fb[j] + TB::PLANE, s); }
+#pragma unroll
+            for (int i = 0; i < MT; ++i)
+#pragma unroll
+                for (int j = 0; j < NT; ++j) {
+                    acc[i][j] = mfma_bf(ah[i], bh[j], acc[i][j]);
+                    acc[i][j] = mfma_bf(ah[i], bl[j], acc[i][j]);
+                    acc[i][j] = mfma_bf(al[i], bh[j], acc[i][j]);
+                }
+        }
+    }
+};
+
+// Core = core_f32<BM, BN, MT, NT> or core_bf16x3<BM, BN, MT, NT, MODE != 2, MODE == 0> (conv_launch)
+template <int BM, int BN, int MT, int NT, int MODE, class Core>
+__global__ __launch_bounds__((gemm_threads<BM, BN, MT, NT>)) void conv_gemm_kernel(
     const float* __restrict__ G, const float* __restrict__ O, float* __restrict__ C, conv_geom g, int M, int N, int K, int ksplit,
     const float* __restrict__ bias, double* __restrict__ stats) {
     // G: the gathered tensor (x for forward / wgrad, dz for dgrad); O: the other operand (weights, or dz for wgrad)
-    __shared__ __attribute__((aligned(16))) float As[GB_K][BM + 4];
-    __shared__ __attribute__((aligned(16))) float Bs[GB_K][BN + 4];
     constexpr int WN = BN / (32 * NT);
-    constexpr int NTH = (BM / (32 * MT)) * WN * 64;
+    constexpr int NTH = gemm_threads<BM, BN, MT, NT>;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int tiles_n = (N + BN - 1) / BN;
     const int m0 = ((int)blockIdx.x / tiles_n) * BM, n0 = ((int)blockIdx.x % tiles_n) * BN;
@@ -350,10 +487,11 @@ __global__ __launch_bounds__((BM / (32 * MT)) * (BN / (32 * NT)) * 64) void conv
         }
     };
 
+    // the next K tile travels global -> registers while the current one is multiplied
+    const Core core(wm, wn, lane);
     load_a(k_begin);
     load_b(k_begin);
-    la.store(As, tid);
-    lb.store(Bs, tid);
+    core.stage(la, lb, tid);
     __syncthreads();
     f32x16 acc[MT][NT];
 #pragma unroll
@@ -366,243 +504,10 @@ __global__ __launch_bounds__((BM / (32 * MT)) * (BN / (32 * NT)) * 64) void conv
             load_a(k0 + GB_K);
             load_b(k0 + GB_K);
         }
-#pragma unroll
-        for (int s = 0; s < GB_K / 2; ++s) {
-            float av[MT], bv[NT];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) av[i] = As[2 * s + (lane >> 5)][wm + 32 * i + (lane & 31)];
-#pragma unroll
-            for (int j = 0; j < NT; ++j) bv[j] = Bs[2 * s + (lane >> 5)][wn + 32 * j + (lane & 31)];
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j) acc[i][j] = mfma32(av[i], bv[j], acc[i][j]);
-        }
+        core.multiply(acc);
         __syncthreads();
         if (more) {
-            la.store(As, tid);
-            lb.store(Bs, tid);
-            __syncthreads();
-        }
-    }
-    // forward with stats != NULL: the per-channel sums of z and z^2 over all rows (the BatchNorm batch statistics) ride
-    // along in float64 -- lane pairs, then the workgroup's waves through LDS, then one atomic per channel and workgroup
-    __shared__ double red[MODE == 0 ? 2 * BN : 1];
-    const bool with_stats = MODE == 0 && stats != nullptr;
-    if (with_stats) {
-        for (int q = tid; q < 2 * BN; q += NTH) red[q] = 0.0;
-        __syncthreads();
-    }
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) {
-            const int col = n0 + wn + 32 * j + (lane & 31);
-            double s1 = 0.0, s2 = 0.0;
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int row = m0 + wm + 32 * i + NQ_DROW(r, lane >> 5);
-                if (row < M && col < N) {
-                    const float v = acc[i][j][r];
-                    if (MODE == 2) atomicAdd(C + (int64_t)row * N + col, v);
-                    else {
-                        const float zv = bias ? v + bias[col] : v;
-                        C[(int64_t)row * N + col] = zv;
-                        if (MODE == 0) { s1 += (double)zv; s2 += (double)zv * (double)zv; }
-                    }
-                }
-            }
-            if (with_stats) {
-                s1 += __shfl_xor(s1, 32);
-                s2 += __shfl_xor(s2, 32);
-                if (lane < 32 && col < N) {
-                    atomicAdd(&red[wn + 32 * j + lane], s1);
-                    atomicAdd(&red[BN + wn + 32 * j + lane], s2);
-                }
-            }
-        }
-    if (with_stats) {
-        __syncthreads();
-        for (int q = tid; q < BN; q += NTH)
-            if (n0 + q < N) {
-                atomicAdd(stats + n0 + q, red[q]);
-                atomicAdd(stats + N + n0 + q, red[BN + q]);
-            }
-    }
-}
-
-// ---------------------------------------------------------------------------------------------------------
-// The same three products on split-bf16 MFMA (v_mfma_f32_32x32x16_bf16; hi * hi + hi * lo + lo * hi, fp32 accumulate:
-// 16 operand bits like the inference path, 5.3x the fp32-MFMA rate).  Loaders and tiling as above; what changes is
-// the LDS image and how fragments come out of it.  A tile is two bf16 planes (hi, lo) written by the loader threads, which
-// split their four fp32 values on the way (v_cvt_pk_bf16_f32):
-//   * operand whose CONTIGUOUS index in memory is k (forward / dgrad patches, forward weights): image [row][32 k] with
-//     80-byte rows; a lane's fragment (row lane & 31, k = 8 * (lane >> 5) .. + 7) is one ds_read_b128;
-//   * operand whose contiguous index is the row (dgrad weights; dz and the patches of wgrad, where k is the pixel row of
-//     the batch): image [32 k][rows] as loaded (row stride 2 * rows + 64 bytes: the four k-rows of a transpose read land
-//     in different bank quarters), and the fragment comes out of ds_read_b64_tr_b16, gfx950's transposing LDS read:
-//     within a 16-lane group lane s points at row (s >> 2), columns 4 * (s & 3) .. + 3 of a [4 k][16 rows] block and
-//     lane i receives column i of that block (tools/micro/trread.hip prints the mapping from the hardware).
-// ---------------------------------------------------------------------------------------------------------
-typedef short nq_s16x4 __attribute__((ext_vector_type(4)));
-
-template <int R, bool KC>
-struct bf_tile {
-    static constexpr int RS = KC ? 80 : 2 * R + ((R / 32) % 2 ? 128 : 64);   // row stride in bytes: an odd multiple of 64
-    static constexpr int PLANE = KC ? R * 80 : GB_K * RS;     // one bf16 plane
-    static constexpr int BYTES = 2 * PLANE;
-    // the loader thread's groups of four values -> both planes
-    template <int NV, int NTH>
-    static __device__ __forceinline__ void store(const f32x4 (&v)[NV], unsigned base, int tid) {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int i = tid + NTH * j;
-            unsigned a;
-            if (KC) a = base + (i / (GB_K / 4)) * RS + 8 * (i % (GB_K / 4));
-            else a = base + (i / (R / 4)) * RS + 8 * (i % (R / 4));
-            unsigned h0, l0, h1, l1;
-            split2(v[j][0], v[j][1], h0, l0);
-            split2(v[j][2], v[j][3], h1, l1);
-            *(NQ_AS3 u32x2*)(a) = u32x2{h0, h1};
-            *(NQ_AS3 u32x2*)(a + PLANE) = u32x2{l0, l1};
-        }
-    }
-    // lane-dependent part of a fragment address for the 32 rows starting at row0
-    static __device__ __forceinline__ unsigned lane_base(unsigned base, int row0, int lane) {
-        if (KC) return base + (row0 + (lane & 31)) * RS + 16 * (lane >> 5);
-        return base + (8 * (lane >> 5) + ((lane & 15) >> 2)) * RS + 2 * (row0 + 16 * ((lane >> 4) & 1) + 4 * (lane & 3));
-    }
-    // fragment of k-substep s (k = 16 s .. 16 s + 15) of one plane
-    static __device__ __forceinline__ f32x4 frag(unsigned lb, int s) {
-        if (KC) return lds_ld128(lb + 32 * s);
-        const unsigned a = lb + 16 * s * RS;
-        const nq_s16x4 x0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((NQ_AS3 nq_s16x4*)(a));
-        const nq_s16x4 x1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((NQ_AS3 nq_s16x4*)(a + 4 * RS));
-        struct { nq_s16x4 a, b; } both = {x0, x1};
-        return __builtin_bit_cast(f32x4, both);
-    }
-};
-
-template <int BM, int BN, int MT, int NT, int MODE>
-__global__ __launch_bounds__((BM / (32 * MT)) * (BN / (32 * NT)) * 64) void conv_gemm_bf16_kernel(
-    const float* __restrict__ G, const float* __restrict__ O, float* __restrict__ C, conv_geom g, int M, int N, int K, int ksplit,
-    const float* __restrict__ bias, double* __restrict__ stats) {
-    typedef bf_tile<BM, MODE != 2> TA;
-    typedef bf_tile<BN, MODE == 0> TB;
-    __shared__ __attribute__((aligned(16))) unsigned char smem[TA::BYTES + TB::BYTES];
-    constexpr int WN = BN / (32 * NT);
-    constexpr int NTH = (BM / (32 * MT)) * WN * 64;
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int tiles_n = (N + BN - 1) / BN;
-    const int m0 = ((int)blockIdx.x / tiles_n) * BM, n0 = ((int)blockIdx.x % tiles_n) * BN;
-    int kc = (K + ksplit - 1) / ksplit;
-    kc = (kc + GB_K - 1) / GB_K * GB_K;
-    const int k_begin = blockIdx.y * kc, k_end = min(K, k_begin + kc);
-    if (k_begin >= k_end) return;
-    const int wm = (wave / WN) * 32 * MT, wn = (wave % WN) * 32 * NT;
-    tile_loader<BM, MODE != 2, NTH> la;
-    tile_loader<BN, MODE == 0, NTH> lb;
-    const int csm = (1 << g.lcs) - 1;
-    const unsigned sa = (unsigned)(size_t)(NQ_AS3 unsigned char*)smem, sb = sa + TA::BYTES;
-    smem[TA::BYTES + TB::BYTES - 1] = 0;                    // a pad byte: the kernel must be seen to use its LDS through the symbol
-
-    int a_s[la.NV], a_y[la.NV], a_x[la.NV];
-    if (MODE != 2) {
-#pragma unroll
-        for (int j = 0; j < la.NV; ++j) {
-            const int row = m0 + (tid + NTH * j) / (GB_K / 4);
-            const uint32_t s = fdiv_q((uint32_t)row, g.d_img);
-            const uint32_t rem = (uint32_t)row - s * (uint32_t)(g.hr * g.wr);
-            const uint32_t y = fdiv_q(rem, g.d_row);
-            a_s[j] = row < M ? (int)s : -1;
-            a_y[j] = (int)y;
-            a_x[j] = (int)(rem - y * (uint32_t)g.wr);
-        }
-    }
-    auto load_a = [&](int k0) {
-#pragma unroll
-        for (int j = 0; j < la.NV; ++j) {
-            const int i = tid + NTH * j;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (MODE != 2) {
-                const int kk = k0 + 4 * (i % (GB_K / 4));
-                if (a_s[j] >= 0 && kk < k_end) v = conv_gather(G, g, a_s[j], a_y[j], a_x[j], kk >> g.lcs, kk & csm);
-            } else {
-                const int kk = k0 + i / (BM / 4), m = m0 + 4 * (i % (BM / 4));
-                if (kk < k_end && m < M) v = *(const f32x4*)(O + (int64_t)kk * g.co + m);
-            }
-            la.v[j] = v;
-        }
-    };
-    auto load_b = [&](int k0) {
-#pragma unroll
-        for (int j = 0; j < lb.NV; ++j) {
-            const int i = tid + NTH * j;
-            f32x4 v = {0.f, 0.f, 0.f, 0.f};
-            if (MODE == 0) {
-                const int n = n0 + i / (GB_K / 4), kk = k0 + 4 * (i % (GB_K / 4));
-                if (n < N && kk < k_end) v = *(const f32x4*)(O + (int64_t)n * K + kk);
-            } else if (MODE == 1) {
-                const int kk = k0 + i / (BN / 4), n = n0 + 4 * (i % (BN / 4));
-                if (kk < k_end && n < N) {
-                    const int tap = kk >> g.lcs, co = kk & csm;
-                    v = *(const f32x4*)(O + (int64_t)co * (9 * g.ci) + tap * g.ci + n);
-                }
-            } else {
-                const int kk = k0 + i / (BN / 4), n = n0 + 4 * (i % (BN / 4));
-                if (kk < k_end && n < N) {
-                    const uint32_t s = fdiv_q((uint32_t)kk, g.d_img);
-                    const uint32_t rem = (uint32_t)kk - s * (uint32_t)(g.hr * g.wr);
-                    const uint32_t y = fdiv_q(rem, g.d_row);
-                    v = conv_gather(G, g, (int)s, (int)y, (int)(rem - y * (uint32_t)g.wr), n >> g.lcs, n & csm);
-                }
-            }
-            lb.v[j] = v;
-        }
-    };
-
-    unsigned fa[MT], fb[NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i) fa[i] = TA::lane_base(sa, wm + 32 * i, lane);
-#pragma unroll
-    for (int j = 0; j < NT; ++j) fb[j] = TB::lane_base(sb, wn + 32 * j, lane);
-
-    load_a(k_begin);
-    load_b(k_begin);
-    TA::template store<la.NV, NTH>(la.v, sa, tid);
-    TB::template store<lb.NV, NTH>(lb.v, sb, tid);
-    __syncthreads();
-    f32x16 acc[MT][NT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i)
-#pragma unroll
-        for (int j = 0; j < NT; ++j) acc[i][j] = zero16();
-    for (int k0 = k_begin; k0 < k_end; k0 += GB_K) {
-        const bool more = k0 + GB_K < k_end;
-        if (more) {
-            load_a(k0 + GB_K);
-            load_b(k0 + GB_K);
-        }
-#pragma unroll
-        for (int s = 0; s < GB_K / 16; ++s) {
-            f32x4 ah[MT], al[MT], bh[NT], bl[NT];
-#pragma unroll
-            for (int i = 0; i < MT; ++i) { ah[i] = TA::frag(fa[i], s); al[i] = TA::frag(fa[i] + TA::PLANE, s); }
-#pragma unroll
-            for (int j = 0; j < NT; ++j) { bh[j] = TB::frag(fb[j], s); bl[j] = TB::frag(fb[j] + TB::PLANE, s); }
-#pragma unroll
-            for (int i = 0; i < MT; ++i)
-#pragma unroll
-                for (int j = 0; j < NT; ++j) {
-                    acc[i][j] = mfma_bf(ah[i], bh[j], acc[i][j]);
-                    acc[i][j] = mfma_bf(ah[i], bl[j], acc[i][j]);
-                    acc[i][j] = mfma_bf(al[i], bh[j], acc[i][j]);
-                }
-        }
-        __syncthreads();
-        if (more) {
-            TA::template store<la.NV, NTH>(la.v, sa, tid);
-            TB::template store<lb.NV, NTH>(lb.v, sb, tid);
+            core.stage(la, lb, tid);
             __syncthreads();
         }
     }
@@ -656,9 +561,10 @@ template <int BM, int BN, int MT, int NT, int MODE>
 static void conv_launch(hipStream_t st, const float* gsrc, const float* other, float* c, const conv_geom& g, int M, int N, int K,
                         int ksplit, const float* bias, bool bf16, double* stats = nullptr) {
     const int64_t tiles = (int64_t)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
-    const dim3 grid((unsigned)tiles, ksplit), block((BM / (32 * MT)) * (BN / (32 * NT)) * 64);
-    if (bf16) hipLaunchKernelGGL((conv_gemm_bf16_kernel<BM, BN, MT, NT, MODE>), grid, block, 0, st, gsrc, other, c, g, M, N, K, ksplit, bias, stats);
-    else hipLaunchKernelGGL((conv_gemm_kernel<BM, BN, MT, NT, MODE>), grid, block, 0, st, gsrc, other, c, g, M, N, K, ksplit, bias, stats);
+    const dim3 grid((unsigned)tiles, ksplit), block(gemm_threads<BM, BN, MT, NT>);
+    const auto kernel = bf16 ? conv_gemm_kernel<BM, BN, MT, NT, MODE, core_bf16x3<BM, BN, MT, NT, MODE != 2, MODE == 0>>
+                             : conv_gemm_kernel<BM, BN, MT, NT, MODE, core_f32<BM, BN, MT, NT>>;
+    hipLaunchKernelGGL(kernel, grid, block, 0, st, gsrc, other, c, g, M, N, K, ksplit, bias, stats);
 }
 
 static int ilog2_exact(int v) {
@@ -854,6 +760,37 @@ extern "C" int nisqa_conv1_wgrad(const float* mel_tm, const int32_t* frame_off, 
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// helpers shared by the layer-1 kernels and the BatchNorm / pooling kernels further down
+// ---------------------------------------------------------------------------------------------------------
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+// adaptive max pool: the input window of output cell i
+NQ_DEV int win_lo(int i, int n_in, int n_out) { return (i * n_in) / n_out; }
+NQ_DEV int win_hi(int i, int n_in, int n_out) { return ((i + 1) * n_in + n_out - 1) / n_out; }
+
+// BatchNorm batch statistics of channel ch from the float64 column sums (sum z, sum z^2 over m_rows rows)
+NQ_DEV void bn_stats(const double* __restrict__ sums, int c, int ch, double m_rows, float& mean, float& rstd, double& var) {
+    const double mu = sums[ch] / m_rows;
+    var = sums[c + ch] / m_rows - mu * mu;
+    if (var < 0.0) var = 0.0;
+    mean = (float)mu;
+    rstd = (float)(1.0 / sqrt(var + 1e-5));
+}
+
+__global__ void bn_finalize_kernel(const double* __restrict__ sums, int c, int64_t m_rows, float* __restrict__ running_mean,
+                                   float* __restrict__ running_var, float* __restrict__ mean_rstd) {
+    const int ch = threadIdx.x;
+    if (ch >= c) return;
+    float mean, rstd;
+    double var;
+    bn_stats(sums, c, ch, (double)m_rows, mean, rstd, var);
+    mean_rstd[ch] = mean;
+    mean_rstd[c + ch] = rstd;
+    const double unb = m_rows > 1 ? var * ((double)m_rows / (double)(m_rows - 1)) : var;
+    running_mean[ch] = 0.9f * running_mean[ch] + 0.1f * mean;
+    running_var[ch] = 0.9f * running_var[ch] + 0.1f * (float)unb;
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // Layer 1 without its activations.  z1 = conv1(patch) has S x 720 x 16 entries (364 MB at 32 x 10 s clips) and the
 // unfused step makes nine passes over tensors of that size (z, dyb, dz).  But z is AFFINE in nine numbers per pixel, so
 //   * the BatchNorm statistics follow from the first and second moments of the patches, P1[t] = sum patch[t] and
@@ -867,11 +804,6 @@ extern "C" int nisqa_conv1_wgrad(const float* mel_tm, const int32_t* frame_off, 
 // No tensor of 720 pixels per segment is ever written.
 // ---------------------------------------------------------------------------------------------------------
 #define C1_MOM 54                                            /* P1[9], then P2 upper triangle [t <= u] */
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-NQ_DEV int win_lo(int i, int n_in, int n_out);
-NQ_DEV int win_hi(int i, int n_in, int n_out);
-__global__ void bn_finalize_kernel(const double* __restrict__ sums, int c, int64_t m_rows, float* __restrict__ running_mean,
-                                   float* __restrict__ running_var, float* __restrict__ mean_rstd);
 NQ_DEV int c1_p2(int t, int u) { return t <= u ? 9 + t * 9 - t * (t - 1) / 2 + (u - t) : 9 + u * 9 - u * (u - 1) / 2 + (t - u); }
 
 // every WAVE walks over its own segments with its own LDS copy: no workgroup barrier inside the loop (with 256 threads per
@@ -1341,33 +1273,6 @@ extern "C" int nisqa_col_dot(const float* a, const float* b, int64_t rows, int32
 // ---------------------------------------------------------------------------------------------------------
 // BatchNorm (batch statistics) + ReLU + adaptive max pool + Dropout2d
 // ---------------------------------------------------------------------------------------------------------
-NQ_DEV int win_lo(int i, int n_in, int n_out) { return (i * n_in) / n_out; }
-NQ_DEV int win_hi(int i, int n_in, int n_out) { return ((i + 1) * n_in + n_out - 1) / n_out; }
-
-NQ_DEV void bn_stats(const double* __restrict__ sums, int c, int ch, double m_rows, float& mean, float& rstd, double& var) {
-    const double mu = sums[ch] / m_rows;
-    var = sums[c + ch] / m_rows - mu * mu;
-    if (var < 0.0) var = 0.0;
-    mean = (float)mu;
-    rstd = (float)(1.0 / sqrt(var + 1e-5));
-}
-
-__global__ void bn_finalize_kernel(const double* __restrict__ sums, int c, int64_t m_rows, float* __restrict__ running_mean,
-                                   float* __restrict__ running_var, float* __restrict__ mean_rstd) {
-    const int ch = threadIdx.x;
-    if (ch >= c) return;
-    float mean, rstd;
-    double var;
-    bn_stats(sums, c, ch, (double)m_rows, mean, rstd, var);
-    mean_rstd[ch] = mean;
-    mean_rstd[c + ch] = rstd;
-    const double unb = m_rows > 1 ? var * ((double)m_rows / (double)(m_rows - 1)) : var;
-    running_mean[ch] = 0.9f * running_mean[ch] + 0.1f * mean;
-    running_var[ch] = 0.9f * running_var[ch] + 0.1f * (float)unb;
-}
-
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
 // per-channel affine form of the normalisation for four consecutive channels: y = z * g + b
 NQ_DEV void bn_affine4(const float* __restrict__ gamma, const float* __restrict__ beta, const float* __restrict__ mean_rstd, int c,
                        int ch, f32x4& g, f32x4& b) {

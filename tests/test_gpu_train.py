@@ -142,12 +142,22 @@ def test_im2col_col2im_against_unfold_and_adjointness(h, w, c, pad_w):
     assert abs(lhs - rhs) < 1e-6 * max(1.0, abs(lhs))                # <im2col(x), d> == <x, col2im(d)>
 
 
+# the AdaptCNN's conv2..6, then the StandardCNN's (which only these kernels serve: nisqa_segconv_supported refuses them).
+# S = 37: rows not a multiple of any tile; S = 1: fewer rows than one tile (every row guard of loader and epilogue is live) and,
+# for the weight gradient, a K shorter than ksplit * 32 (workgroups past the end leave at once).  Last, the smallest layer
+# the argument check admits: K = 36 = 32 + 4 (a K tail), N = 4 (less than a tile), 45 rows.
+_IGEMM_LAYERS = [(24, 7, 16, 32, 1), (12, 5, 32, 64, 1), (12, 5, 64, 64, 1), (6, 3, 64, 64, 1), (6, 3, 64, 64, 0),
+                 (24, 8, 16, 32, 1), (12, 4, 32, 64, 1), (12, 4, 64, 64, 1), (6, 2, 64, 64, 1)]
+_IGEMM_CASES = [pytest.param(*layer, S, id='-'.join(map(str, layer)) + ('' if S == 37 else '-S%d' % S))  # S = 37 keeps its old id
+                for layer, S in [(la, S) for la in _IGEMM_LAYERS for S in (1, 37)] + [((3, 3, 4, 4, 1), 5)]]
+
+
 @pytest.mark.parametrize('entry', ['nisqa_conv3x3_gemm', 'nisqa_conv3x3_gemm_bf16'])
-@pytest.mark.parametrize('h,w,ci,co,pad_w', [(24, 7, 16, 32, 1), (12, 5, 32, 64, 1), (12, 5, 64, 64, 1), (6, 3, 64, 64, 1), (6, 3, 64, 64, 0)])
-def test_implicit_gemm_convolution_forward_dgrad_wgrad(h, w, ci, co, pad_w, entry):
+@pytest.mark.parametrize('h,w,ci,co,pad_w,S', _IGEMM_CASES)
+def test_implicit_gemm_convolution_forward_dgrad_wgrad(h, w, ci, co, pad_w, S, entry):
     lib, L = _L()
     conv = getattr(L, entry)                                          # exact fp32 MFMA / split-bf16 MFMA (same tolerances)
-    S = 37                                                            # rows not a multiple of any tile
+    ksplit = 5 if S == 37 else 3
     wo = w + 2 * pad_w - 2
     x = _r(S, h * w, ci, seed=50).requires_grad_(True)
     wt = (_r(co, ci, 3, 3, seed=51) * 0.2).requires_grad_(True)
@@ -161,7 +171,7 @@ def test_implicit_gemm_convolution_forward_dgrad_wgrad(h, w, ci, co, pad_w, entr
     dx = torch.empty(S, h * w, ci, device=DEV)
     lib.check(conv(1, _p(dz), _p(wk), _p(dx), S, h, w, ci, co, pad_w, None, 1, _st()), 'conv dgrad')
     dw = torch.zeros(co, 9 * ci, device=DEV)
-    lib.check(conv(2, _p(x.detach()), _p(dz), _p(dw), S, h, w, ci, co, pad_w, None, 5, _st()), 'conv wgrad')
+    lib.check(conv(2, _p(x.detach()), _p(dz), _p(dw), S, h, w, ci, co, pad_w, None, ksplit, _st()), 'conv wgrad')
     torch.cuda.synchronize()
     want_z = z_t.detach().permute(0, 2, 3, 1).reshape(S * h * wo, co)
     print(entry, 'max|d| z %.2e of %.1f, dx %.2e of %.1f, dw %.2e of %.1f' % (
