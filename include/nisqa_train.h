@@ -34,6 +34,11 @@ int nisqa_gemm_f32(const float* a, const float* b, float* c, const int64_t* desc
 int nisqa_gemm_f32_one(const float* a, const float* b, float* c, int64_t m, int64_t n, int64_t k, int64_t lda,
                        int64_t ldb, int64_t ldc, int32_t trans_a, int32_t trans_b, int32_t ksplit, float alpha,
                        const float* bias, int32_t relu, void* stream);
+/* the tile nisqa_gemm_f32_one runs an m x n product on (host only, launches nothing; the launcher calls it, so a test
+ * reads the kernel a shape selects instead of restating the rule): returns the configuration index and writes the
+ * tile's rows / columns to *bm / *bn (either may be NULL): 0 = 64 x 64, 1 = 128 x 32, 2 = 128 x 128, 3 = 256 x 64,
+ * 4 = 64 x 256.  The big tiles 2 and 3 only from 192 workgroups up. */
+int nisqa_gemm_f32_one_tile(int64_t m, int64_t n, int32_t* bm, int32_t* bn);
 
 /* conv1 patches straight from the dB spectrogram (Framewise + segment_specs, NISQA_lib.py:2239-2282, 487-502):
  * col[s*720 + m*15 + j][dy*3+dx] = max(mel_tm[frame_off[b] + k*seg_hop + j+dx-1][m+dy-1], clip_floor[b]) or 0

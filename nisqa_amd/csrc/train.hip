@@ -200,21 +200,31 @@ extern "C" int nisqa_gemm_f32(const float* a, const float* b, float* c, const in
     return NQ_LAUNCH_STATUS();
 }
 
-extern "C" int nisqa_gemm_f32_one(const float* a, const float* b, float* c, int64_t m, int64_t n, int64_t k, int64_t lda,
-                                  int64_t ldb, int64_t ldc, int32_t trans_a, int32_t trans_b, int32_t ksplit, float alpha,
-                                  const float* bias, int32_t relu, void* stream) {
-    if (!a || !b || !c || m < 0 || n < 0 || k <= 0 || ksplit < 1 || ksplit > 65535 || (ksplit > 1 && (bias || relu)))
-        return NISQA_ERR_ARG;
-    // tile shape by problem shape: (BM, BN) and the 32 x 32 blocks per wave (more blocks = fewer LDS reads and
-    // barriers per MFMA): conv1/2 outputs are narrow, conv/Linear forward is tall (N = 64), the patch gradient is
-    // tall and wide, weight gradients are short and wide with K = the row count of the batch
+// The tile of nisqa_gemm_f32_one by problem shape, the one place that states it (host only; the launcher below calls it
+// and tests read it): (BM, BN) and the 32 x 32 blocks per wave (more blocks = fewer LDS reads and barriers per MFMA):
+// conv1/2 outputs are narrow, conv/Linear forward is tall (N = 64), the patch gradient is tall and wide, weight
+// gradients are short and wide with K = the row count of the batch.  Returns the configuration index:
+// 0 = 64 x 64, 1 = 128 x 32, 2 = 128 x 128, 3 = 256 x 64, 4 = 64 x 256.
+extern "C" int nisqa_gemm_f32_one_tile(int64_t m, int64_t n, int32_t* bm_out, int32_t* bn_out) {
     int cfg = 0;
-    int64_t bm = 64, bn = 64;
+    int32_t bm = 64, bn = 64;
     if (n <= 32 && m > 64) { cfg = 1; bm = 128; bn = 32; }
     // (the big tiles only where they still give every CU a workgroup: a 7 904 x 64 product is 31 tiles of 256 x 64)
     else if (m >= 256 && n >= 128 && ((m + 127) / 128) * ((n + 127) / 128) >= 192) { cfg = 2; bm = 128; bn = 128; }
     else if (m >= 512 && n > 32 && ((m + 255) / 256) * ((n + 63) / 64) >= 192) { cfg = 3; bm = 256; bn = 64; }
     else if (m <= 64 && n >= 256) { cfg = 4; bm = 64; bn = 256; }
+    if (bm_out) *bm_out = bm;
+    if (bn_out) *bn_out = bn;
+    return cfg;
+}
+
+extern "C" int nisqa_gemm_f32_one(const float* a, const float* b, float* c, int64_t m, int64_t n, int64_t k, int64_t lda,
+                                  int64_t ldb, int64_t ldc, int32_t trans_a, int32_t trans_b, int32_t ksplit, float alpha,
+                                  const float* bias, int32_t relu, void* stream) {
+    if (!a || !b || !c || m < 0 || n < 0 || k <= 0 || ksplit < 1 || ksplit > 65535 || (ksplit > 1 && (bias || relu)))
+        return NISQA_ERR_ARG;
+    int32_t bm, bn;
+    const int cfg = nisqa_gemm_f32_one_tile(m, n, &bm, &bn);
     const int64_t tiles = ((m + bm - 1) / bm) * ((n + bn - 1) / bn);
     if (tiles == 0) return NISQA_OK;
     if (tiles > 0x7fffffff) return NISQA_ERR_ARG;

@@ -67,7 +67,9 @@ def test_gemm_single_group_all_layouts(M, N, K, ta, tb):
 
 def test_gemm_bias_relu_epilogue_and_large_tiles():
     lib, L = _L()
-    for M, N, K in [(700, 64, 288), (600, 300, 64), (64, 576, 3000), (1000, 16, 144)]:      # every tile configuration
+    # by nisqa_gemm_f32_one_tile: 64x64, 64x64 (the 256x64 and 128x128 tiles start at 192 workgroups), 64x256, 128x32 --
+    # tests/test_gpu_gemm_tiles.py runs every tile configuration; test_gemm_tiles_host.py pins what these four select
+    for M, N, K in [(700, 64, 288), (600, 300, 64), (64, 576, 3000), (1000, 16, 144)]:
         A, W, b = _r(M, K, seed=40), _r(N, K, seed=41), _r(N, seed=42)
         C = torch.empty(M, N, device=DEV)
         lib.check(L.nisqa_gemm_f32_one(_p(A), _p(W), _p(C), M, N, K, K, K, N, 0, 1, 1, 1.0, _p(b), 1, _st()), 'gemm')
@@ -190,6 +192,54 @@ def test_implicit_gemm_convolution_forward_dgrad_wgrad(h, w, ci, co, pad_w, S, e
     assert torch.equal(z2, z)
     assert (st2[:co] - z.double().sum(0)).abs().max() < 1e-9 * float(z.double().abs().sum(0).max())
     assert (st2[co:] - (z.double() ** 2).sum(0)).abs().max() < 1e-9 * float((z.double() ** 2).sum(0).max())
+
+
+_IGEMM_EXACT = {}           # the int64-exact convolution of the latest case, shared by the two entries
+
+
+def _igemm_exact_case(h, w, ci, co, pad_w, S):
+    """Activations, weights, bias and output gradient as integers in [-8, 8] and their convolution, input gradient and weight
+    gradient from F.conv2d in float64 on the CPU.  Every partial sum is an integer below 2^24 (the longest, the weight gradient's,
+    has S * h * wo <= 7 104 terms of at most 64), so float64 holds the int64 result in any order -- and so does fp32."""
+    key = (h, w, ci, co, pad_w, S)
+    if _IGEMM_EXACT.get('key') != key:
+        g = torch.Generator().manual_seed(54)
+        wo = w + 2 * pad_w - 2
+        x, wt, b, dz = (torch.randint(-8, 9, s, generator=g).double() for s in ((S, h * w, ci), (co, ci, 3, 3), (co,), (S, h * wo, co)))
+        x.requires_grad_(True)
+        wt.requires_grad_(True)
+        z = F.conv2d(x.view(S, h, w, ci).permute(0, 3, 1, 2), wt, b, padding=(1, pad_w)).permute(0, 2, 3, 1).reshape(S, h * wo, co)
+        (z * dz).sum().backward()
+        want = (z.detach().reshape(S * h * wo, co), x.grad, wt.grad.permute(0, 2, 3, 1).reshape(co, 9 * ci))
+        assert all(float(t.abs().max()) < 2 ** 24 and bool((t == t.round()).all()) for t in want)
+        _IGEMM_EXACT.clear()
+        _IGEMM_EXACT.update(key=key, x=x.detach().float().to(DEV), wk=wt.detach().permute(0, 2, 3, 1).reshape(co, 9 * ci).float().to(DEV),
+                            b=b.float().to(DEV), dz=dz.float().to(DEV), want=[t.float().to(DEV) for t in want])
+    return _IGEMM_EXACT
+
+
+@pytest.mark.parametrize('entry', ['nisqa_conv3x3_gemm', 'nisqa_conv3x3_gemm_bf16'])
+@pytest.mark.parametrize('h,w,ci,co,pad_w,S', _IGEMM_CASES)
+def test_implicit_gemm_convolution_exact_on_integers(h, w, ci, co, pad_w, S, entry):
+    """Forward with bias, input gradient and split-K weight gradient of both entries, bit for bit: on integers up to 8 every
+    summation order and the split-K atomics give the integer result, and the split-bf16 entry's lo terms are zero (its three
+    products are exact), so one wrong border tap at one pixel of one tile cannot hide behind a tolerance."""
+    lib, L = _L()
+    conv = getattr(L, entry)
+    c = _igemm_exact_case(h, w, ci, co, pad_w, S)
+    ksplit = 5 if S == 37 else 3
+    wo = w + 2 * pad_w - 2
+    z = torch.full((S * h * wo, co), float('nan'), device=DEV)
+    lib.check(conv(0, _p(c['x']), _p(c['wk']), _p(z), S, h, w, ci, co, pad_w, _p(c['b']), 1, _st()), 'conv fwd')
+    dx = torch.full((S, h * w, ci), float('nan'), device=DEV)
+    lib.check(conv(1, _p(c['dz']), _p(c['wk']), _p(dx), S, h, w, ci, co, pad_w, None, 1, _st()), 'conv dgrad')
+    dw = torch.zeros(co, 9 * ci, device=DEV)
+    lib.check(conv(2, _p(c['x']), _p(c['dz']), _p(dw), S, h, w, ci, co, pad_w, None, ksplit, _st()), 'conv wgrad')
+    torch.cuda.synchronize()
+    want_z, want_dx, want_dw = c['want']
+    assert torch.equal(z, want_z)
+    assert torch.equal(dx, want_dx)
+    assert torch.equal(dw, want_dw)
 
 
 @pytest.mark.parametrize('S', [1, 14, 37, 61, 600])
