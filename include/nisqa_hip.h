@@ -220,6 +220,26 @@ int nisqa_td_pool_bf16x6(const float* feat, const int32_t* tok_off, const int32_
 int nisqa_pool_final(const int32_t* tok_off, const int32_t* n_wins, int32_t n_clips,
                      int32_t total_tok_padded, int32_t n_heads, const float* ws, float* out, void* stream);
 
+/* Per-segment profile of a pooled score: what a forward hook on model.pool shows in the reference -- PoolAttFF.forward
+ * (NISQA_lib.py:1171-1183) and PoolAvg.forward (NISQA_lib.py:1196-1205) taken apart per token.  PoolAttFF computes
+ * linear3(sum_t a_t x_t) with sum_t a_t = 1, so score = sum_t a_t (w3 . x_t + b3); PoolAvg the same with a_t = 1 / n.
+ * x [dev]: the token rows the pooling read, rows of `ld` floats in the tok_off layout (clip c: rows tok_off[c] .. + n_wins[c]; every
+ * tok_off a multiple of 64); rows behind n_wins are never read.
+ *   mode 0 (PoolAttFF, ld = 64, n_heads 1..5): per token and head logit = w2 . relu(W1 x + b1) + b2 (hidden width 128),
+ *          local = w3 . x + b3, weights = softmax of the logits over the clip's n_wins tokens;
+ *   mode 1 (PoolAvg on the BiLSTM output, ld = 256, n_heads = 1): local = w . h_t + b, weights = 1 / n_wins.
+ * w [dev]: fp32, natural order -- mode 0: per head W1 [128][64], b1 [128], w2 [128], b2, w3 [64], b3 (8514 floats,
+ * nisqa_amd.weights.pack_pool_profile); mode 1: w [256], b (pack_pool_profile_avg).  Not the MFMA-fragment blobs of nisqa_pool_att*.
+ * weights_out, local_out [dev]: [total_tok_padded][n_heads]; padding rows (behind n_wins up to the next clip's first row, behind the
+ * last clip up to total_tok_padded) are written as zeros.  Every dot product is one k-ordered fp32 fmaf chain from the bias, the
+ * same in every precision form of the engine; a clip's maximum and sum are taken in a fixed order and nothing is accumulated
+ * atomically: two calls give the same bits.  One launch, one workgroup per clip and head.
+ * NULL pointers, n_clips <= 0, total_tok_padded <= 0, n_heads outside 1..5 (mode 1: other than 1), mode outside {0, 1} or an ld that
+ * is not the mode's return NISQA_ERR_ARG before any launch. */
+int nisqa_pool_profile(const float* x, int32_t ld, const int32_t* tok_off, const int32_t* n_wins, int32_t n_clips,
+                       int32_t total_tok_padded, int32_t n_heads, int32_t mode, const float* w, float* weights_out,
+                       float* local_out, void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * nisqa_tts.tar architecture.
  * nisqa_cnn_standard replaces segment_specs + Framewise.forward + StandardCNN.forward incl. fc_out

@@ -215,18 +215,9 @@ class _NisqaBase(nn.Module):
         (ValueError); a clip too short for one segment or with more than ms_max_segments segments (engine.BatchPlan's
         ValueErrors); a gradient in a fast precision, or while the checkpoint's ms_sr differs from sr -- the resampler has no
         backward -- (NotImplementedError; the plain call still works)."""
-        from .engine import DEFAULT_PRECISION, BatchPlan
-        from .melbank import resampled_lengths
-        y2, n = _audio_args(y, lengths)
-        if int(sr) != sr or int(sr) < 1:
-            raise ValueError('sr must be one positive integer rate for the batch, got {}'.format(sr))
-        sr, args = int(sr), self._engine_args
-        if args is None:
-            raise RuntimeError('bind_args(checkpoint_args) must be called before the HIP engine is built')
-        rate = sr if args.get('ms_sr') is None else int(args['ms_sr'])
-        # the engine's audio_plan(n, sr), on the host: too short a clip and too many segments raise here
-        plan = BatchPlan(n if rate == sr else resampled_lengths(n, sr, rate)[0], int(rate * args['ms_hop_length']),
-                         int(args['ms_seg_hop_length']), args['ms_max_segments'])
+        from .engine import DEFAULT_PRECISION
+        y2, n, sr, plan = self._audio_plan(y, sr, lengths)
+        rate = sr if self._engine_args.get('ms_sr') is None else int(self._engine_args['ms_sr'])
         dev = y.device if y.is_cuda else None
         if not (torch.is_grad_enabled() and y.requires_grad):
             eng = self.engine(dev)
@@ -240,6 +231,87 @@ class _NisqaBase(nn.Module):
         eng = self.engine(dev)
         # the Function sees the samples the kernels read: torch supplies the adjoint of the device / dtype / rank conversion
         return _AudioFunction.apply(y2.to(eng.device, dtype=torch.float32), eng, n, sr, plan)
+
+    def profile_audio(self, y, sr, lengths=None):
+        """forward_audio with every score taken apart per segment: the same arguments, the same checks and the same refusals
+        (forward_audio's, raised before any GPU work) -> SegmentProfile (see there) with
+          scores [B, heads]           forward_audio's, bit for bit, in every engine precision;
+          weights, local [B, Lmax, heads]   the share a_l of segment l in the score and what the segment says on its own, in MOS
+                                      units: score = sum_l weights * local up to float32 rounding (PoolAttFF: the attention
+                                      weights and w3 . x_l + b3; PoolAvg: 1 / n_wins and w . h_l + b; DESIGN.md 4.10);
+          embed [B, Lmax, D]          the rows the pooling read (D = 64 behind self-attention, 256 behind the BiLSTM);
+          n_wins [B], t_start / t_end [Lmax]   the segment counts and each segment's span in seconds.
+        Rows l >= n_wins[b] are exact zeros.  pool=last_step_bi and pool=max have no such decomposition: NotImplementedError naming
+        the pool, before any GPU work.  The result is detached: gradients are out of scope here, whatever y requires (use
+        forward_audio for d score / d y).  Not a throughput path."""
+        from .engine import check_profile_args
+        y2, n, sr, plan = self._audio_plan(y, sr, lengths)
+        check_profile_args(self._engine_args)
+        eng = self.engine(y.device if y.is_cuda else None)
+        with torch.no_grad():
+            prof = eng.profile_audio(_pack_clips(y2.detach().to(eng.device, dtype=torch.float32), n), n, sr, plan)
+        return _segment_profile(prof, plan.n_wins, self._engine_args)
+
+    def _audio_plan(self, y, sr, lengths):
+        """The argument checks of forward_audio and the plan it builds, on the host -> (y as [B, N], lengths, sr, plan)"""
+        from .engine import BatchPlan
+        from .melbank import resampled_lengths
+        y2, n = _audio_args(y, lengths)
+        if int(sr) != sr or int(sr) < 1:
+            raise ValueError('sr must be one positive integer rate for the batch, got {}'.format(sr))
+        sr, args = int(sr), self._engine_args
+        if args is None:
+            raise RuntimeError('bind_args(checkpoint_args) must be called before the HIP engine is built')
+        rate = sr if args.get('ms_sr') is None else int(args['ms_sr'])
+        # the engine's audio_plan(n, sr), on the host: too short a clip and too many segments raise here
+        plan = BatchPlan(n if rate == sr else resampled_lengths(n, sr, rate)[0], int(rate * args['ms_hop_length']),
+                         int(args['ms_seg_hop_length']), args['ms_max_segments'])
+        return y2, n, sr, plan
+
+
+class SegmentProfile(object):
+    """What profile_audio returns.  scores [B, heads], weights / local [B, Lmax, heads], embed [B, Lmax, D] and (NISQA_DE)
+    aligned_to [B, Lmax] are detached tensors on the engine's device, Lmax the largest segment count of the batch; n_wins [B]
+    (int64) and t_start / t_end [Lmax] (float64, seconds) are host tensors.  heads: the names of the head axis, in order."""
+    __slots__ = ('scores', 'weights', 'local', 'embed', 'n_wins', 't_start', 't_end', 'aligned_to', 'heads')
+
+    def __init__(self, **kw):
+        for k in self.__slots__:
+            setattr(self, k, kw.get(k))
+
+    def __repr__(self):
+        return 'SegmentProfile(B={}, Lmax={}, heads={})'.format(self.scores.shape[0], self.weights.shape[1], list(self.heads))
+
+
+HEAD_NAMES = {1: ('mos',), 5: ('mos', 'noi', 'dis', 'col', 'loud')}          # the head axis of NISQA / NISQA_DE and of NISQA_DIM
+
+
+def segment_times(args, n_segments):
+    """(t_start, t_end) of segments 0 .. n_segments - 1 in seconds, float64: segment l covers the ms_seg_length frames from frame
+    l * ms_seg_hop_length on, a frame being ms_hop_length seconds (NL:2266-2280)."""
+    first = np.arange(int(n_segments), dtype=np.float64) * int(args['ms_seg_hop_length'])
+    hop = float(args['ms_hop_length'])
+    return first * hop, (first + int(args['ms_seg_length'])) * hop
+
+
+def _segment_profile(prof, n_wins, args):
+    """engine.PoolProfile in the plan's token layout (n_wins: the counts of the clips it covers) -> SegmentProfile [B, Lmax, ...]"""
+    from .engine import BatchPlan
+    n = np.asarray(n_wins, np.int64)
+    tok_off, L = BatchPlan.from_n_wins(n).tok_off, int(n.max())
+    valid = np.arange(L)[None, :] < n[:, None]
+    dev = prof.scores.device
+    rows = torch.from_numpy(np.where(valid, tok_off[:-1, None].astype(np.int64) + np.arange(L)[None, :], 0)).to(dev)
+    pad = ~torch.from_numpy(valid).to(dev)
+    cut = lambda t: t.detach()[rows].masked_fill(pad[..., None], 0.0)
+    t0, t1 = segment_times(args, L)
+    aligned = None
+    if args.get('model') == 'NISQA_DE':                            # hard alignment: the engine's indices; soft: -1 everywhere
+        aligned = torch.full((len(n), L), -1, dtype=torch.int64, device=dev) if prof.aligned_to is None else \
+            prof.aligned_to.detach().to(torch.int64)[rows].masked_fill(pad, -1)
+    return SegmentProfile(scores=prof.scores.detach(), weights=cut(prof.weights), local=cut(prof.local), embed=cut(prof.embed),
+                          n_wins=torch.from_numpy(n.copy()), t_start=torch.from_numpy(t0), t_end=torch.from_numpy(t1),
+                          aligned_to=aligned, heads=HEAD_NAMES[prof.scores.shape[1]])
 
 
 def _audio_args(y, lengths, name='y', size='N'):
@@ -468,7 +540,44 @@ class NISQA_DE(nn.Module):
         than ms_max_segments segments (engine.BatchPlan's ValueErrors); a gradient in a fast precision, or while the
         checkpoint's ms_sr differs from sr -- the resampler has no backward -- (NotImplementedError; the plain call still
         works)."""
-        from .engine import DEFAULT_PRECISION, BatchPlan
+        from .engine import DEFAULT_PRECISION
+        d2, r2, n_deg, n_ref, sr, plan = self._audio_plan(y_deg, y_ref, sr, lengths_deg, lengths_ref)
+        rate = sr if self._engine_args.get('ms_sr') is None else int(self._engine_args['ms_sr'])
+        dev = y_deg.device if y_deg.is_cuda else (y_ref.device if y_ref.is_cuda else None)
+        if not (torch.is_grad_enabled() and (y_deg.requires_grad or y_ref.requires_grad)):
+            eng = self.engine(dev)
+            to = lambda y: y.detach().to(eng.device, dtype=torch.float32)
+            return _score_audio_de(eng, to(d2), to(r2), n_deg, n_ref, sr, plan)
+        from .input_grad import check_precision
+        check_precision(self._engine.precision if self._engine is not None
+                        else os.environ.get('NISQA_HIP_PRECISION') or DEFAULT_PRECISION)
+        if rate != sr:
+            raise NotImplementedError('the gradient with respect to the audio needs sr == ms_sr ({} != {}): the resampler has no '
+                                      'backward; the plain call works'.format(sr, rate))
+        eng = self.engine(dev)
+        # the Function sees the samples the kernels read: torch supplies the adjoint of the device / dtype / rank conversion
+        to = lambda y: y.to(eng.device, dtype=torch.float32)
+        return _AudioFunctionDE.apply(to(d2), to(r2), eng, n_deg, n_ref, sr, plan)
+
+    def profile_audio(self, y_deg, y_ref, sr, lengths_deg=None, lengths_ref=None):
+        """forward_audio with the score taken apart per segment of the DEGRADED clip: the same arguments, checks and refusals
+        (forward_audio's, raised before any GPU work) -> SegmentProfile as _NisqaBase.profile_audio returns it (scores [B, 1]
+        forward_audio's, bit for bit; weights, local [B, Lmax, 1]; embed [B, Lmax, 64], the second self-attention's output;
+        n_wins [B] of the degraded clips; t_start / t_end [Lmax]) and additionally
+          aligned_to [B, Lmax] int64   the reference segment each degraded segment was aligned to with hard alignment
+                                       (HipNisqaDE.forward_pcm(..., want_idx=True)); -1 with soft alignment and on padding rows.
+        The result is detached: gradients are out of scope here (use forward_audio for them).  Not a throughput path."""
+        d2, r2, n_deg, n_ref, sr, plan = self._audio_plan(y_deg, y_ref, sr, lengths_deg, lengths_ref)
+        eng = self.engine(y_deg.device if y_deg.is_cuda else (y_ref.device if y_ref.is_cuda else None))
+        to = lambda y: y.detach().to(eng.device, dtype=torch.float32)
+        with torch.no_grad():
+            prof = eng.profile_audio(torch.cat([_pack_clips(to(d2), n_deg), _pack_clips(to(r2), n_ref)]), n_deg, n_ref, sr, plan)
+        return _segment_profile(prof, plan.n_wins[:len(n_deg)], dict(self._engine_args, model='NISQA_DE'))
+
+    def _audio_plan(self, y_deg, y_ref, sr, lengths_deg, lengths_ref):
+        """The argument checks of forward_audio and the 2B-clip plan it builds, on the host
+        -> (y_deg as [B, N], y_ref as [B, M], lengths_deg, lengths_ref, sr, plan)"""
+        from .engine import BatchPlan
         from .melbank import resampled_lengths
         d2, n_deg = _audio_args(y_deg, lengths_deg, 'y_deg', 'N')
         r2, n_ref = _audio_args(y_ref, lengths_ref, 'y_ref', 'M')
@@ -487,21 +596,7 @@ class NISQA_DE(nn.Module):
         n2 = np.concatenate([n_deg, n_ref])
         plan = BatchPlan(n2 if rate == sr else resampled_lengths(n2, sr, rate)[0], int(rate * args['ms_hop_length']),
                          int(args['ms_seg_hop_length']), args['ms_max_segments'])
-        dev = y_deg.device if y_deg.is_cuda else (y_ref.device if y_ref.is_cuda else None)
-        if not (torch.is_grad_enabled() and (y_deg.requires_grad or y_ref.requires_grad)):
-            eng = self.engine(dev)
-            to = lambda y: y.detach().to(eng.device, dtype=torch.float32)
-            return _score_audio_de(eng, to(d2), to(r2), n_deg, n_ref, sr, plan)
-        from .input_grad import check_precision
-        check_precision(self._engine.precision if self._engine is not None
-                        else os.environ.get('NISQA_HIP_PRECISION') or DEFAULT_PRECISION)
-        if rate != sr:
-            raise NotImplementedError('the gradient with respect to the audio needs sr == ms_sr ({} != {}): the resampler has no '
-                                      'backward; the plain call works'.format(sr, rate))
-        eng = self.engine(dev)
-        # the Function sees the samples the kernels read: torch supplies the adjoint of the device / dtype / rank conversion
-        to = lambda y: y.to(eng.device, dtype=torch.float32)
-        return _AudioFunctionDE.apply(to(d2), to(r2), eng, n_deg, n_ref, sr, plan)
+        return d2, r2, n_deg, n_ref, sr, plan
 
 
 # ---------------------------------------------------------------------------------------------

@@ -402,6 +402,66 @@ class nisqaModel(object):
         self.timing = {'predict_s': t1 - t0, 'table_s': time.perf_counter() - t1}
         return self.ds_val.df
 
+    def profile(self):
+        """Where in each file its score comes from: one long-form frame with a row per file and segment, for the files
+        ``predict()`` would score (the three predict modes).  Columns: the file column, ``seg``, ``t_start`` / ``t_end`` (seconds),
+        per head ``w_<name>`` (the segment's share of the score, summing to 1 per file) and ``local_<name>`` (what the segment says
+        on its own, in MOS units) with <name> = mos [, noi, dis, col, loud], and for NISQA_DE ``aligned_to`` (the reference segment a
+        degraded segment was aligned to; -1 with soft alignment).  Per file sum(w * local) is the prediction up to float32 rounding
+        (engine.HipNisqa.profile_pcm).  Written as NISQA_profile.csv when output_dir is set.
+        A plain loop -- files read one by one on the host, batches of tr_bs_val files grouped by sample rate, the stages of the
+        engine run one by one -- and NOT the throughput path: predict() is.  One process; ranks are not sharded."""
+        from .engine import BatchPlan, check_profile_args
+        check_profile_args(self.args)                            # pool=last_step_bi / max: refused before any file is read
+        ds, de = self.ds_val, bool(self.args['double_ended'])
+        eng = self.model.engine(self.dev)
+        heads = NL.HEAD_NAMES[5 if self.args['dim'] == True else 1]  # noqa: E712
+        names, bs = ds.df[ds.filename_column].tolist(), max(1, int(self.args['tr_bs_val']))
+        ref = ds.ref_view() if de else None
+        as_f32 = lambda y: y.astype(np.float32) / np.float32(32768.0) if y.dtype == np.int16 else y
+        frames = [None] * len(ds)
+        for first in range(0, len(ds), bs):
+            groups = {}
+            for i in range(first, min(first + bs, len(ds))):
+                y, sr = ds.load_audio(i)
+                item = (y,)
+                if de:
+                    yr, sr_ref = ref.load_audio(i)
+                    if sr_ref != sr:
+                        raise NotImplementedError('profile(): {} ({} Hz) and its reference ({} Hz) differ in sample rate'.format(
+                            ds.file_path(i), sr, sr_ref))
+                    item = (y, yr) if y.dtype == yr.dtype else (as_f32(y), as_f32(yr))
+                groups.setdefault((int(sr), item[0].dtype == np.int16), []).append((i, item))
+            for (sr, _), members in groups.items():
+                ids = [i for i, _ in members]
+                sides = [[it[s] for _, it in members] for s in range(2 if de else 1)]
+                lengths = [[len(y) for y in side] for side in sides]
+                pcm = torch.from_numpy(np.concatenate(sides[0] + (sides[1] if de else []))).to(eng.device)
+                paths = ds.file_paths(ids) + (ref.file_paths(ids) if de else [])
+                if de:
+                    plan = eng.audio_plan(lengths[0], lengths[1], sr, names=paths)
+                    prof = eng.profile_audio(pcm, lengths[0], lengths[1], sr, plan)
+                    plan = BatchPlan.from_n_wins(plan.n_wins[:len(ids)])               # the degraded clips' tokens
+                else:
+                    plan = eng.audio_plan(lengths[0], sr, names=paths)
+                    prof = eng.profile_audio(pcm, lengths[0], sr, plan)
+                w, loc = prof.weights.cpu().numpy(), prof.local.cpu().numpy()
+                idx = prof.aligned_to.cpu().numpy() if prof.aligned_to is not None else None
+                for k, i in enumerate(ids):
+                    n, r0 = int(plan.n_wins[k]), int(plan.tok_off[k])
+                    t0, t1 = NL.segment_times(self.args, n)
+                    cols = {ds.filename_column: [names[i]] * n, 'seg': np.arange(n), 't_start': t0, 't_end': t1}
+                    for h, name in enumerate(heads):
+                        cols['w_' + name] = w[r0:r0 + n, h].astype(np.float64)
+                        cols['local_' + name] = loc[r0:r0 + n, h].astype(np.float64)
+                    if de:
+                        cols['aligned_to'] = idx[r0:r0 + n].astype(np.int64) if idx is not None else np.full(n, -1, np.int64)
+                    frames[i] = pd.DataFrame(cols)
+        df = pd.concat(frames, ignore_index=True)
+        if self.args['output_dir']:
+            df.to_csv(os.path.join(self.args['output_dir'], 'NISQA_profile.csv'), index=False)
+        return df
+
     # ---- datasets (reference NISQA_model.py:732-847) ---------------------------------------------
     def _loadDatasets(self):
         if self.args['double_ended'] and self.args['mode'] in ('predict_file', 'predict_dir'):

@@ -220,6 +220,20 @@ def check_lstm_args(args, n_heads=1):
     return LSTM_ARCH[pool]
 
 
+# What profile_pcm / profile_segments return (HipNisqa, HipNisqaDE): device tensors in the plan's token layout.  aligned_to: NISQA_DE
+# with hard alignment only -- int32 [NP], the reference token each degraded token was aligned to (-1 on padding rows) --, else None.
+PoolProfile = collections.namedtuple('PoolProfile', 'scores embed weights local aligned_to')
+
+
+def check_profile_args(args):
+    """A score splits into per-segment weights and local scores where the pooling is a weighted mean followed by a linear layer:
+    PoolAttFF and PoolAvg.  The last LSTM step (last_step_bi) and the maximum over time (max) are no such mean: NotImplementedError
+    naming the pool, before any GPU work (no device is touched here)."""
+    if args.get('td') == 'lstm' and args.get('pool') != 'avg':
+        raise NotImplementedError('a score has no per-segment profile with pool={} (pool=att and pool=avg have one)'.format(
+            args.get('pool')))
+
+
 class HipNisqa(object):
     """nisqa.tar / nisqa_mos_only.tar (CNN-SA-AP) on one MI355X."""
 
@@ -273,6 +287,7 @@ class HipNisqa(object):
         self._ws = {}                      # one workspace per stream (batches may be in flight on several)
         self._flac_ws = {}                 # the same for nisqa_flac_decode
         self._state_dict, self._input_grad = state_dict, None     # grad_segments builds its operator chain from them on first use
+        self._profile_w = None                                      # pool_profile packs its blob from state_dict on first use
         if self.arch >= 1:
             # StandardCNN (split 16-bit or exact-fp32 MFMA) + BiLSTM + last-step / average / max pooling (fp32 VALU in every mode)
             self.n_layers, self.n_heads = 0, 1
@@ -685,12 +700,15 @@ class HipNisqa(object):
         _lib.check(getattr(self.lib, name)(*args), what)
         return x
 
-    def td_pool(self, feat, plan, td_w=None, td_wb=None, n_layers=None, pool_w=None, pool_wb=None, n_heads=None):
+    def td_pool(self, feat, plan, td_w=None, td_wb=None, n_layers=None, pool_w=None, pool_wb=None, n_heads=None, want_x=False):
         """self-attention + attention pooling as the whole-batch forward runs them: in the three-term modes ONE chain of
-        n_layers + 1 launches (nisqa_td_pool_bf16x6), otherwise td() then pool()"""
+        n_layers + 1 launches (nisqa_td_pool_bf16x6), otherwise td() then pool().  want_x: -> (out, x [NP, 64]), x the rows the
+        pooling read (the chain writes them in either form; rows of padding tokens hold whatever the kernels left there)"""
         fused = TD[self.td_precision].fused
         if not fused:
-            return self.pool(self.td(feat, plan, td_w, td_wb, n_layers), plan, pool_w, pool_wb, n_heads)
+            x = self.td(feat, plan, td_w, td_wb, n_layers)
+            out = self.pool(x, plan, pool_w, pool_wb, n_heads)
+            return (out, x) if want_x else out
         td_w, td_wb, n_layers = _or(td_w, self.td_w), _or(td_wb, self.td_wb), _or(n_layers, self.n_layers)
         pool_wb, n_heads = _or(pool_wb, self.pool_wb), _or(n_heads, self.n_heads)
         d = plan.to(self.device)
@@ -701,7 +719,7 @@ class HipNisqa(object):
         _lib.check(getattr(self.lib, fused)(_ptr(feat), _ptr(d['tok_off']), _ptr(d['n_wins']), plan.n_clips, plan.total_tok, n_layers,
                                             _ptr(td_w), _ptr(td_wb), n_heads, _ptr(pool_wb), _ptr(ws), _ptr(x), _ptr(wsp), _ptr(out),
                                             self._stream()), fused)
-        return out
+        return (out, x) if want_x else out
 
     def pool(self, x, plan, pool_w=None, pool_wb=None, n_heads=None):
         """attention pooling -> [B, n_heads]; the weights default to the engine's own"""
@@ -714,6 +732,68 @@ class HipNisqa(object):
                                    _ptr(pool_wb) if pool_wb is not None else None, (_ptr(ws), _ptr(out), self._stream()))
         _lib.check(getattr(self.lib, name)(*args), what)
         return out
+
+    # -- per-segment profile of a score (csrc/pool_profile.hip) ---------------------------------------------------
+    def pool_profile(self, x, plan):
+        """nisqa_pool_profile on the rows x the pooling read ([NP, 64] behind self-attention, [NP, 256] behind the BiLSTM with
+        pool=avg) -> (weights [NP, heads], local [NP, heads]); rows of padding tokens are never read and come back as zeros."""
+        check_profile_args(self.args)
+        mode, ld = (0, 64) if self.arch == 0 else (1, 256)
+        assert x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() and tuple(x.shape) == (plan.total_tok, ld)
+        if self._profile_w is None:
+            heads = ['pool_layers.%d.model.' % h for h in range(5)] if self.dim else ['pool.model.']
+            blob = _w.pack_pool_profile(self._state_dict, heads) if mode == 0 else _w.pack_pool_profile_avg(self._state_dict)
+            self._profile_w = torch.from_numpy(blob).to(self.device)
+        d = plan.to(self.device)
+        weights = torch.empty((plan.total_tok, self.n_heads), dtype=torch.float32, device=self.device)
+        local = torch.empty((plan.total_tok, self.n_heads), dtype=torch.float32, device=self.device)
+        _lib.check(self.lib.nisqa_pool_profile(_ptr(x), ld, _ptr(d['tok_off']), _ptr(d['n_wins']), plan.n_clips, plan.total_tok,
+                                               self.n_heads, mode, _ptr(self._profile_w), _ptr(weights), _ptr(local), self._stream()),
+                   'nisqa_pool_profile')
+        return weights, local
+
+    def _profile(self, scores, x, plan, aligned_to=None):
+        weights, local = self.pool_profile(x, plan)
+        valid = torch.zeros(plan.total_tok, dtype=torch.bool, device=self.device)
+        valid[torch.from_numpy(plan.token_index()).to(self.device)] = True
+        embed = torch.where(valid[:, None], x, torch.zeros((), dtype=x.dtype, device=self.device))     # padding rows: exact zeros
+        return PoolProfile(scores, embed, weights, local, aligned_to)
+
+    def profile_features(self, feat, plan):
+        """The CNN rows of a plan -> PoolProfile: the scores from the chain forward_pcm / forward_segments run (bit for bit theirs),
+        the rows that chain's pooling read, and nisqa_pool_profile on them."""
+        check_profile_args(self.args)
+        scores, x = self.td_pool(feat, plan, want_x=True) if self.arch == 0 else self.lstm(feat, plan, want_seq=True)
+        return self._profile(scores, x, plan)
+
+    def profile_pcm(self, pcm, plan, sr):
+        """forward_pcm with the score taken apart per segment -> PoolProfile(scores [B, heads], embed [NP, D], weights [NP, heads],
+        local [NP, heads]) in the plan's token layout (clip b: rows plan.tok_off[b] .. + plan.n_wins[b]; padding rows are exact zeros):
+          scores   forward_pcm's, bit for bit (the same kernels in the same order; they do not come from the profile);
+          embed    the rows the pooling read: the last self-attention layer's output (D = 64), or the BiLSTM's with pool=avg (256);
+          weights  the share a_t of segment t in the score: PoolAttFF's softmax over the clip's segments (one track per head, NISQA_DIM:
+                   mos, noi, dis, col, loud), 1 / n_wins for PoolAvg; they sum to 1 per clip and head;
+          local    what segment t says on its own, in MOS units: s_t = w3 . x_t + b3 (PoolAvg: w . h_t + b).
+        score = sum_t a_t s_t up to float32 rounding.  pool=last_step_bi and pool=max have no such decomposition:
+        NotImplementedError, before any GPU work.  Not a throughput path: the stages run one by one with their tensors in HBM."""
+        check_profile_args(self.args)
+        assert pcm.dtype in (torch.float32, torch.int16) and pcm.is_cuda and pcm.numel() == plan.total_samples
+        mel, floor = self.mel(pcm, plan, sr, clamp=False)
+        return self.profile_features(self.cnn(mel, floor, plan)[0] if self.arch == 0 else self.cnn_std(mel, floor, plan), plan)
+
+    def profile_audio(self, pcm, lengths, sr, plan):
+        """profile_pcm for a batch as the files hold it (resampled to ms_sr first when the checkpoint sets it; see forward_audio)"""
+        check_profile_args(self.args)
+        return self.profile_pcm(self.resample(pcm, lengths, sr), plan, self.rate(sr))
+
+    def profile_segments(self, x, n_wins):
+        """profile_pcm for the reference's inner operator model(x[B,L,1,48,15], n_wins[B]): scores are forward_segments', bit for bit;
+        the token layout is BatchPlan.from_n_wins(n_wins)'s."""
+        check_profile_args(self.args)
+        n = check_segments(x, n_wins, 1)
+        x = x.to(self.device, dtype=torch.float32).contiguous()
+        plan = BatchPlan.from_n_wins(n)
+        return self.profile_features(self.cnn_segments(x, plan) if self.arch == 0 else self.cnn_std_segments(x, plan), plan)
 
 
 # -- NISQA_DE (double-ended): reference NISQA_lib.py:272-424 ------------------------------------------------------------------
@@ -808,11 +888,12 @@ class HipNisqaDE(object):
                    'nisqa_de_align_fuse')
         return out, idx
 
-    def td2_pool(self, fused, dplan):
-        """time_dependency_2 + pool on the fused features of the degraded clips (dplan: their plan) -> [B, 1]"""
+    def td2_pool(self, fused, dplan, want_x=False):
+        """time_dependency_2 + pool on the fused features of the degraded clips (dplan: their plan) -> [B, 1]; want_x: and the rows
+        the pooling read (HipNisqa.td_pool)"""
         b = self.base
         return b.td_pool(fused, dplan, td_w=self.td2_w, td_wb=self.td2_wb, n_layers=self.n_layers2, pool_w=b.pool_w, pool_wb=b.pool_wb,
-                         n_heads=1)
+                         n_heads=1, want_x=want_x)
 
     def forward_features(self, feat, plan, want_idx=False):
         """feat [NP, 384]: AdaptCNN output of the plan's 2B clips -> ([B, 1], hard-mode indices or None)"""
@@ -857,6 +938,27 @@ class HipNisqaDE(object):
         """pcm: device tensor of the plan's 2B clips back to back (degraded, then reference; float32 or int16 PCM) -> [B, 1]"""
         assert pcm.is_cuda and pcm.numel() == plan.total_samples
         return self.forward_features(self.features(pcm, plan, sr), plan, want_idx)
+
+    # -- per-segment profile of a score (HipNisqa.profile_pcm, DESIGN.md 4.10) ---------------------------------------------------
+    def profile_features(self, feat, plan):
+        """forward_features with the score taken apart over the DEGRADED clips' tokens -> PoolProfile in the token layout of
+        BatchPlan.from_n_wins(plan.n_wins[:B]): scores forward_features', bit for bit; embed the second self-attention's output;
+        aligned_to the hard alignment's reference token per degraded token (what want_idx returns), None with soft alignment."""
+        hard = self.apply == DE_APPLY['hard']
+        fused, idx = self.align_fuse(self.base.td(feat, plan), plan, want_idx=hard)
+        dplan = BatchPlan.from_n_wins(plan.n_wins[:plan.n_clips // 2])
+        scores, x = self.td2_pool(fused, dplan, want_x=True)
+        return self.base._profile(scores, x, dplan, idx)
+
+    def profile_pcm(self, pcm, plan, sr):
+        """forward_pcm with the score taken apart per segment of the degraded clip (profile_features)"""
+        assert pcm.is_cuda and pcm.numel() == plan.total_samples
+        return self.profile_features(self.features(pcm, plan, sr), plan)
+
+    def profile_audio(self, pcm, lengths_deg, lengths_ref, sr, plan):
+        """profile_pcm for 2B clips as the caller holds them (resampled to ms_sr first when the checkpoint sets it; forward_audio)"""
+        b = self.base
+        return self.profile_pcm(b.resample(pcm, list(lengths_deg) + list(lengths_ref), sr), plan, b.rate(sr))
 
     def audio_plan(self, lengths_deg, lengths_ref, sr, names=None):
         """plan() of 2B clips of rate ``sr`` as the network sees them (resampled to ms_sr when the checkpoint sets it)."""

@@ -506,3 +506,41 @@ def pack_pool_att_t16(sd, head_prefixes):
             par[2 * h + j, 192] = _np(sd, p + 'linear2.bias').reshape(-1)[0]
             par[2 * h + j, 193] = _np(sd, p + 'linear3.bias').reshape(-1)[0]
     return np.concatenate([frags.reshape(-1), par.reshape(-1).view(np.uint16)])
+
+
+# ---- per-segment profile of a pooled score (csrc/pool_profile.hip) ---------------------------------------------
+PP_W1 = 0                       # linear1.weight [128][64], row-major
+PP_B1 = PP_W1 + 128 * 64        # linear1.bias [128]
+PP_W2 = PP_B1 + 128             # linear2.weight [128]
+PP_B2 = PP_W2 + 128             # linear2.bias
+PP_W3 = PP_B2 + 1               # linear3.weight [64]
+PP_B3 = PP_W3 + 64              # linear3.bias
+PP_FLOATS = PP_B3 + 1           # 8514 floats per head
+PP_AVG_FLOATS = 257             # PoolAvg: linear.weight [256], linear.bias
+
+
+def pack_pool_profile(sd, head_prefixes):
+    """PoolAttFF heads for nisqa_pool_profile (mode 0) in natural order: per head linear1.weight [128][64], linear1.bias, linear2.weight,
+    linear2.bias, linear3.weight, linear3.bias -> float32 [n_heads * PP_FLOATS]"""
+    blob = np.zeros(len(head_prefixes) * PP_FLOATS, np.float32)
+    for h, p in enumerate(head_prefixes):
+        if tuple(sd[p + 'linear1.weight'].shape) != (128, 64):
+            raise NotImplementedError('HIP pooling kernel needs pool_att_h=128 on d=64')
+        head = blob[h * PP_FLOATS:(h + 1) * PP_FLOATS]
+        head[PP_W1:PP_B1] = _np(sd, p + 'linear1.weight').reshape(-1)
+        head[PP_B1:PP_W2] = _np(sd, p + 'linear1.bias')
+        head[PP_W2:PP_B2] = _np(sd, p + 'linear2.weight').reshape(-1)
+        head[PP_B2] = _np(sd, p + 'linear2.bias').reshape(-1)[0]
+        head[PP_W3:PP_B3] = _np(sd, p + 'linear3.weight').reshape(-1)
+        head[PP_B3] = _np(sd, p + 'linear3.bias').reshape(-1)[0]
+    return blob
+
+
+def pack_pool_profile_avg(sd, ppfx='pool.model.'):
+    """PoolAvg's [256] -> 1 linear layer for nisqa_pool_profile (mode 1): linear.weight [256], linear.bias -> float32 [PP_AVG_FLOATS]"""
+    if tuple(sd[ppfx + 'linear.weight'].shape) != (1, 256):
+        raise NotImplementedError('HIP pooling kernel needs the BiLSTM output width 256')
+    blob = np.zeros(PP_AVG_FLOATS, np.float32)
+    blob[:256] = _np(sd, ppfx + 'linear.weight').reshape(-1)
+    blob[256] = _np(sd, ppfx + 'linear.bias').reshape(-1)[0]
+    return blob
