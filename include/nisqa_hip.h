@@ -239,6 +239,20 @@ int nisqa_pool_final(const int32_t* tok_off, const int32_t* n_wins, int32_t n_cl
 int nisqa_pool_profile(const float* x, int32_t ld, const int32_t* tok_off, const int32_t* n_wins, int32_t n_clips,
                        int32_t total_tok_padded, int32_t n_heads, int32_t mode, const float* w, float* weights_out,
                        float* local_out, void* stream);
+/* The backward of mode 0 in x: dx = d (sum d_weights . weights + sum d_local . local + sum d_embed . x) / d x, x, the token layout and
+ * the blob w being nisqa_pool_profile's.  d_weights, d_local [dev]: [total_tok_padded][n_heads]; d_embed [dev]: [total_tok_padded][64];
+ * each may be NULL, which means zero.  With u = W1 x_t + b1, a = softmax_t(w2 . relu(u) + b2) per clip and head:
+ *   r = sum_u a_u d_weights_u;  dz_t = a_t (d_weights_t - r);  du_t = dz_t w2 * [u_t > 0];
+ *   dx_t = d_embed_t + sum_heads (W1^T du_t + d_local_t w3).
+ * Self-contained: the logits are recomputed from x with the forward's fmaf chains and reduced in the forward's fixed order; none of
+ * the forward's outputs is read.  dx [dev]: [total_tok_padded][64], every row written (its rows also park the logits while the call
+ * runs; it must not overlap x or a cotangent); padding rows get exact zeros, and neither x nor a cotangent is read there.  One launch,
+ * one workgroup per clip that walks the heads in order; no atomics: two calls give the same bits.  fp32 in every engine precision.
+ * mode != 0 (PoolAvg has no entry here), ld != 64, n_heads outside 1..5, NULL x / tok_off / n_wins / w / dx, n_clips <= 0 or
+ * total_tok_padded <= 0 return NISQA_ERR_ARG before any launch. */
+int nisqa_pool_profile_bwd(const float* x, int32_t ld, const int32_t* tok_off, const int32_t* n_wins, int32_t n_clips,
+                           int32_t total_tok_padded, int32_t n_heads, int32_t mode, const float* w, const float* d_weights,
+                           const float* d_local, const float* d_embed, float* dx, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * nisqa_tts.tar architecture.

@@ -215,24 +215,17 @@ class _NisqaBase(nn.Module):
         (ValueError); a clip too short for one segment or with more than ms_max_segments segments (engine.BatchPlan's
         ValueErrors); a gradient in a fast precision, or while the checkpoint's ms_sr differs from sr -- the resampler has no
         backward -- (NotImplementedError; the plain call still works)."""
-        from .engine import DEFAULT_PRECISION
         y2, n, sr, plan = self._audio_plan(y, sr, lengths)
-        rate = sr if self._engine_args.get('ms_sr') is None else int(self._engine_args['ms_sr'])
         dev = y.device if y.is_cuda else None
         if not (torch.is_grad_enabled() and y.requires_grad):
             eng = self.engine(dev)
             return _score_audio(eng, y2.detach().to(eng.device, dtype=torch.float32), n, sr, plan)
-        from .input_grad import check_precision
-        check_precision(self._engine.precision if self._engine is not None
-                        else os.environ.get('NISQA_HIP_PRECISION') or DEFAULT_PRECISION)
-        if rate != sr:
-            raise NotImplementedError('the gradient with respect to the audio needs sr == ms_sr ({} != {}): the resampler has no '
-                                      'backward; the plain call works'.format(sr, rate))
+        _check_audio_grad(self, sr)
         eng = self.engine(dev)
         # the Function sees the samples the kernels read: torch supplies the adjoint of the device / dtype / rank conversion
         return _AudioFunction.apply(y2.to(eng.device, dtype=torch.float32), eng, n, sr, plan)
 
-    def profile_audio(self, y, sr, lengths=None):
+    def profile_audio(self, y, sr, lengths=None, differentiable=False):
         """forward_audio with every score taken apart per segment: the same arguments, the same checks and the same refusals
         (forward_audio's, raised before any GPU work) -> SegmentProfile (see there) with
           scores [B, heads]           forward_audio's, bit for bit, in every engine precision;
@@ -242,15 +235,30 @@ class _NisqaBase(nn.Module):
           embed [B, Lmax, D]          the rows the pooling read (D = 64 behind self-attention, 256 behind the BiLSTM);
           n_wins [B], t_start / t_end [Lmax]   the segment counts and each segment's span in seconds.
         Rows l >= n_wins[b] are exact zeros.  pool=last_step_bi and pool=max have no such decomposition: NotImplementedError naming
-        the pool, before any GPU work.  The result is detached: gradients are out of scope here, whatever y requires (use
-        forward_audio for d score / d y).  Not a throughput path."""
-        from .engine import check_profile_args
+        the pool, before any GPU work.  Not a throughput path.
+        By default the result is detached, whatever y requires.  With ``differentiable=True``, gradients enabled and a y that
+        requires one, scores, weights, local and embed are the four outputs of ONE autograd function (values: the plain call's,
+        bit for bit) and backward delivers d / d y of whatever was built on them -- min_l local, a distance between embeddings -- in
+        y's shape, dtype and device, exact zeros at n >= lengths[b]: the four cotangents (None: zero; rows l >= n_wins[b] are
+        ignored whatever they hold) go through ONE recomputation and ONE backward chain (engine.HipNisqa.grad_profile_audio;
+        DESIGN.md 4.10).  No double backward, no gradient for the parameters.  Refused before any GPU work, as forward_audio
+        refuses a gradient: a fast precision, an ms_sr that differs from sr; and the StandardCNN + BiLSTM family with pool=avg,
+        whose backward through time takes no per-step gradient (NotImplementedError; its plain profile works).  With nothing to
+        differentiate, differentiable=True is the plain call."""
+        from .engine import check_profile_args, check_profile_grad_args
         y2, n, sr, plan = self._audio_plan(y, sr, lengths)
         check_profile_args(self._engine_args)
-        eng = self.engine(y.device if y.is_cuda else None)
-        with torch.no_grad():
-            prof = eng.profile_audio(_pack_clips(y2.detach().to(eng.device, dtype=torch.float32), n), n, sr, plan)
-        return _segment_profile(prof, plan.n_wins, self._engine_args)
+        dev = y.device if y.is_cuda else None
+        if not (differentiable and torch.is_grad_enabled() and y.requires_grad):
+            eng = self.engine(dev)
+            with torch.no_grad():
+                prof = eng.profile_audio(_pack_clips(y2.detach().to(eng.device, dtype=torch.float32), n), n, sr, plan)
+            return _segment_profile(prof, plan.n_wins, self._engine_args)
+        check_profile_grad_args(self._engine_args)
+        _check_audio_grad(self, sr)
+        eng = self.engine(dev)
+        # the Function sees the samples the kernels read: torch supplies the adjoint of the device / dtype / rank conversion
+        return _differentiable_profile(eng, (y2.to(eng.device, dtype=torch.float32),), (n,), sr, plan, self._engine_args)
 
     def _audio_plan(self, y, sr, lengths):
         """The argument checks of forward_audio and the plan it builds, on the host -> (y as [B, N], lengths, sr, plan)"""
@@ -271,8 +279,12 @@ class _NisqaBase(nn.Module):
 
 class SegmentProfile(object):
     """What profile_audio returns.  scores [B, heads], weights / local [B, Lmax, heads], embed [B, Lmax, D] and (NISQA_DE)
-    aligned_to [B, Lmax] are detached tensors on the engine's device, Lmax the largest segment count of the batch; n_wins [B]
-    (int64) and t_start / t_end [Lmax] (float64, seconds) are host tensors.  heads: the names of the head axis, in order."""
+    aligned_to [B, Lmax] are tensors on the engine's device, Lmax the largest segment count of the batch; n_wins [B]
+    (int64) and t_start / t_end [Lmax] (float64, seconds) are host tensors.  heads: the names of the head axis, in order.
+    The tensors are detached unless profile_audio(..., differentiable=True) had something to differentiate: then scores, weights,
+    local and embed (never aligned_to) share one grad_fn, and a loss built on any of them -- the worst segment's local score,
+    res.local[..., 0].masked_fill(pad, inf).amin(1), or the distance between two clips' embed -- backpropagates to the samples.
+    Rows l >= n_wins[b] take no part: whatever cotangent reaches them is dropped."""
     __slots__ = ('scores', 'weights', 'local', 'embed', 'n_wins', 't_start', 't_end', 'aligned_to', 'heads')
 
     def __init__(self, **kw):
@@ -399,6 +411,77 @@ class _AudioFunctionDE(torch.autograd.Function):
 
 def _score_audio_de(eng, y_deg, y_ref, n_deg, n_ref, sr, plan):
     return eng.forward_audio(torch.cat([_pack_clips(y_deg, n_deg), _pack_clips(y_ref, n_ref)]), n_deg, n_ref, sr, plan)
+
+
+def _check_audio_grad(model, sr):
+    """What forward_audio and profile_audio refuse when a gradient with respect to the audio is asked for, before any GPU work: an
+    engine precision without a gradient (that of the engine, or the one it would be built with) and a checkpoint that resamples."""
+    from .engine import DEFAULT_PRECISION
+    from .input_grad import check_precision
+    check_precision(model._engine.precision if model._engine is not None
+                    else os.environ.get('NISQA_HIP_PRECISION') or DEFAULT_PRECISION)
+    ms_sr = model._engine_args.get('ms_sr')
+    if ms_sr is not None and int(ms_sr) != sr:
+        raise NotImplementedError('the gradient with respect to the audio needs sr == ms_sr ({} != {}): the resampler has no '
+                                  'backward; the plain call works'.format(sr, int(ms_sr)))
+
+
+class _ProfileFunction(torch.autograd.Function):
+    """An engine's profile_audio (HipNisqa: one sample tensor; HipNisqaDE: the degraded and the reference one) with its
+    grad_profile_audio as the backward.  The forward is profile_audio's untouched; its SegmentProfile is handed out through ``box``
+    and its scores, weights, local and embed are the outputs.  Only the samples are kept: the backward scatters the four cotangents
+    into the token layout (rows l >= n_wins[b] are dropped, None stays None) and runs ONE recomputation and ONE chain for them."""
+
+    @staticmethod
+    def forward(ctx, eng, lengths, sr, plan, args, box, *ys):
+        ctx.eng, ctx.lengths, ctx.sr, ctx.plan = eng, lengths, sr, plan
+        ctx.save_for_backward(*ys)
+        ctx.set_materialize_grads(False)
+        prof = eng.profile_audio(torch.cat([_pack_clips(y, n) for y, n in zip(ys, lengths)]), *lengths, sr, plan)
+        sp = _segment_profile(prof, plan.n_wins[:len(lengths[0])], args)
+        box.append(sp)
+        return sp.scores, sp.weights, sp.local, sp.embed
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_scores, *d_tokens):
+        ys, lengths, plan = ctx.saved_tensors, ctx.lengths, ctx.plan
+        if d_scores is None and all(d is None for d in d_tokens):
+            return (None,) * (6 + len(ys))
+        tok = _to_token_layout(d_tokens, plan.n_wins[:len(lengths[0])])
+        pcm = torch.cat([_pack_clips(y, n) for y, n in zip(ys, lengths)])
+        if len(ys) == 1:
+            ds = (ctx.eng.grad_profile_audio(pcm, plan, ctx.sr, d_scores, *tok),)
+        else:
+            ds = ctx.eng.grad_profile_audio(pcm, plan, ctx.sr, d_scores, *tok, need=ctx.needs_input_grad[6:])
+        return (None,) * 6 + tuple(_unpack_clips(d, y, n) if d is not None else None for d, y, n in zip(ds, ys, lengths))
+
+
+def _to_token_layout(ds, n_wins):
+    """The adjoint of _segment_profile's cut: tensors [B, Lmax, w] (or None) -> [NP, w] in the token layout of clips of n_wins[b]
+    segments; rows l >= n_wins[b] are dropped whatever they hold, padding rows of the result are zeros.  The indices come from the
+    host: nothing here waits for the device."""
+    from .engine import BatchPlan
+    n = np.asarray(n_wins, np.int64)
+    plan = BatchPlan.from_n_wins(n)
+    valid = np.flatnonzero(np.arange(int(n.max()))[None, :] < n[:, None])                  # into the flattened [B * Lmax]
+    out, idx = [], None
+    for d in ds:
+        if d is not None:
+            idx = idx or [torch.from_numpy(a.astype(np.int64)).to(d.device) for a in (valid, plan.token_index())]
+            d = d.new_zeros((plan.total_tok, d.shape[-1])).index_copy_(0, idx[1], d.reshape(-1, d.shape[-1]).index_select(0, idx[0]))
+        out.append(d)
+    return out
+
+
+def _differentiable_profile(eng, ys, lengths, sr, plan, args):
+    """_ProfileFunction on the sample tensors ys (on the engine's device, float32) -> the SegmentProfile of the plain call whose
+    scores, weights, local and embed carry the function's grad_fn"""
+    box = []
+    out = _ProfileFunction.apply(eng, lengths, sr, plan, args, box, *ys)
+    sp, = box
+    sp.scores, sp.weights, sp.local, sp.embed = out
+    return sp
 
 
 class _SegmentsFunction(torch.autograd.Function):
@@ -540,39 +623,42 @@ class NISQA_DE(nn.Module):
         than ms_max_segments segments (engine.BatchPlan's ValueErrors); a gradient in a fast precision, or while the
         checkpoint's ms_sr differs from sr -- the resampler has no backward -- (NotImplementedError; the plain call still
         works)."""
-        from .engine import DEFAULT_PRECISION
         d2, r2, n_deg, n_ref, sr, plan = self._audio_plan(y_deg, y_ref, sr, lengths_deg, lengths_ref)
-        rate = sr if self._engine_args.get('ms_sr') is None else int(self._engine_args['ms_sr'])
         dev = y_deg.device if y_deg.is_cuda else (y_ref.device if y_ref.is_cuda else None)
         if not (torch.is_grad_enabled() and (y_deg.requires_grad or y_ref.requires_grad)):
             eng = self.engine(dev)
             to = lambda y: y.detach().to(eng.device, dtype=torch.float32)
             return _score_audio_de(eng, to(d2), to(r2), n_deg, n_ref, sr, plan)
-        from .input_grad import check_precision
-        check_precision(self._engine.precision if self._engine is not None
-                        else os.environ.get('NISQA_HIP_PRECISION') or DEFAULT_PRECISION)
-        if rate != sr:
-            raise NotImplementedError('the gradient with respect to the audio needs sr == ms_sr ({} != {}): the resampler has no '
-                                      'backward; the plain call works'.format(sr, rate))
+        _check_audio_grad(self, sr)
         eng = self.engine(dev)
         # the Function sees the samples the kernels read: torch supplies the adjoint of the device / dtype / rank conversion
         to = lambda y: y.to(eng.device, dtype=torch.float32)
         return _AudioFunctionDE.apply(to(d2), to(r2), eng, n_deg, n_ref, sr, plan)
 
-    def profile_audio(self, y_deg, y_ref, sr, lengths_deg=None, lengths_ref=None):
+    def profile_audio(self, y_deg, y_ref, sr, lengths_deg=None, lengths_ref=None, differentiable=False):
         """forward_audio with the score taken apart per segment of the DEGRADED clip: the same arguments, checks and refusals
         (forward_audio's, raised before any GPU work) -> SegmentProfile as _NisqaBase.profile_audio returns it (scores [B, 1]
         forward_audio's, bit for bit; weights, local [B, Lmax, 1]; embed [B, Lmax, 64], the second self-attention's output;
         n_wins [B] of the degraded clips; t_start / t_end [Lmax]) and additionally
           aligned_to [B, Lmax] int64   the reference segment each degraded segment was aligned to with hard alignment
                                        (HipNisqaDE.forward_pcm(..., want_idx=True)); -1 with soft alignment and on padding rows.
-        The result is detached: gradients are out of scope here (use forward_audio for them).  Not a throughput path."""
+        Not a throughput path.  By default the result is detached.  With ``differentiable=True``, gradients enabled and a y_deg or
+        y_ref that requires one, scores, weights, local and embed are the four outputs of ONE autograd function, as
+        _NisqaBase.profile_audio describes, and backward delivers d / d y_deg and d / d y_ref (engine.HipNisqaDE.grad_profile_audio;
+        the refusals, the hard alignment's argmax and the side that requires no gradient are forward_audio's)."""
         d2, r2, n_deg, n_ref, sr, plan = self._audio_plan(y_deg, y_ref, sr, lengths_deg, lengths_ref)
-        eng = self.engine(y_deg.device if y_deg.is_cuda else (y_ref.device if y_ref.is_cuda else None))
-        to = lambda y: y.detach().to(eng.device, dtype=torch.float32)
-        with torch.no_grad():
-            prof = eng.profile_audio(torch.cat([_pack_clips(to(d2), n_deg), _pack_clips(to(r2), n_ref)]), n_deg, n_ref, sr, plan)
-        return _segment_profile(prof, plan.n_wins[:len(n_deg)], dict(self._engine_args, model='NISQA_DE'))
+        dev = y_deg.device if y_deg.is_cuda else (y_ref.device if y_ref.is_cuda else None)
+        args = dict(self._engine_args, model='NISQA_DE')
+        if not (differentiable and torch.is_grad_enabled() and (y_deg.requires_grad or y_ref.requires_grad)):
+            eng = self.engine(dev)
+            to = lambda y: y.detach().to(eng.device, dtype=torch.float32)
+            with torch.no_grad():
+                prof = eng.profile_audio(torch.cat([_pack_clips(to(d2), n_deg), _pack_clips(to(r2), n_ref)]), n_deg, n_ref, sr, plan)
+            return _segment_profile(prof, plan.n_wins[:len(n_deg)], args)
+        _check_audio_grad(self, sr)
+        eng = self.engine(dev)
+        to = lambda y: y.to(eng.device, dtype=torch.float32)
+        return _differentiable_profile(eng, (to(d2), to(r2)), (n_deg, n_ref), sr, plan, args)
 
     def _audio_plan(self, y_deg, y_ref, sr, lengths_deg, lengths_ref):
         """The argument checks of forward_audio and the 2B-clip plan it builds, on the host

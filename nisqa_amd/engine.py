@@ -234,6 +234,16 @@ def check_profile_args(args):
             args.get('pool')))
 
 
+def check_profile_grad_args(args):
+    """The profile is differentiable where its backward can enter the existing chain per token: behind self-attention (PoolAttFF).
+    The StandardCNN + BiLSTM family's pool=avg profile is refused by name -- nisqa_lstm_train_bptt takes ONE pooled gradient per
+    clip, not a dh per step --, and so is what has no profile at all (check_profile_args).  No device is touched here."""
+    check_profile_args(args)
+    if args.get('td') == 'lstm':
+        raise NotImplementedError('the per-segment profile of the StandardCNN + BiLSTM models (pool=avg) has no gradient: the BiLSTM\'s '
+                                  'backward through time takes a pooled gradient, not one per step; the plain profile works')
+
+
 class HipNisqa(object):
     """nisqa.tar / nisqa_mos_only.tar (CNN-SA-AP) on one MI355X."""
 
@@ -650,6 +660,10 @@ class HipNisqa(object):
         is cut from them on the device, grad_segments (a recomputation of the network) gives d / d x, and the
         segment adjoint and the mel backward carry it to the samples.  The segment-fed and the frame-fed CNN give the same bits
         for the same window, so the gradient belongs to the values forward_pcm returned."""
+        return self._audio_bwd(pcm, plan, sr, lambda x: self.grad_segments(x, plan.n_wins, grad_out))
+
+    def _audio_bwd(self, pcm, plan, sr, segments_bwd):
+        """grad_audio's chain around ``segments_bwd``: x [B, L, 1, 48, 15] -> d / d x"""
         from . import input_grad
         input_grad.check_precision(self.precision)
         assert pcm.dtype == torch.float32, 'int16 PCM has no gradient'
@@ -657,9 +671,48 @@ class HipNisqa(object):
         mel_db, floor = self.mel(pcm, plan, sr, clamp=False)
         clip_of_frame = torch.from_numpy(np.repeat(np.arange(plan.n_clips), plan.T)).to(self.device)
         x = self.segments_from_mel(torch.maximum(mel_db, floor[clip_of_frame][:, None]), plan)
-        dx = self.grad_segments(x, plan.n_wins, grad_out)
+        dx = segments_bwd(x)
         del x
         return self.mel_bwd(pcm, plan, sr, self.segments_to_mel_bwd(dx, plan), mel_db, floor)
+
+    # -- the gradient of the per-segment profile (nisqa_pool_profile_bwd) ------------------------------------------
+    def profile_cotangents(self, plan, d_weights, d_local, d_embed):
+        """Cotangents of a PoolProfile in the plan's token layout ([NP, heads], [NP, heads], [NP, 64]; None: zero) -> the same over
+        the plan's valid tokens, clip by clip, float32 on the device: what input_grad.InputGrad takes as ``profile_cot``.  Padding
+        rows are dropped here, whatever they hold."""
+        idx = torch.from_numpy(plan.token_index()).to(self.device)
+        out = []
+        for name, t, width in (('d_weights', d_weights, self.n_heads), ('d_local', d_local, self.n_heads), ('d_embed', d_embed, 64)):
+            if t is not None and (not torch.is_tensor(t) or tuple(t.shape) != (plan.total_tok, width)):
+                raise ValueError('expected {} of shape [{}, {}], got {}'.format(
+                    name, plan.total_tok, width, tuple(t.shape) if torch.is_tensor(t) else type(t).__name__))
+            out.append(None if t is None else t.detach().to(self.device, dtype=torch.float32)[idx].contiguous())
+        return tuple(out)
+
+    def grad_profile_segments(self, x, n_wins, d_scores=None, d_weights=None, d_local=None, d_embed=None):
+        """The backward of profile_segments in precision 'f32' / 'bf16x6', CNN-SA-AP models: d_scores [B, heads] and d_weights,
+        d_local [NP, heads], d_embed [NP, 64] in the token layout of BatchPlan.from_n_wins(n_wins) (padding rows are ignored); None
+        means zero -> d (sum d_scores * scores + sum d_weights * weights + sum d_local * local + sum d_embed * embed) / d x, float32
+        [B, L, 1, 48, 15], rows l >= n_wins[b] exact zeros.  grad_segments with one more launch: the token-level cotangents become
+        d / d (the rows the pooling read) in nisqa_pool_profile_bwd, are added to the pooling heads' backward of d_scores (which
+        is skipped when d_scores is None), and ONE walk back through self-attention and the CNN serves all four.  The BiLSTM
+        family's pool=avg profile has no backward (its BPTT entry takes a pooled gradient, not one per step)."""
+        from . import input_grad
+        check_profile_grad_args(self.args)
+        input_grad.check_precision(self.precision)
+        n = check_segments(x, n_wins, 1)
+        cot = self.profile_cotangents(BatchPlan.from_n_wins(n), d_weights, d_local, d_embed)
+        if self._input_grad is None:
+            self._input_grad = input_grad.InputGrad(self, self._state_dict)
+        return self._input_grad(x, n_wins, d_scores, profile_cot=cot)
+
+    def grad_profile_audio(self, pcm, plan, sr, d_scores=None, d_weights=None, d_local=None, d_embed=None):
+        """The backward of profile_pcm, built as grad_audio is on grad_segments: pcm float32 [plan.total_samples] at the rate the
+        spectrogram is computed at, the cotangents of grad_profile_segments in the plan's token layout
+        -> d / d pcm, float32 [plan.total_samples]."""
+        check_profile_grad_args(self.args)
+        return self._audio_bwd(pcm, plan, sr,
+                               lambda x: self.grad_profile_segments(x, plan.n_wins, d_scores, d_weights, d_local, d_embed))
 
     # -- nisqa_tts.tar stages ------------------------------------------------------------------------
     def cnn_std(self, mel_tm, clip_floor, plan):
@@ -740,17 +793,21 @@ class HipNisqa(object):
         check_profile_args(self.args)
         mode, ld = (0, 64) if self.arch == 0 else (1, 256)
         assert x.dtype == torch.float32 and x.is_cuda and x.is_contiguous() and tuple(x.shape) == (plan.total_tok, ld)
-        if self._profile_w is None:
-            heads = ['pool_layers.%d.model.' % h for h in range(5)] if self.dim else ['pool.model.']
-            blob = _w.pack_pool_profile(self._state_dict, heads) if mode == 0 else _w.pack_pool_profile_avg(self._state_dict)
-            self._profile_w = torch.from_numpy(blob).to(self.device)
         d = plan.to(self.device)
         weights = torch.empty((plan.total_tok, self.n_heads), dtype=torch.float32, device=self.device)
         local = torch.empty((plan.total_tok, self.n_heads), dtype=torch.float32, device=self.device)
         _lib.check(self.lib.nisqa_pool_profile(_ptr(x), ld, _ptr(d['tok_off']), _ptr(d['n_wins']), plan.n_clips, plan.total_tok,
-                                               self.n_heads, mode, _ptr(self._profile_w), _ptr(weights), _ptr(local), self._stream()),
-                   'nisqa_pool_profile')
+                                               self.n_heads, mode, _ptr(self.profile_weights()), _ptr(weights), _ptr(local),
+                                               self._stream()), 'nisqa_pool_profile')
         return weights, local
+
+    def profile_weights(self):
+        """The natural-order fp32 blob nisqa_pool_profile and nisqa_pool_profile_bwd read, packed from the state_dict on first use"""
+        if self._profile_w is None:
+            heads = ['pool_layers.%d.model.' % h for h in range(5)] if self.dim else ['pool.model.']
+            blob = _w.pack_pool_profile(self._state_dict, heads) if self.arch == 0 else _w.pack_pool_profile_avg(self._state_dict)
+            self._profile_w = torch.from_numpy(blob).to(self.device)
+        return self._profile_w
 
     def _profile(self, scores, x, plan, aligned_to=None):
         weights, local = self.pool_profile(x, plan)
@@ -983,18 +1040,39 @@ class HipNisqaDE(object):
         under its own plan.  Hard alignment: the argmax carries no gradient, and the backward takes the recomputation's own
         argmax (InputGradDE.last_idx), which at a near-tie of two scores may differ from the choice of the fused inference chain
         that produced the score (DESIGN.md 4.8 "argmax deviation")."""
+        return self._audio_bwd(pcm, plan, sr, grad_out, need, None)
+
+    def _deg_cotangents(self, n_deg, d_weights, d_local, d_embed):
+        """HipNisqa.profile_cotangents over the degraded clips' tokens (the layout of BatchPlan.from_n_wins(n_deg))"""
+        return self.base.profile_cotangents(BatchPlan.from_n_wins(n_deg), d_weights, d_local, d_embed)
+
+    def grad_profile_segments(self, x, n_wins, d_scores=None, d_weights=None, d_local=None, d_embed=None):
+        """HipNisqa.grad_profile_segments for x [B, L, 2, 48, 15], n_wins [B, 2]: d_scores [B, 1]; d_weights, d_local [NP, 1] and
+        d_embed [NP, 64] over the DEGRADED clips' tokens, in the layout of BatchPlan.from_n_wins(n_wins[:, 0]) -> d / d x, float32
+        in x's shape (both channels: the reference clip's segments reach the profile through the alignment)."""
+        n = check_segments(x, n_wins, 2)
+        return self._grad()(x, n_wins, d_scores, profile_cot=self._deg_cotangents(n[:, 0], d_weights, d_local, d_embed))
+
+    def grad_profile_audio(self, pcm, plan, sr, d_scores=None, d_weights=None, d_local=None, d_embed=None, need=(True, True)):
+        """The backward of profile_pcm, built as grad_audio is: the cotangents of grad_profile_segments over the degraded clips'
+        tokens -> (d_deg, d_ref) as grad_audio returns them, None for a side ``need`` does not name."""
+        self._grad()                                                         # the precision is refused before anything is copied
+        cot = self._deg_cotangents(plan.n_wins[:plan.n_clips // 2], d_weights, d_local, d_embed)
+        return self._audio_bwd(pcm, plan, sr, d_scores, need, cot)
+
+    def _audio_bwd(self, pcm, plan, sr, grad_out, need, cot):
+        """grad_audio's chain; cot: token-level cotangents for InputGradDE.packed (beside them grad_out may be None)"""
         ig = self._grad()
         need = (bool(need[0]), bool(need[1]))
         B, b = plan.n_clips // 2, self.base
         assert plan.n_clips == 2 * B and any(need) and pcm.dtype == torch.float32, 'int16 PCM has no gradient'
-        from .input_grad import _check_grad_out
-        _check_grad_out(grad_out, B, 1)
+        from .input_grad import _grad_out
+        g = _grad_out(grad_out, B, 1, self.device, cot)
         pcm = pcm.detach().contiguous()
-        g = grad_out.detach().to(self.device, dtype=torch.float32).contiguous()
         mel_db, floor = b.mel(pcm, plan, sr, clamp=False)
         x2 = b.segments_from_mel_db(mel_db, floor, plan)
         n = np.stack([plan.n_wins[:B], plan.n_wins[B:]], 1).astype(np.int64)
-        dx2 = ig.packed(x2, n, g, need)
+        dx2 = ig.packed(x2, n, g, need, cot)
         del x2
         if all(need):
             d = b.mel_bwd(pcm, plan, sr, b.segments_to_mel_bwd(dx2, plan), mel_db, floor)

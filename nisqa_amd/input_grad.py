@@ -14,7 +14,8 @@ and walks back through it:
              step (csrc/train_conv.hip: forward and input gradient of conv2..6, exact fp32 for precision 'f32', three bf16 terms
              and six products for 'bf16x6');
   attention  _AttTrainer._sa_fwd / _sa_bwd without dropout masks: the eval-mode function;
-  heads      attention pooling forward and the input half of its backward, fed with the caller's grad_out.
+  heads      attention pooling forward and the input half of its backward, fed with the caller's grad_out; and / or the backward
+             of the score's per-segment profile (nisqa_pool_profile_bwd), fed with cotangents per token.
 Parameters get no gradient here (that is the trainers' business): the weight-gradient GEMMs and column sums of the borrowed
 operators are not run.
 
@@ -123,6 +124,14 @@ def _check_grad_out(grad_out, B, H):
             B, H, tuple(grad_out.shape) if torch.is_tensor(grad_out) else type(grad_out).__name__))
 
 
+def _grad_out(grad_out, B, H, device, profile_cot=None):
+    """grad_out checked and as float32 on the device; None is accepted (and returned) only beside a token-level cotangent"""
+    if grad_out is None and profile_cot is not None and any(t is not None for t in profile_cot):
+        return None
+    _check_grad_out(grad_out, B, H)
+    return grad_out.detach().to(device, dtype=torch.float32).contiguous()
+
+
 class InputGrad(_EvalCNN, _AttTrainer):
     FEAT_W = 'time_dependency.model.linear.weight'
 
@@ -131,6 +140,7 @@ class InputGrad(_EvalCNN, _AttTrainer):
             raise NotImplementedError('the gradient with respect to x is built for the CNN-SA-AP models (NISQA, NISQA_DIM)')
         self.precision = check_precision(eng.precision)
         self.eng, self.lib, self.device, self.args = eng, eng.lib, eng.device, eng.args
+        self._pool_eng = eng                                # the HipNisqa that owns the pooling heads' profile blob
         self.n_layers = eng.n_layers
         self.heads = ['pool_layers.%d.model.' % h for h in range(5)] if eng.dim else ['pool.model.']
         self.p_cnn = self.p_td = 0.0
@@ -206,18 +216,42 @@ class InputGrad(_EvalCNN, _AttTrainer):
             self._ew(4, dx, aux=self._linear_bwd(du, x, hp + 'linear1.weight', hp + 'linear1.bias', S, 64, 128))
         return dx
 
-    def __call__(self, x, n_wins, grad_out):
+    def _profile_bwd(self, cs, x, cot):
+        """The backward of the per-segment profile on x [S][64]: cot = (d_weights [S][heads], d_local [S][heads],
+        d_embed [S][64]) in the clip set's token layout, float32 on the device, None for zero -> d (sum d_weights * weights +
+        sum d_local * local + sum d_embed * x) / d x [S][64]: ONE nisqa_pool_profile_bwd launch, which recomputes the logits."""
+        H = len(self.heads)
+        ptrs = []
+        for t, width in zip(cot, (H, H, 64)):
+            assert t is None or (t.dtype == torch.float32 and t.device == self.device and t.is_contiguous()
+                                 and tuple(t.shape) == (cs.S, width)), 'a profile cotangent is [S, heads] / [S, 64] float32'
+            ptrs.append(_ptr(t) if t is not None else None)
+        dx = self._new(cs.S, 64)                            # every row is written: no clearing
+        self._ck(self.lib.nisqa_pool_profile_bwd(_ptr(x), 64, _ptr(cs.seg_off), _ptr(cs.pool_len), cs.B, cs.S, H, 0,
+                                                 _ptr(self._pool_eng.profile_weights()), *ptrs, _ptr(dx), self._st()),
+                 'nisqa_pool_profile_bwd')
+        return dx
+
+    def _seed(self, cs, x, g, cot):
+        """What the walk back starts from, d / d x [S][64]: _heads_bwd of the score cotangent g [B][heads], _profile_bwd of the
+        token-level cotangents cot, or their sum; either may be None (not both).  Without cot: the launches of _heads_bwd alone."""
+        if cot is None or all(t is None for t in cot):
+            return self._heads_bwd(cs, x, g)
+        dx = self._profile_bwd(cs, x, cot)
+        return dx if g is None else self._ew(4, dx, aux=self._heads_bwd(cs, x, g))
+
+    def __call__(self, x, n_wins, grad_out, profile_cot=None):
         """x [B, L, 1, 48, 15], n_wins [B], grad_out [B, heads] -> d (sum grad_out * model(x, n_wins)) / d x, float32 on the
-        engine's device, in x's shape."""
+        engine's device, in x's shape.  profile_cot = (d_weights, d_local, d_embed), see _profile_bwd: cotangents of the score's
+        per-segment profile over the S = sum n_wins valid tokens, clip by clip; with them grad_out may be None."""
         n = check_segments(x, n_wins, 1)
         B, L, H = x.shape[0], x.shape[1], len(self.heads)
-        _check_grad_out(grad_out, B, H)
+        g = _grad_out(grad_out, B, H, self.device, profile_cot)
         x = x.detach().to(self.device, dtype=torch.float32).contiguous()
-        g = grad_out.detach().to(self.device, dtype=torch.float32).contiguous()
         cs = self._tables(np.asarray(n, dtype=np.int64))
         recs, feat = self._cnn_fwd_eval(x, cs.seg_off, cs.B, cs.S)
         xs, rec = self._sa_fwd(cs, feat, 384, 'time_dependency.model.', self.n_layers, None, 'td%d_%s', 0.0)
-        dfeat = self._sa_bwd(rec, self._heads_bwd(cs, xs, g))
+        dfeat = self._sa_bwd(rec, self._seed(cs, xs, g, profile_cot))
         del rec, xs, feat
         return self._cnn_bwd_eval(recs, dfeat, cs.seg_off, B, cs.S, L)
 
@@ -238,7 +272,7 @@ class InputGradDE(InputGrad):
 
     def __init__(self, eng, state_dict):
         InputGrad.__init__(self, eng.base, state_dict)          # eng: engine.HipNisqaDE; its base runs the CNN-SA-AP half
-        self.eng, self.args = eng, eng.args
+        self.eng, self.args = eng, eng.args                     # (_pool_eng stays eng.base: pool.model is the single-ended engine's)
         self.n_layers2 = eng.n_layers2
         self.align, self.soft, self.fuse, self.fuse_width = eng.align, eng.apply, eng.fuse, eng.fuse_width
         w2 = state_dict[_TD2 + 'linear.weight']
@@ -263,26 +297,28 @@ class InputGradDE(InputGrad):
             self._tab_key, self._tab = key, (host, buf, tv, _ClipSet(L12, tv, tiles_a, 'a_'), _ClipSet(Lx, tv, tiles_d))
         return self._tab[2:]
 
-    def __call__(self, x, n_wins, grad_out):
+    def __call__(self, x, n_wins, grad_out, profile_cot=None):
         """x [B, L, 2, 48, 15], n_wins [B, 2], grad_out [B, 1] -> d (sum grad_out * model(x, n_wins)) / d x, float32 on the
         engine's device, in x's shape; rows l >= n_wins[b, c] of channel c exactly zero.  The channels are copied into the
-        2B-clip layout, ``packed`` does the work, and the two halves of its result go side by side again."""
+        2B-clip layout, ``packed`` does the work, and the two halves of its result go side by side again.  profile_cot: see
+        ``packed``."""
         n = check_segments(x, n_wins, 2)
         B = x.shape[0]
-        _check_grad_out(grad_out, B, 1)
+        g = _grad_out(grad_out, B, 1, self.device, profile_cot)
         x = x.detach().to(self.device, dtype=torch.float32)
         x2 = torch.cat([x[:, :, 0:1], x[:, :, 1:2]], 0).contiguous()             # [2B, L, 1, 48, 15], degraded clips first
-        g = grad_out.detach().to(self.device, dtype=torch.float32).contiguous()
-        dx = self.packed(x2, np.asarray(n, dtype=np.int64), g)
+        dx = self.packed(x2, np.asarray(n, dtype=np.int64), g, profile_cot=profile_cot)
         return torch.cat([dx[:B], dx[B:]], 2)
 
-    def packed(self, x2, n, g, need=(True, True)):
+    def packed(self, x2, n, g, need=(True, True), profile_cot=None):
         """The same in the 2B-clip layout, for callers that hold it (engine.HipNisqaDE.grad_audio): x2 [2B, L, 1, 48, 15] float32,
         contiguous, on the engine's device, the B degraded clips first, then their B reference clips; n int64 [B, 2] (checked by
         the caller); g [B, 1] float32 on the device -> dx2 in x2's layout.  need = (degraded, reference): the CNN backward runs
         over the segments of the sides named -- the degraded segments are the leading Sx rows of every kept activation, the
         reference segments the rest, so one side is a view -- and the half of dx2 of a side not named is exact zeros.  The
-        recomputation and the self-attention backward over both sides stay whole: either side's gradient needs them."""
+        recomputation and the self-attention backward over both sides stay whole: either side's gradient needs them.
+        profile_cot: InputGrad._profile_bwd's cotangents over the Sx valid tokens of the degraded clips (the second
+        self-attention's rows); beside them g may be None."""
         B, L, F = n.shape[0], x2.shape[1], self.fuse_width
         assert tuple(x2.shape) == (2 * B, L, 1, 48, 15) and x2.dtype == torch.float32 and x2.is_contiguous() and any(need)
         tv, cs_all, cs_deg = self._tables(n)
@@ -306,7 +342,7 @@ class InputGradDE(InputGrad):
             self.last_idx = idx
         xs, rec2 = self._sa_fwd(cs_deg, fused, F, _TD2, self.n_layers2, None, 'td2_%d_%s', 0.0)
         # backward, input halves only
-        dfused = self._sa_bwd(rec2, self._heads_bwd(cs_deg, xs, g))              # [Sx][F]
+        dfused = self._sa_bwd(rec2, self._seed(cs_deg, xs, g, profile_cot))      # [Sx][F]
         del rec2, xs, fused
         dx1 = self._new(cs_all.S, 64)                                            # every row is written: no clearing
         if self.soft:

@@ -95,6 +95,7 @@ SYMBOLS = {
     'nisqa_pool_final': (ctypes.c_int, [c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p]),
     'nisqa_pool_att': (ctypes.c_int, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p]),
     'nisqa_pool_profile': (ctypes.c_int, [c_p, c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p]),
+    'nisqa_pool_profile_bwd': (ctypes.c_int, [c_p, c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_p]),
     'nisqa_workspace_bytes': (ctypes.c_size_t, [c_i32, c_i32, c_i32]),
     'nisqa_predict_batch': (ctypes.c_int, [c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, ctypes.POINTER(MelCfg),
                                            ctypes.POINTER(ModelDev), c_p, ctypes.c_size_t, c_p, c_p]),
