@@ -162,6 +162,41 @@ NQ_DEV float wave_max(float v) {
     return v;
 }
 
+typedef int i32x4 __attribute__((ext_vector_type(4)));
+// adaptive_max_pool2d's window of output cell i: the inputs [lo, hi)
+NQ_DEV int win_lo(int i, int n_in, int n_out) { return (i * n_in) / n_out; }
+NQ_DEV int win_hi(int i, int n_in, int n_out) { return ((i + 1) * n_in + n_out - 1) / n_out; }
+
+// BatchNorm (batch statistics) backward, the constants of four consecutive channels ch .. ch + 3 of c:
+//   dz = g (dyb - m1 - xhat m2),  xhat = (z - mean) rstd,  g = gamma rstd,  m1 = mean(dyb),  m2 = mean(dyb xhat)
+// from mean_rstd [2c] and the float64 sums2 [2c] = sum dyb, sum dyb z over the 1 / inv rows; b = beta - mean g is the shift of
+// the forward's y = z g + b (the ReLU gate).  (bn_act_pool_bwd_dense_kernel and bn_bwd2_kernel of train.hip compute the same
+// values with their own order of loads: through this helper their instruction streams change.)
+struct bn_bwd4 { f32x4 mean, rstd, g, b, m1, m2; };
+NQ_DEV bn_bwd4 bn_bwd_channels4(const float* mean_rstd, const float* gamma, const float* beta, const double* sums2, int c, int ch,
+                                double inv) {
+    bn_bwd4 k;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        k.mean[e] = mean_rstd[ch + e];
+        k.rstd[e] = mean_rstd[c + ch + e];
+        k.g[e] = gamma[ch + e] * k.rstd[e];
+        k.b[e] = beta[ch + e] - k.mean[e] * k.g[e];
+        k.m1[e] = (float)(sums2[ch + e] * inv);
+        k.m2[e] = (float)((double)k.rstd[e] * (sums2[c + ch + e] - (double)k.mean[e] * sums2[ch + e]) * inv);
+    }
+    return k;
+}
+// the BatchNorm parameter gradients from the same sums: block 0 writes them, one thread per channel
+NQ_DEV void bn_bwd_param_grads(const float* mean_rstd, const double* sums2, int c, float* dgamma, float* dbeta) {
+    if (blockIdx.x == 0 && (int)threadIdx.x < c) {
+        const int ch = threadIdx.x;
+        const double mean = mean_rstd[ch], rstd = mean_rstd[c + ch];
+        dbeta[ch] = (float)sums2[ch];
+        dgamma[ch] = (float)(rstd * (sums2[c + ch] - mean * sums2[ch]));
+    }
+}
+
 // The two waves that share a SIMD start together and take the same time per work item, so without help
 // they stay phase-locked: both in their VALU/LDS/epilogue phases at once (matrix pipe idle), both in their
 // MFMA phases at once (pipe contended).  Delaying the odd hardware wave slots of the FIRST round of

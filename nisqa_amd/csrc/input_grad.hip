@@ -13,12 +13,6 @@
 #include "../../include/nisqa_hip.h"
 #include "../../include/nisqa_train.h"
 
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-
-// adaptive_max_pool2d's window of output i: [lo, hi)
-NQ_DEV int win_lo(int i, int n_in, int n_out) { return (i * n_in) / n_out; }
-NQ_DEV int win_hi(int i, int n_in, int n_out) { return ((i + 1) * n_in + n_out - 1) / n_out; }
-
 // BatchNorm on the running statistics as one multiply-add per element: y = z * scale + shift, scale = gamma / sqrt(var + eps),
 // shift = beta - mean * scale, for four consecutive channels.  Forward and backward derive the ReLU gate from this one
 // expression (bn_apply), so the two agree on every element's side of zero.

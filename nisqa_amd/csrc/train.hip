@@ -772,11 +772,6 @@ extern "C" int nisqa_conv1_wgrad(const float* mel_tm, const int32_t* frame_off, 
 // ---------------------------------------------------------------------------------------------------------
 // helpers shared by the layer-1 kernels and the BatchNorm / pooling kernels further down
 // ---------------------------------------------------------------------------------------------------------
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-// adaptive max pool: the input window of output cell i
-NQ_DEV int win_lo(int i, int n_in, int n_out) { return (i * n_in) / n_out; }
-NQ_DEV int win_hi(int i, int n_in, int n_out) { return ((i + 1) * n_in + n_out - 1) / n_out; }
-
 // BatchNorm batch statistics of channel ch from the float64 column sums (sum z, sum z^2 over m_rows rows)
 NQ_DEV void bn_stats(const double* __restrict__ sums, int c, int ch, double m_rows, float& mean, float& rstd, double& var) {
     const double mu = sums[ch] / m_rows;
@@ -1526,12 +1521,7 @@ __global__ __launch_bounds__(256) void bn_act_pool_bwd_dense_kernel(
     const int h = H ? H : h_, w = H ? W : w_, c = H ? C : c_, ho = H ? HO : ho_, wo = H ? WO : wo_;
     const int c4 = c / 4;
     const double inv = 1.0 / ((double)(total4 / c4));
-    if (blockIdx.x == 0 && (int)threadIdx.x < c) {
-        const int ch = threadIdx.x;
-        const double mean = mean_rstd[ch], rstd = mean_rstd[c + ch];
-        dbeta[ch] = (float)sums2[ch];
-        dgamma[ch] = (float)(rstd * (sums2[c + ch] - mean * sums2[ch]));
-    }
+    bn_bwd_param_grads(mean_rstd, sums2, c, dgamma, dbeta);
     constexpr bool INV = H != 0 && 256 % ((C ? C : 4) / 4) == 0;        // see bn_act_pool_fwd_kernel
     f32x4 g, bsh, mean, rstd, m1, m2;
     auto channel_constants = [&](int ch) {                  // eight float64 operations per channel: once per thread where INV
@@ -1622,12 +1612,7 @@ __global__ __launch_bounds__(256) void bn_bwd2_kernel(float* __restrict__ d, con
                                                       const float* __restrict__ gamma, int64_t rows, int c,
                                                       float* __restrict__ dgamma, float* __restrict__ dbeta,
                                                       double* __restrict__ sum_dz) {
-    if (blockIdx.x == 0 && (int)threadIdx.x < c) {
-        const int ch = threadIdx.x;
-        const double mean = mean_rstd[ch], rstd = mean_rstd[c + ch];
-        dbeta[ch] = (float)sums2[ch];
-        dgamma[ch] = (float)(rstd * (sums2[c + ch] - mean * sums2[ch]));
-    }
+    bn_bwd_param_grads(mean_rstd, sums2, c, dgamma, dbeta);
     const int c4 = c / 4;
     const int64_t total4 = rows * c4;
     const double inv = 1.0 / (double)rows;

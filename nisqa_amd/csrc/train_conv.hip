@@ -693,6 +693,11 @@ struct segwgrad_cfg {
     static constexpr int NVX = (FX + 511) / 512, NVZ = (FZ + 511) / 512;
     static_assert(LDS <= 160 * 1024, "LDS");
     static_assert(BUF % 16 == 0 && CI % 16 == 0 && CO % 32 == 0 && MT % MSPLIT == 0, "shapes");
+    // for segw_stage: rows in bytes; four channels of an x / a dz pixel are split into the TERMS planes
+    static constexpr bool F32 = false;
+    static constexpr int PAD = PADW;
+    NQ_DEV void store_x(unsigned a, f32x4 v) { sc_store_terms4<TERMS>(a, PLX, v); }
+    NQ_DEV void store_z(unsigned a, f32x4 v) { sc_store_terms4<TERMS>(a, PLZ, v); }
 };
 
 // K loop of a wave: its N tiles are wq, wq + NSPLIT, ...; noff[j] = byte offset of tile j (tap, channels) in an x plane
@@ -738,22 +743,131 @@ struct segw_bn {
     const float* z; const float* dy; const int32_t* arg; const float* drop; const float* mean_rstd; const float* gamma;
     const float* beta; const double* sums2; float* dz_out; float* dgamma; float* dbeta;
 };
-NQ_DEV int sc_win_lo(int i, int n_in, int n_out) { return (i * n_in) / n_out; }
-NQ_DEV int sc_win_hi(int i, int n_in, int n_out) { return ((i + 1) * n_in + n_out - 1) / n_out; }
-typedef int sc_i32x4 __attribute__((ext_vector_type(4)));
+
+// A group on its way from HBM into LDS, for both weight-gradient kernels: the registers it travels in between its request (the
+// global loads, issued ahead of the K loop of the group before it) and its deposit (the LDS stores behind that K loop), with
+// the BatchNorm backward of segw_bn applied on the way where PH > 0.  C is the kernel's config: the group's sizes (PXI, PXZ, FX,
+// FZ, NVX, NVZ), the planes' geometry (PXX, XPW, PAD, RSX, RSZ, ZB; rows in bytes of 16-bit elements or, C::F32, in words)
+// and how four channels are stored at an address: C::store_x, C::store_z.  Every array is indexed by fully unrolled loops only.
+// What looks arbitrary here holds the kernels' instruction streams where they were: the order of the members (hipcc gives the
+// loop-carried registers their places in that order), and the two address forms written out in deposit() rather than handed
+// to C (a function around them is simplified on its own before it is inlined, and the address arithmetic comes out differently).
+template <typename C, int CI, int CO, int H, int W, int WO, int SEGS, int PH, int PW>
+struct segw_stage {
+    static constexpr bool BN = PH > 0;
+    static constexpr bool IDENT = PH == H && PW == WO;
+    static_assert(!BN || (H % PH == 0 && 512 % (CO / 4) == 0), "pooling rows are disjoint; a thread keeps its four channels");
+    const float* const x;
+    const float* const dz;
+    const segw_bn& bn;
+    const int n_segments, n_groups;
+    bn_bwd4 k;                                               // BN: this thread's four channels
+    // BN: the arg-max pixels and pooled gradients of the <= 2 windows that contain the element's pixel, and the Dropout2d
+    // multipliers of its (segment, channels)
+    i32x4 va1[(BN && !IDENT) ? C::NVZ : 1], va0[(BN && !IDENT) ? C::NVZ : 1];
+    f32x4 vdr[BN ? C::NVZ : 1], vd1[(BN && !IDENT) ? C::NVZ : 1], vd0[BN ? C::NVZ : 1];
+    f32x4 vz[C::NVZ], vx[C::NVX];                            // a group's dz (BN: z) and x
+
+    __device__ __forceinline__ segw_stage(const float* x_, const float* dz_, const segw_bn& bn_, int n_segments_, int tid0)
+        : x(x_), dz(dz_), bn(bn_), n_segments(n_segments_), n_groups((n_segments_ + SEGS - 1) / SEGS) {
+        if (BN) {
+            // this thread's four channels are the same in every element it stages (512 * 4 % CO == 0): their constants once
+            k = bn_bwd_channels4(bn.mean_rstd, bn.gamma, bn.beta, bn.sums2, CO, (4 * tid0) % CO, 1.0 / ((double)n_segments * C::PXZ));
+            bn_bwd_param_grads(bn.mean_rstd, bn.sums2, CO, bn.dgamma, bn.dbeta);   // (what the dense kernel's block 0 wrote)
+        }
+    }
+    __device__ __forceinline__ void request(int grp, int tid) {
+        const int seg0 = grp * SEGS;
+        const int nseg = grp < n_groups ? min(SEGS, n_segments - seg0) : 0;
+        const f32x4* gx = (const f32x4*)(x + (size_t)seg0 * C::PXI * CI);
+        const f32x4* gz = (const f32x4*)((BN ? bn.z : dz) + (size_t)seg0 * C::PXZ * CO);
+#pragma unroll
+        for (int j = 0; j < C::NVX; ++j) {
+            const int i = tid + 512 * j;
+            vx[j] = i < nseg * C::PXI * CI / 4 ? gx[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+        }
+#pragma unroll
+        for (int j = 0; j < C::NVZ; ++j) {
+            const int i = tid + 512 * j;
+            const bool ok = i < nseg * C::PXZ * CO / 4;
+            vz[j] = ok ? gz[i] : f32x4{0.f, 0.f, 0.f, 0.f};
+            if (BN) {
+                const int pix = (4 * i) / CO, c = (4 * i) % CO;
+                const int sg = pix / C::PXZ, p = pix - sg * C::PXZ;
+                vdr[j] = (ok && bn.drop) ? *(const f32x4*)(bn.drop + (size_t)(seg0 + sg) * CO + c) : f32x4{1.f, 1.f, 1.f, 1.f};
+                if (IDENT) {
+                    vd0[j] = ok ? *(const f32x4*)(bn.dy + ((size_t)(seg0 + sg) * C::PXZ + p) * CO + c) : f32x4{0.f, 0.f, 0.f, 0.f};
+                } else {
+                    const int yy = p / WO, xx = p - yy * WO;
+                    const int oy = yy / (H / PH);
+                    int oa = (xx * PW) / WO;                    // the window whose floor bound is at or below xx ...
+                    if (oa > 0 && win_hi(oa - 1, WO, PW) > xx) --oa;         // ... or the one before it when that still covers xx
+                    const int ob = oa + 1;
+                    const bool has_b = ob < PW && win_lo(ob, WO, PW) <= xx;
+                    const size_t o0 = ((size_t)(seg0 + sg) * (PH * PW) + oy * PW + oa) * CO + c;
+                    const size_t o1 = ((size_t)(seg0 + sg) * (PH * PW) + oy * PW + ob) * CO + c;
+                    vd0[j] = ok ? *(const f32x4*)(bn.dy + o0) : f32x4{0.f, 0.f, 0.f, 0.f};
+                    va0[j] = ok ? *(const i32x4*)(bn.arg + o0) : i32x4{-1, -1, -1, -1};
+                    vd1[j] = (ok && has_b) ? *(const f32x4*)(bn.dy + o1) : f32x4{0.f, 0.f, 0.f, 0.f};
+                    va1[j] = (ok && has_b) ? *(const i32x4*)(bn.arg + o1) : i32x4{-1, -1, -1, -1};
+                }
+            }
+        }
+    }
+    __device__ __forceinline__ void deposit(unsigned buf, int tid, int grp) {    // store the requested group into buffer `buf`
+#pragma unroll
+        for (int j = 0; j < C::NVX; ++j) {
+            const int i = tid + 512 * j;
+            if (C::FX % 512 == 0 || i < C::FX) {
+                const int pix = (4 * i) / CI, c = (4 * i) % CI;
+                const int sg = pix / C::PXI, p = pix - sg * C::PXI, y = p / W, xx = p - y * W;
+                const int row = sg * C::PXX + (y + 1) * C::XPW + xx + C::PAD;      // inside the zero border
+                C::store_x(C::F32 ? buf + 4u * (unsigned)(row * C::RSX + c) : buf + (unsigned)(row * C::RSX) + 2 * c, vx[j]);
+            }
+        }
+        const int seg0 = grp * SEGS;
+        const int nseg_d = grp < n_groups ? min(SEGS, n_segments - seg0) : 0;
+#pragma unroll
+        for (int j = 0; j < C::NVZ; ++j) {
+            const int i = tid + 512 * j;
+            if (C::FZ % 512 == 0 || i < C::FZ) {
+                const int pix = (4 * i) / CO, c = (4 * i) % CO;
+                f32x4 dzv = vz[j];
+                if (BN) {
+                    const bool ok = i < nseg_d * C::PXZ * CO / 4;
+                    const int sg = pix / C::PXZ, p = pix - sg * C::PXZ;
+                    const f32x4 zi = vz[j];
+                    f32x4 a4;
+                    if (IDENT) a4 = vd0[j];
+                    else {
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) a4[e] = (va0[j][e] == p ? vd0[j][e] : 0.f) + (va1[j][e] == p ? vd1[j][e] : 0.f);
+                    }
+                    a4 *= vdr[j];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        float zv = zi[e];
+                        asm volatile("" : "+v"(zv));              // scalar gates: packed, hipcc emits the op_sel form of DESIGN.md 7.1
+                        const float a_ = fmaf(zv, k.g[e], k.b[e]) > 0.f ? a4[e] : 0.f;
+                        const float xh = (zv - k.mean[e]) * k.rstd[e];
+                        dzv[e] = ok ? k.g[e] * (a_ - k.m1[e] - xh * k.m2[e]) : 0.f;
+                    }
+                    if (ok) *(f32x4*)(bn.dz_out + (size_t)seg0 * C::PXZ * CO + (size_t)4 * i) = dzv;
+                }
+                C::store_z(C::F32 ? buf + C::ZB + 4u * (unsigned)(pix * C::RSZ + c) : buf + C::ZB + (unsigned)(pix * C::RSZ) + 2 * c, dzv);
+            }
+        }
+    }
+};
 
 template <int CI, int CO, int H, int W, int WO, int PADW, int SEGS, int MSPLIT, int PH, int PW, int TERMS = 2>
 __global__ __launch_bounds__(512, 1) void segwgrad_bf16_kernel(const float* __restrict__ x, const float* __restrict__ dz,
                                                                float* __restrict__ dw, int n_segments, segw_bn bn) {
     typedef segwgrad_cfg<CI, CO, H, W, WO, PADW, SEGS, MSPLIT, TERMS> C;
-    constexpr bool BN = PH > 0;
-    constexpr bool IDENT = PH == H && PW == WO;
-    static_assert(!BN || (H % PH == 0 && 512 % (CO / 4) == 0), "pooling rows are disjoint; a thread keeps its four channels");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid0 = threadIdx.x, lane0 = tid0 & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
     const int wq = wave / MSPLIT, wm = wave % MSPLIT;           // this wave's N residue and M part
-    const int n_groups = (n_segments + SEGS - 1) / SEGS;
     // zero both buffers once: the borders of the x planes and the zero rows of dz stay zero
     for (unsigned a = 16u * tid0; a < C::LDS; a += 16u * 512u) *(f32x4*)(smem + a) = f32x4{0.f, 0.f, 0.f, 0.f};
     // lane-static read addresses (buffer 0): k row of (step, read) -> dz row / x pixel at tap (0, 0) in padded coordinates
@@ -783,115 +897,11 @@ __global__ __launch_bounds__(512, 1) void segwgrad_bf16_kernel(const float* __re
 #pragma unroll
         for (int j = 0; j < C::NTW; ++j) acc[m][j] = zero16();
 
-    f32x4 vx[C::NVX], vz[C::NVZ];
-    // BN: the pooled gradients (and arg-max pixels) of the <= 2 windows that contain the element's pixel
-    f32x4 vd0[BN ? C::NVZ : 1], vd1[(BN && !IDENT) ? C::NVZ : 1];
-    sc_i32x4 va0[(BN && !IDENT) ? C::NVZ : 1], va1[(BN && !IDENT) ? C::NVZ : 1];
-    // this thread's four channels are the same in every element it stages (512 * 4 % CO == 0): their constants once
-    f32x4 bn_g, bn_b, bn_mu, bn_rs, bn_m1, bn_m2;
-    f32x4 vdr[BN ? C::NVZ : 1];                                  // Dropout2d multipliers of the element's (segment, channels)
-    if (BN) {
-        const int ch = (4 * tid0) % CO;
-        const double inv = 1.0 / ((double)n_segments * C::PXZ);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float mu = bn.mean_rstd[ch + e], rs = bn.mean_rstd[CO + ch + e];
-            bn_mu[e] = mu;
-            bn_rs[e] = rs;
-            bn_g[e] = bn.gamma[ch + e] * rs;
-            bn_b[e] = bn.beta[ch + e] - mu * bn_g[e];
-            bn_m1[e] = (float)(bn.sums2[ch + e] * inv);
-            bn_m2[e] = (float)((double)rs * (bn.sums2[CO + ch + e] - (double)mu * bn.sums2[ch + e]) * inv);
-        }
-        if (blockIdx.x == 0 && tid0 < CO) {                     // the BatchNorm parameter gradients (what the dense kernel's block 0 wrote)
-            const double mean = bn.mean_rstd[tid0], rstd = bn.mean_rstd[CO + tid0];
-            bn.dbeta[tid0] = (float)bn.sums2[tid0];
-            bn.dgamma[tid0] = (float)(rstd * (bn.sums2[CO + tid0] - mean * bn.sums2[tid0]));
-        }
-    }
-    auto request = [&](int grp, int tid) {
-        const int seg0 = grp * SEGS;
-        const int nseg = grp < n_groups ? min(SEGS, n_segments - seg0) : 0;
-        const f32x4* gx = (const f32x4*)(x + (size_t)seg0 * C::PXI * CI);
-        const f32x4* gz = (const f32x4*)((BN ? bn.z : dz) + (size_t)seg0 * C::PXZ * CO);
-#pragma unroll
-        for (int j = 0; j < C::NVX; ++j) {
-            const int i = tid + 512 * j;
-            vx[j] = i < nseg * C::PXI * CI / 4 ? gx[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int j = 0; j < C::NVZ; ++j) {
-            const int i = tid + 512 * j;
-            const bool ok = i < nseg * C::PXZ * CO / 4;
-            vz[j] = ok ? gz[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-            if (BN) {
-                const int pix = (4 * i) / CO, c = (4 * i) % CO;
-                const int sg = pix / C::PXZ, p = pix - sg * C::PXZ;
-                vdr[j] = (ok && bn.drop) ? *(const f32x4*)(bn.drop + (size_t)(seg0 + sg) * CO + c) : f32x4{1.f, 1.f, 1.f, 1.f};
-                if (IDENT) {
-                    vd0[j] = ok ? *(const f32x4*)(bn.dy + ((size_t)(seg0 + sg) * C::PXZ + p) * CO + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-                } else {
-                    const int yy = p / WO, xx = p - yy * WO;
-                    const int oy = yy / (H / PH);
-                    int oa = (xx * PW) / WO;                    // the window whose floor bound is at or below xx ...
-                    if (oa > 0 && sc_win_hi(oa - 1, WO, PW) > xx) --oa;      // ... or the one before it when that still covers xx
-                    const int ob = oa + 1;
-                    const bool has_b = ob < PW && sc_win_lo(ob, WO, PW) <= xx;
-                    const size_t o0 = ((size_t)(seg0 + sg) * (PH * PW) + oy * PW + oa) * CO + c;
-                    const size_t o1 = ((size_t)(seg0 + sg) * (PH * PW) + oy * PW + ob) * CO + c;
-                    vd0[j] = ok ? *(const f32x4*)(bn.dy + o0) : f32x4{0.f, 0.f, 0.f, 0.f};
-                    va0[j] = ok ? *(const sc_i32x4*)(bn.arg + o0) : sc_i32x4{-1, -1, -1, -1};
-                    vd1[j] = (ok && has_b) ? *(const f32x4*)(bn.dy + o1) : f32x4{0.f, 0.f, 0.f, 0.f};
-                    va1[j] = (ok && has_b) ? *(const sc_i32x4*)(bn.arg + o1) : sc_i32x4{-1, -1, -1, -1};
-                }
-            }
-        }
-    };
-    auto deposit = [&](unsigned buf, int tid, int grp) {         // split and store the requested group into buffer `buf`
-#pragma unroll
-        for (int j = 0; j < C::NVX; ++j) {
-            const int i = tid + 512 * j;
-            if (C::FX % 512 == 0 || i < C::FX) {
-                const int pix = (4 * i) / CI, c = (4 * i) % CI;
-                const int sg = pix / C::PXI, p = pix - sg * C::PXI, y = p / W, xx = p - y * W;
-                const unsigned a = buf + (unsigned)((sg * C::PXX + (y + 1) * C::XPW + xx + PADW) * C::RSX) + 2 * c;
-                sc_store_terms4<TERMS>(a, C::PLX, vx[j]);
-            }
-        }
-        const int seg0 = grp * SEGS;
-        const int nseg_d = grp < n_groups ? min(SEGS, n_segments - seg0) : 0;
-#pragma unroll
-        for (int j = 0; j < C::NVZ; ++j) {
-            const int i = tid + 512 * j;
-            if (C::FZ % 512 == 0 || i < C::FZ) {
-                const int pix = (4 * i) / CO, c = (4 * i) % CO;
-                f32x4 dzv = vz[j];
-                if (BN) {
-                    const bool ok = i < nseg_d * C::PXZ * CO / 4;
-                    const int sg = pix / C::PXZ, p = pix - sg * C::PXZ;
-                    const f32x4 zi = vz[j];
-                    f32x4 acc;
-                    if (IDENT) acc = vd0[j];
-                    else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) acc[e] = (va0[j][e] == p ? vd0[j][e] : 0.f) + (va1[j][e] == p ? vd1[j][e] : 0.f);
-                    }
-                    acc *= vdr[j];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float zv = zi[e];
-                        asm volatile("" : "+v"(zv));              // scalar gates: packed, hipcc emits the op_sel form of DESIGN.md 7.1
-                        const float a_ = fmaf(zv, bn_g[e], bn_b[e]) > 0.f ? acc[e] : 0.f;
-                        const float xh = (zv - bn_mu[e]) * bn_rs[e];
-                        dzv[e] = ok ? bn_g[e] * (a_ - bn_m1[e] - xh * bn_m2[e]) : 0.f;
-                    }
-                    if (ok) *(f32x4*)(bn.dz_out + (size_t)seg0 * C::PXZ * CO + (size_t)4 * i) = dzv;
-                }
-                const unsigned a = buf + C::ZB + (unsigned)(pix * C::RSZ) + 2 * c;
-                sc_store_terms4<TERMS>(a, C::PLZ, dzv);
-            }
-        }
-    };
+    segw_stage<C, CI, CO, H, W, WO, SEGS, PH, PW> stage(x, dz, bn, n_segments, tid0);
+    // (through lambdas, unlike the fp32 kernel: called directly, the folded 12x5 32>64 instantiations come out with the operands of
+    // one address add in the K loop swapped; the fp32 kernel changes the other way round)
+    auto request = [&](int g, int t) { stage.request(g, t); };
+    auto deposit = [&](unsigned b, int t, int g) { stage.deposit(b, t, g); };
 
     int grp = blockIdx.x;
     request(grp, tid0);
@@ -900,7 +910,7 @@ __global__ __launch_bounds__(512, 1) void segwgrad_bf16_kernel(const float* __re
     __syncthreads();
     unsigned cur = 0u;
     NQ_SUM_BEGIN();
-    for (; grp < n_groups; grp += gridDim.x) {
+    for (; grp < stage.n_groups; grp += gridDim.x) {
         int tid = tid0;
         asm volatile("" : "+v"(tid));                          // keep the staging addresses inside the loop
         request(grp + gridDim.x, tid);                          // the next group travels while this one is multiplied
@@ -945,14 +955,14 @@ __global__ __launch_bounds__(512, 1) void segwgrad_bf16_kernel(const float* __re
     NQ_SUM_END(g_sc_clk, blockIdx.x * 8 + wave, lane0 == 0);
 }
 
-template <int CI, int CO, int H, int W, int WO, int PADW, int SEGS, int MSPLIT, int PH, int PW, int TERMS>
+// The launch of either kernel: the LDS opt-in of this instantiation, one 512-thread workgroup per CU at the most, each walking
+// the groups blockIdx.x, blockIdx.x + gridDim.x, ...
+template <auto KERNEL, unsigned LDS, int SEGS>
 static int segwgrad_launch(hipStream_t st, const float* x, const float* dz, float* dw, int n_segments, segw_bn bn) {
-    typedef segwgrad_cfg<CI, CO, H, W, WO, PADW, SEGS, MSPLIT, TERMS> C;
-    const auto kernel = segwgrad_bf16_kernel<CI, CO, H, W, WO, PADW, SEGS, MSPLIT, PH, PW, TERMS>;
     static std::atomic<bool> lds_ok[64];
-    if (nq_lds_opt_in((const void*)kernel, (int)C::LDS, lds_ok)) return 2;
+    if (nq_lds_opt_in((const void*)KERNEL, (int)LDS, lds_ok)) return 2;
     const int n_groups = (n_segments + SEGS - 1) / SEGS;
-    hipLaunchKernelGGL(kernel, dim3(n_groups < sc_cu_count() ? n_groups : sc_cu_count()), dim3(512), C::LDS, st, x, dz, dw, n_segments, bn);
+    hipLaunchKernelGGL(KERNEL, dim3(n_groups < sc_cu_count() ? n_groups : sc_cu_count()), dim3(512), LDS, st, x, dz, dw, n_segments, bn);
     return 0;
 }
 
@@ -972,27 +982,38 @@ static constexpr segwgrad_tile SEGWGRAD_TILE[2][sc_shapes::N] = {
     {{1, 1}, {1, 2}, {1, 1}, {4, 1}, {8, 1}},
     {{1, 1}, {1, 2}, {1, 1}, {2, 1}, {4, 1}},
 };
-// dw[co][9 * ci] += dz^T * patches(x)  (dw zeroed by the caller, as for nisqa_conv3x3_gemm mode 2).  Folded (bn != NULL): (ho, wo)
-// must be the shape's own pooled size, dz is computed from bn and written to bn->dz_out.
+// the 16-bit kernel of shape S, two or three terms; PH = PW = 0: the plain form
 template <int TERMS>
+struct segw_bf16_kernels {
+    template <typename S, int PH, int PW>
+    static int launch(hipStream_t st, const float* x, const float* dz, float* dw, int n_segments, segw_bn bn) {
+        constexpr segwgrad_tile T = SEGWGRAD_TILE[TERMS == 3][S::I];
+        typedef segwgrad_cfg<S::CI, S::CO, S::H, S::W, S::WO, S::PADW, T.segs, T.msplit, TERMS> C;
+        return segwgrad_launch<segwgrad_bf16_kernel<S::CI, S::CO, S::H, S::W, S::WO, S::PADW, T.segs, T.msplit, PH, PW, TERMS>, C::LDS, T.segs>(
+            st, x, dz, dw, n_segments, bn);
+    }
+};
+// dw[co][9 * ci] += dz^T * patches(x)  (dw zeroed by the caller, as for nisqa_conv3x3_gemm mode 2) with the kernels K
+// (segw_bf16_kernels<TERMS> or segw_f32_kernels).  Folded (bn != NULL): (ho, wo) must be the shape's own pooled size, dz is computed
+// from bn and written to bn->dz_out.
+template <typename K>
 static int segwgrad_dispatch(const float* x, const float* dz, float* dw, int32_t n_segments, int32_t h, int32_t w, int32_t ci,
                              int32_t co, int32_t pad_w, const segw_bn* bn, int32_t ho, int32_t wo, void* stream) {
     if (!segw_args_ok(x, dz, dw, n_segments, bn)) return NISQA_ERR_ARG;
     return sc_shapes::for_shape(h, w, ci, co, pad_w, [&](auto shape) -> int {
         typedef decltype(shape) S;
-        constexpr segwgrad_tile T = SEGWGRAD_TILE[TERMS == 3][S::I];
         if (bn && (ho != S::PH || wo != S::PW)) return NISQA_ERR_ARG;
         hipStream_t st = (hipStream_t)stream;
         NQ_LAUNCH_BEGIN();
-        const int rc = bn ? segwgrad_launch<S::CI, S::CO, S::H, S::W, S::WO, S::PADW, T.segs, T.msplit, S::PH, S::PW, TERMS>(st, x, nullptr, dw, n_segments, *bn)
-                          : segwgrad_launch<S::CI, S::CO, S::H, S::W, S::WO, S::PADW, T.segs, T.msplit, 0, 0, TERMS>(st, x, dz, dw, n_segments, segw_bn{});
+        const int rc = bn ? K::template launch<S, S::PH, S::PW>(st, x, nullptr, dw, n_segments, *bn)
+                          : K::template launch<S, 0, 0>(st, x, dz, dw, n_segments, segw_bn{});
         return rc ? rc : NQ_LAUNCH_STATUS();
     });
 }
 
 extern "C" int nisqa_segconv_wgrad_bf16(const float* x, const float* dz, float* dw, int32_t n_segments, int32_t h, int32_t w,
                                         int32_t ci, int32_t co, int32_t pad_w, void* stream) {
-    return segwgrad_dispatch<2>(x, dz, dw, n_segments, h, w, ci, co, pad_w, nullptr, 0, 0, stream);
+    return segwgrad_dispatch<segw_bf16_kernels<2>>(x, dz, dw, n_segments, h, w, ci, co, pad_w, nullptr, 0, 0, stream);
 }
 // The folded form only: NISQA_ERR_ARG for anything else (callers then run nisqa_bn_act_pool_bwd + nisqa_segconv_wgrad_bf16).
 extern "C" int nisqa_segconv_wgrad_bn_bf16(const float* x, const float* z, const float* dy, const int32_t* arg, const float* drop,
@@ -1000,7 +1021,7 @@ extern "C" int nisqa_segconv_wgrad_bn_bf16(const float* x, const float* z, const
                                            float* dz_out, float* dgamma, float* dbeta, float* dw, int32_t n_segments, int32_t h,
                                            int32_t w, int32_t ci, int32_t co, int32_t pad_w, int32_t ho, int32_t wo, void* stream) {
     const segw_bn bn = {z, dy, arg, drop, mean_rstd, gamma, beta, sums2, dz_out, dgamma, dbeta};
-    return segwgrad_dispatch<2>(x, nullptr, dw, n_segments, h, w, ci, co, pad_w, &bn, ho, wo, stream);
+    return segwgrad_dispatch<segw_bf16_kernels<2>>(x, nullptr, dw, n_segments, h, w, ci, co, pad_w, &bn, ho, wo, stream);
 }
 // The weight gradient at fp32 OPERAND precision on the bf16 matrix pipe (precision mode 'bf16x6'): x and dz as three exact bf16
 // terms, six products; the contract of nisqa_segconv_wgrad_f32 (z == NULL: dz_out holds dz on entry and nothing is folded;
@@ -1010,7 +1031,7 @@ extern "C" int nisqa_segconv_wgrad_bf16x6(const float* x, const float* z, const 
                                           float* dz_out, float* dgamma, float* dbeta, float* dw, int32_t n_segments, int32_t h, int32_t w,
                                           int32_t ci, int32_t co, int32_t pad_w, int32_t ho, int32_t wo, void* stream) {
     const segw_bn bn = {z, dy, arg, drop, mean_rstd, gamma, beta, sums2, dz_out, dgamma, dbeta};
-    return segwgrad_dispatch<3>(x, dz_out, dw, n_segments, h, w, ci, co, pad_w, z ? &bn : nullptr, ho, wo, stream);
+    return segwgrad_dispatch<segw_bf16_kernels<3>>(x, dz_out, dw, n_segments, h, w, ci, co, pad_w, z ? &bn : nullptr, ho, wo, stream);
 }
 
 // ======================================================================================================================
@@ -1022,8 +1043,8 @@ extern "C" int nisqa_segconv_wgrad_bf16x6(const float* x, const float* z, const 
 // [pixel][channel], keeps its share of dw in registers over all the groups it walks, and adds it to dw once.  An MFMA takes
 // one dword per lane and operand: A = dz[pixel 2 s + (lane >> 5)][co], B = x[that pixel + tap][ci], both ds_read_b32 on 32
 // consecutive words per lane half (conflict-free at any row stride).  The eight waves split (M tiles) x (N tiles) x (K steps):
-// every wave holds NTW accumulator tiles of one M tile and walks every KSPLIT-th K step.  PH > 0 folds the BatchNorm backward
-// into the staging exactly like the split-bf16 kernel (segw_bn).
+// every wave holds NTW accumulator tiles of one M tile and walks every KSPLIT-th K step.  The staging, and with it the BatchNorm
+// backward that PH > 0 folds into it (segw_bn), is segw_stage, shared with the split-bf16 kernel.
 // ======================================================================================================================
 template <int CI, int CO, int H, int W, int WO, int PADW, int SEGS, int MSPLIT, int NSPLIT, int KSPLIT>
 struct segwf_cfg {
@@ -1042,20 +1063,22 @@ struct segwf_cfg {
     static constexpr int NVX = (FX + 511) / 512, NVZ = (FZ + 511) / 512;
     static_assert(MSPLIT * NSPLIT * KSPLIT == 8 && MT == MSPLIT, "eight waves; one M tile per wave");
     static_assert(LDS <= 160 * 1024 && BUF % 16 == 0, "LDS");
+    // for segw_stage: rows in words; four channels of an x / a dz pixel are stored as they are
+    static constexpr bool F32 = true;
+    static constexpr int PAD = PADW;
+    static constexpr unsigned ZB = XB;                       // inside a buffer: the x plane, then the dz plane
+    NQ_DEV void store_x(unsigned a, f32x4 v) { lds_st128(a, v); }
+    NQ_DEV void store_z(unsigned a, f32x4 v) { lds_st128(a, v); }
 };
 
 template <int CI, int CO, int H, int W, int WO, int PADW, int SEGS, int MSPLIT, int NSPLIT, int KSPLIT, int PH, int PW>
 __global__ __launch_bounds__(512, 1) void segwgrad_f32_kernel(const float* __restrict__ x, const float* __restrict__ dz,
                                                               float* __restrict__ dw, int n_segments, segw_bn bn) {
     typedef segwf_cfg<CI, CO, H, W, WO, PADW, SEGS, MSPLIT, NSPLIT, KSPLIT> C;
-    constexpr bool BN = PH > 0;
-    constexpr bool IDENT = PH == H && PW == WO;
-    static_assert(!BN || (H % PH == 0 && 512 % (CO / 4) == 0), "pooling rows are disjoint; a thread keeps its four channels");
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid0 = threadIdx.x, lane0 = tid0 & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid0 >> 6);
     const int wm = wave % MSPLIT, wn = (wave / MSPLIT) % NSPLIT, wk = wave / (MSPLIT * NSPLIT);
-    const int n_groups = (n_segments + SEGS - 1) / SEGS;
     for (unsigned a = 16u * tid0; a < C::LDS; a += 16u * 512u) *(f32x4*)(smem + a) = f32x4{0.f, 0.f, 0.f, 0.f};   // borders, zero rows
     const int hf = lane0 >> 5, l31 = lane0 & 31;
     // this wave's N tiles: wn, wn + NSPLIT, ...; byte offset of the lane's column (tap, ci) inside an x plane
@@ -1072,121 +1095,18 @@ __global__ __launch_bounds__(512, 1) void segwgrad_f32_kernel(const float* __res
 #pragma unroll
     for (int j = 0; j < C::NTW; ++j) acc[j] = zero16();
 
-    f32x4 vx[C::NVX], vz[C::NVZ];
-    f32x4 vd0[BN ? C::NVZ : 1], vd1[(BN && !IDENT) ? C::NVZ : 1], vdr[BN ? C::NVZ : 1];
-    sc_i32x4 va0[(BN && !IDENT) ? C::NVZ : 1], va1[(BN && !IDENT) ? C::NVZ : 1];
-    f32x4 bn_g, bn_b, bn_mu, bn_rs, bn_m1, bn_m2;
-    if (BN) {
-        const int ch = (4 * tid0) % CO;
-        const double inv = 1.0 / ((double)n_segments * C::PXZ);
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float mu = bn.mean_rstd[ch + e], rs = bn.mean_rstd[CO + ch + e];
-            bn_mu[e] = mu;
-            bn_rs[e] = rs;
-            bn_g[e] = bn.gamma[ch + e] * rs;
-            bn_b[e] = bn.beta[ch + e] - mu * bn_g[e];
-            bn_m1[e] = (float)(bn.sums2[ch + e] * inv);
-            bn_m2[e] = (float)((double)rs * (bn.sums2[CO + ch + e] - (double)mu * bn.sums2[ch + e]) * inv);
-        }
-        if (blockIdx.x == 0 && tid0 < CO) {
-            const double mean = bn.mean_rstd[tid0], rstd = bn.mean_rstd[CO + tid0];
-            bn.dbeta[tid0] = (float)bn.sums2[tid0];
-            bn.dgamma[tid0] = (float)(rstd * (bn.sums2[CO + tid0] - mean * bn.sums2[tid0]));
-        }
-    }
-    auto request = [&](int grp, int tid) {
-        const int seg0 = grp * SEGS;
-        const int nseg = grp < n_groups ? min(SEGS, n_segments - seg0) : 0;
-        const f32x4* gx = (const f32x4*)(x + (size_t)seg0 * C::PXI * CI);
-        const f32x4* gz = (const f32x4*)((BN ? bn.z : dz) + (size_t)seg0 * C::PXZ * CO);
-#pragma unroll
-        for (int j = 0; j < C::NVX; ++j) {
-            const int i = tid + 512 * j;
-            vx[j] = i < nseg * C::PXI * CI / 4 ? gx[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-        }
-#pragma unroll
-        for (int j = 0; j < C::NVZ; ++j) {
-            const int i = tid + 512 * j;
-            const bool ok = i < nseg * C::PXZ * CO / 4;
-            vz[j] = ok ? gz[i] : f32x4{0.f, 0.f, 0.f, 0.f};
-            if (BN) {
-                const int pix = (4 * i) / CO, c = (4 * i) % CO;
-                const int sg = pix / C::PXZ, p = pix - sg * C::PXZ;
-                vdr[j] = (ok && bn.drop) ? *(const f32x4*)(bn.drop + (size_t)(seg0 + sg) * CO + c) : f32x4{1.f, 1.f, 1.f, 1.f};
-                if (IDENT) {
-                    vd0[j] = ok ? *(const f32x4*)(bn.dy + ((size_t)(seg0 + sg) * C::PXZ + p) * CO + c) : f32x4{0.f, 0.f, 0.f, 0.f};
-                } else {
-                    const int yy = p / WO, xx = p - yy * WO;
-                    const int oy = yy / (H / PH);
-                    int oa = (xx * PW) / WO;
-                    if (oa > 0 && sc_win_hi(oa - 1, WO, PW) > xx) --oa;
-                    const int ob = oa + 1;
-                    const bool has_b = ob < PW && sc_win_lo(ob, WO, PW) <= xx;
-                    const size_t o0 = ((size_t)(seg0 + sg) * (PH * PW) + oy * PW + oa) * CO + c;
-                    const size_t o1 = ((size_t)(seg0 + sg) * (PH * PW) + oy * PW + ob) * CO + c;
-                    vd0[j] = ok ? *(const f32x4*)(bn.dy + o0) : f32x4{0.f, 0.f, 0.f, 0.f};
-                    va0[j] = ok ? *(const sc_i32x4*)(bn.arg + o0) : sc_i32x4{-1, -1, -1, -1};
-                    vd1[j] = (ok && has_b) ? *(const f32x4*)(bn.dy + o1) : f32x4{0.f, 0.f, 0.f, 0.f};
-                    va1[j] = (ok && has_b) ? *(const sc_i32x4*)(bn.arg + o1) : sc_i32x4{-1, -1, -1, -1};
-                }
-            }
-        }
-    };
-    auto deposit = [&](unsigned buf, int tid, int grp) {
-#pragma unroll
-        for (int j = 0; j < C::NVX; ++j) {
-            const int i = tid + 512 * j;
-            if (C::FX % 512 == 0 || i < C::FX) {
-                const int pix = (4 * i) / CI, c = (4 * i) % CI;
-                const int sg = pix / C::PXI, p = pix - sg * C::PXI, y = p / W, xx = p - y * W;
-                lds_st128(buf + 4u * (unsigned)((sg * C::PXX + (y + 1) * C::XPW + xx + PADW) * C::RSX + c), vx[j]);
-            }
-        }
-        const int seg0 = grp * SEGS;
-        const int nseg_d = grp < n_groups ? min(SEGS, n_segments - seg0) : 0;
-#pragma unroll
-        for (int j = 0; j < C::NVZ; ++j) {
-            const int i = tid + 512 * j;
-            if (C::FZ % 512 == 0 || i < C::FZ) {
-                const int pix = (4 * i) / CO, c = (4 * i) % CO;
-                f32x4 dzv = vz[j];
-                if (BN) {
-                    const bool ok = i < nseg_d * C::PXZ * CO / 4;
-                    const int sg = pix / C::PXZ, p = pix - sg * C::PXZ;
-                    const f32x4 zi = vz[j];
-                    f32x4 a4;
-                    if (IDENT) a4 = vd0[j];
-                    else {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e) a4[e] = (va0[j][e] == p ? vd0[j][e] : 0.f) + (va1[j][e] == p ? vd1[j][e] : 0.f);
-                    }
-                    a4 *= vdr[j];
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        float zv = zi[e];
-                        asm volatile("" : "+v"(zv));
-                        const float a_ = fmaf(zv, bn_g[e], bn_b[e]) > 0.f ? a4[e] : 0.f;
-                        const float xh = (zv - bn_mu[e]) * bn_rs[e];
-                        dzv[e] = ok ? bn_g[e] * (a_ - bn_m1[e] - xh * bn_m2[e]) : 0.f;
-                    }
-                    if (ok) *(f32x4*)(bn.dz_out + (size_t)seg0 * C::PXZ * CO + (size_t)4 * i) = dzv;
-                }
-                lds_st128(buf + C::XB + 4u * (unsigned)(pix * C::RSZ + c), dzv);
-            }
-        }
-    };
+    segw_stage<C, CI, CO, H, W, WO, SEGS, PH, PW> stage(x, dz, bn, n_segments, tid0);
 
     int grp = blockIdx.x;
-    request(grp, tid0);
+    stage.request(grp, tid0);
     __syncthreads();                                            // the zero fill is complete
-    deposit(0u, tid0, grp);
+    stage.deposit(0u, tid0, grp);
     __syncthreads();
     unsigned cur = 0u;
-    for (; grp < n_groups; grp += gridDim.x) {
+    for (; grp < stage.n_groups; grp += gridDim.x) {
         int tid = tid0;
         asm volatile("" : "+v"(tid));
-        request(grp + gridDim.x, tid);                          // the next group travels while this one is multiplied
+        stage.request(grp + gridDim.x, tid);                    // the next group travels while this one is multiplied
         __builtin_amdgcn_sched_barrier(0);
         // K steps wk, wk + KSPLIT, ...: the pixel pair 2 s + (lane >> 5); its dz row is linear in s, its x row is not (rows of
         // the padded plane are XPW pixels apart): two constant divisions per step
@@ -1219,7 +1139,7 @@ __global__ __launch_bounds__(512, 1) void segwgrad_f32_kernel(const float* __res
                 if (j < NFULL || j < n_own) acc[j] = mfma32(av[0], bv[0][j], acc[j]);
         }
         __builtin_amdgcn_sched_barrier(0);
-        deposit(C::BUF - cur, tid, grp + (int)gridDim.x);
+        stage.deposit(C::BUF - cur, tid, grp + (int)gridDim.x);
         __syncthreads();
         cur = C::BUF - cur;
     }
@@ -1238,22 +1158,21 @@ __global__ __launch_bounds__(512, 1) void segwgrad_f32_kernel(const float* __res
     }
 }
 
-template <int CI, int CO, int H, int W, int WO, int PADW, int SEGS, int MSPLIT, int NSPLIT, int KSPLIT, int PH, int PW>
-static int segwgrad_f32_launch(hipStream_t st, const float* x, const float* dz, float* dw, int n_segments, segw_bn bn) {
-    typedef segwf_cfg<CI, CO, H, W, WO, PADW, SEGS, MSPLIT, NSPLIT, KSPLIT> C;
-    const auto kernel = segwgrad_f32_kernel<CI, CO, H, W, WO, PADW, SEGS, MSPLIT, NSPLIT, KSPLIT, PH, PW>;
-    static std::atomic<bool> lds_ok[64];
-    if (nq_lds_opt_in((const void*)kernel, (int)C::LDS, lds_ok)) return 2;
-    const int n_groups = (n_segments + SEGS - 1) / SEGS;
-    hipLaunchKernelGGL(kernel, dim3(n_groups < sc_cu_count() ? n_groups : sc_cu_count()), dim3(512), C::LDS, st, x, dz, dw, n_segments, bn);
-    return 0;
-}
-
 // segments per group and the split of the eight waves over (M tiles) x (N tiles) x (K steps), per shape
 struct segwf_tile { int segs, msplit, nsplit, ksplit; };
 static constexpr segwf_tile SEGWF_TILE[sc_shapes::N] = {
     //  24x7 16>32    12x5 32>64    12x5 64>64    6x3 64>64     6x3 64>64 pad 0
     {1, 1, 1, 8}, {1, 2, 2, 2}, {1, 2, 4, 1}, {4, 2, 4, 1}, {8, 2, 4, 1},
+};
+// the fp32 kernel of shape S for segwgrad_dispatch; PH = PW = 0: the plain form
+struct segw_f32_kernels {
+    template <typename S, int PH, int PW>
+    static int launch(hipStream_t st, const float* x, const float* dz, float* dw, int n_segments, segw_bn bn) {
+        constexpr segwf_tile T = SEGWF_TILE[S::I];
+        typedef segwf_cfg<S::CI, S::CO, S::H, S::W, S::WO, S::PADW, T.segs, T.msplit, T.nsplit, T.ksplit> C;
+        return segwgrad_launch<segwgrad_f32_kernel<S::CI, S::CO, S::H, S::W, S::WO, S::PADW, T.segs, T.msplit, T.nsplit, T.ksplit, PH, PW>, C::LDS, T.segs>(
+            st, x, dz, dw, n_segments, bn);
+    }
 };
 // exact fp32, the same contract as nisqa_segconv_wgrad_bf16 / nisqa_segconv_wgrad_bn_bf16 (z == NULL: dz_out holds dz on entry and
 // nothing is folded; otherwise the BatchNorm backward runs inside and dz_out, dgamma, dbeta are written)
@@ -1262,16 +1181,5 @@ extern "C" int nisqa_segconv_wgrad_f32(const float* x, const float* z, const flo
                                        float* dz_out, float* dgamma, float* dbeta, float* dw, int32_t n_segments, int32_t h, int32_t w,
                                        int32_t ci, int32_t co, int32_t pad_w, int32_t ho, int32_t wo, void* stream) {
     const segw_bn bn = {z, dy, arg, drop, mean_rstd, gamma, beta, sums2, dz_out, dgamma, dbeta};
-    const bool fold = z != nullptr;
-    if (!segw_args_ok(x, dz_out, dw, n_segments, fold ? &bn : nullptr)) return NISQA_ERR_ARG;
-    return sc_shapes::for_shape(h, w, ci, co, pad_w, [&](auto shape) -> int {
-        typedef decltype(shape) S;
-        constexpr segwf_tile T = SEGWF_TILE[S::I];
-        if (fold && (ho != S::PH || wo != S::PW)) return NISQA_ERR_ARG;
-        hipStream_t st = (hipStream_t)stream;
-        NQ_LAUNCH_BEGIN();
-        const int rc = fold ? segwgrad_f32_launch<S::CI, S::CO, S::H, S::W, S::WO, S::PADW, T.segs, T.msplit, T.nsplit, T.ksplit, S::PH, S::PW>(st, x, nullptr, dw, n_segments, bn)
-                            : segwgrad_f32_launch<S::CI, S::CO, S::H, S::W, S::WO, S::PADW, T.segs, T.msplit, T.nsplit, T.ksplit, 0, 0>(st, x, dz_out, dw, n_segments, segw_bn{});
-        return rc ? rc : NQ_LAUNCH_STATUS();
-    });
+    return segwgrad_dispatch<segw_f32_kernels>(x, dz_out, dw, n_segments, h, w, ci, co, pad_w, z ? &bn : nullptr, ho, wo, stream);
 }

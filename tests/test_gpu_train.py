@@ -305,6 +305,18 @@ def test_segment_resident_convolutions_forward_dgrad_wgrad(h, w, ci, co, pad_w, 
 @pytest.mark.parametrize('h,w,ci,co,pad_w,ho,wo', [(24, 7, 16, 32, 1, 12, 5), (12, 5, 32, 64, 1, 12, 5), (12, 5, 64, 64, 1, 6, 3),
                                                    (6, 3, 64, 64, 1, 6, 3), (6, 3, 64, 64, 0, 6, 1)])
 def test_segment_resident_fp32_weight_gradient_with_and_without_the_batchnorm_backward(h, w, ci, co, pad_w, ho, wo, S):
+    _segw_fold_case(h, w, ci, co, pad_w, ho, wo, S)
+
+
+@pytest.mark.parametrize('h,w,ci,co,pad_w,ho,wo', [(6, 3, 64, 64, 1, 6, 3), (6, 3, 64, 64, 0, 6, 1)])
+def test_segment_resident_weight_gradient_second_group_of_a_workgroup_with_a_partial_last_group(h, w, ci, co, pad_w, ho, wo):
+    """The 6x3 shapes stage 2, 4 or 8 segments per group, so at 300 segments no workgroup walks a second group: the second trip
+    of the double-buffered loop needs more groups than CUs.  8 CUs + 3 segments = more than one group per workgroup with a
+    partial last group at every group size of the tile tables (2051 on 256 CUs: 2 * 1025 + 1, 4 * 512 + 3, 8 * 256 + 3)."""
+    _segw_fold_case(h, w, ci, co, pad_w, ho, wo, 8 * torch.cuda.get_device_properties(DEV).multi_processor_count + 3)
+
+
+def _segw_fold_case(h, w, ci, co, pad_w, ho, wo, S):
     """nisqa_segconv_wgrad_f32 (exact fp32 MFMA, precision mode 'f32') and nisqa_segconv_wgrad_bf16x6 (three exact bf16 terms per
     operand, six products: mode 'bf16x6', the SAME bounds): (i) handed dz, against autograd's weight gradient;
     (ii) handed z and the pooled gradient (BatchNorm / ReLU / max-pool / Dropout2d backward folded into its staging), against
