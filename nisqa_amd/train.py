@@ -216,6 +216,10 @@ class _FlatTrainer(object):
 
     def _sum_rows(self, n=1):
         """The next n rows of the step's float64 sums (zeroed by _prepare), flat."""
+        if n < 1 or self._sum_i + n > self._sums.shape[0]:
+            # a slice past the end is a short (or empty) view in torch, and the kernel behind it would write its sums out of bounds
+            raise RuntimeError('training step: float64 sum rows exhausted ({} in use, {} more asked for, {} allocated)'.format(
+                self._sum_i, n, self._sums.shape[0]))
         s = self._sums[self._sum_i:self._sum_i + n].view(-1)
         self._sum_i += n
         return s
@@ -794,7 +798,9 @@ class HipTrainer(_AttTrainer):
         self.p_cnn, self.p_td, self.p_pool = float(a['cnn_dropout']), float(a['td_sa_dropout']), float(a['pool_att_dropout'] or 0)
         if self.p_pool:
             raise NotImplementedError('pool_att_dropout > 0 is not built (0 in every shipped config)')
-        self._init_params(state_dict, 96 + 24 * len(self.heads))
+        # the operator path spends six rows of sums per layer (two LayerNorms, four Linears); layers past the fused block's four
+        # get rows of their own, so that its depth is limited by _sum_rows' check only in name
+        self._init_params(state_dict, 96 + 24 * len(self.heads) + 8 * max(0, self.n_layers - 4))
         self._td_poff = self._td_param_offsets()
         geo = [(48, 15, pools[0]), (24, 7, pools[1]), (12, 5, (12, 5)), (12, 5, pools[2]), (6, 3, (6, 3)), (6, 1, (6, 1))]
         self._init_cnn(geo, 0, self.lib.nisqa_conv1_bn_act_pool_fwd, self.lib.nisqa_conv1_bn_act_pool_bwd)
